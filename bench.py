@@ -7,17 +7,25 @@ the rank's 1 GiB shard (both checksums, bytes read once).  N > 1: weak scaling -
 shard of one N GiB logical buffer; the only exchange is the all-gather of {adler, crc, len} (16 bytes per rank over
 RCCL) followed by the ordered on-device combine.
 
-The same line carries a `streams` object at every N (BASELINE.json configs[4], the north_star's multi-stream
+With --full the same line carries a `streams` object at every N (BASELINE.json configs[4], the north_star's multi-stream
 curve): 4096 independent 1 MiB streams, level-1 class, sharded over the N ranks (strong scaling), the {clen,
 adler32, ulen} table all-gathered over RCCL; `streams.value` at N = 1, 2, 4, 8 is the 1 -> 8 GPU scaling curve.
 And the two single-stream members of the metric, `deflate_lvl6` (configs[3]) and `inflate` (configs[2]): one 256 MiB
 stream per GPU (a single stream does not shard: replicas at N > 1).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (N > 1, the driver's form)
 `python bench.py --gpus N` with N > 1 and no launcher around it starts its own N ranks (self_launch(): a child
 `torch.distributed.run`, started before this process has imported torch or touched HIP) and relays rank 0's line.
 Rank 0 prints ONE JSON line.
+
+A plain run does only what the top-level line needs: set-up, the untimed settle launches, W warm-up steps, K timed
+steps, the line.  `--full` adds everything else: the single-checksum kernel rates, the device-copy ceiling, the CPU
+baseline and its check against the GPU result, and the `streams` / `deflate_lvl6` / `inflate` objects.
+`--dump-outputs DIR` writes what the timed path returned in its last step as DIR/<name>.npy (float64): `checksums`
+= {adler32, crc32} of rank 0's shard, and at N > 1 (or ZNG_BENCH_FORCE_DIST=1) `combined` = the ordered combine over
+all ranks; `--workload streams` writes `streams_table`, the {clen, adler32, ulen} row of every stream.  The inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import importlib
@@ -221,11 +229,11 @@ def copy_ceiling(torch, buf):
     return 2 * buf.numel() / 1e9 / (ms / 1e3)
 
 
-def run_streams(args, zr, par, torch, dist, dev, world, rank, rehearse, steps, warmup):
+def run_streams(args, zr, par, torch, dist, dev, world, rank, rehearse, steps, warmup, dump=None):
     """BASELINE.json configs[4]: `--streams` independent 1 MiB streams, level-1 class, sharded over the ranks
     (strong scaling: the total is fixed).  Step = every rank compresses its shard (LZ77 parse + static-Huffman emit)
     and the {clen, adler32, ulen} table is all-gathered (RCCL, 24 bytes per stream) and prefix-summed on every rank.
-    Returns the `streams` object (rank 0) or None."""
+    Returns the `streams` object (rank 0) or None; `dump` (a directory, rank 0) receives the last step's table."""
     import zlib
 
     import numpy as np
@@ -309,6 +317,9 @@ def run_streams(args, zr, par, torch, dist, dev, world, rank, rehearse, steps, w
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = t.item()
+    table = state["table"].cpu()
+    if dump and rank == 0:
+        dump_outputs(dump, {"streams_table": table.numpy()})
     # the exchange by itself (latency bound: tens of KiB), reported separately as SURVEY.md 8e asks
     fence()
     ea, eb = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -318,7 +329,6 @@ def run_streams(args, zr, par, torch, dist, dev, world, rank, rehearse, steps, w
     eb.record()
     eb.synchronize()
     exchange_us = ea.elapsed_time(eb) / 10 * 1e3
-    table = state["table"].cpu()
     # parity on this rank: first and last local stream round-trip through an independent inflater, every local
     # Adler-32 row equals that of its slice
     res = batch.results.cpu()
@@ -517,6 +527,14 @@ def emit(line):
 _REAL_STDOUT = 1
 
 
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as dirname/<name>.npy in float64 (u32 / i64 values up to 2^53 stay exact)"""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -546,18 +564,30 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--shard-mib", type=int, default=SHARD_BYTES >> 20)
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything besides the top-level line: single-checksum kernel rates, "
+                         "device-copy ceiling, cpu_baseline, and (default workload `all`) the streams / deflate_lvl6 / "
+                         "inflate legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline legs")
     ap.add_argument("--settle", type=int, default=SETTLE_LAUNCHES, help="untimed launches in front of the warm-up (disclosed in the line)")
-    ap.add_argument("--workload", choices=("all", "checksum", "streams"), default="all",
+    ap.add_argument("--workload", choices=("all", "checksum", "streams"), default=None,
                     help="all = BASELINE.json configs[1] as the top-level line (the driver's contract) plus the "
-                         "configs[4] `streams` object; checksum = the top-level line only; streams = configs[4] only, "
-                         "printed as the line")
+                         "configs[4] `streams` object and the single-stream legs (implies --full); checksum = the "
+                         "top-level line only; streams = configs[4] only, printed as the line.  Default: all with "
+                         "--full, checksum without")
     ap.add_argument("--streams", type=int, default=4096)
     ap.add_argument("--stream-steps", type=int, default=0, help="timed steps of the streams leg (0 = min(steps, 6))")
     ap.add_argument("--launch-only", action="store_true",
                     help="every rank prints {rank, world, local_rank} as one JSON line and exits: exercises the launcher "
                          "without a GPU (tests/test_bench_launch.py)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.workload is None:
+        args.workload = "all" if args.full else "checksum"
+    full = args.full or args.workload == "all"
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -607,7 +637,8 @@ def main():
     stream_warm = max(1, min(args.warmup, 2))
 
     if args.workload == "streams":
-        s = run_streams(args, zr, par, torch, dist, dev, world, rank, rehearse, args.steps, args.warmup)
+        s = run_streams(args, zr, par, torch, dist, dev, world, rank, rehearse, args.steps, args.warmup,
+                        dump=args.dump_outputs)
         if rank == 0:
             line = {"metric": METRIC, "value": s["value"], "unit": "GB/s", "n_gpus": world, "steps": args.steps,
                     "warmup": max(1, args.warmup), "ms_per_step": s["ms_per_step"], "higher_is_better": True,
@@ -771,9 +802,15 @@ def main():
         assert got_total == [folded[0], folded[1]], (got_total, folded)
         assert rows[rank][:2] == result and all(r[2] == n for r in rows)
         zr.reserve_cus(0)
-    # separate single-checksum timings (outside the timed region, informational)
+    if args.dump_outputs and rank == 0:
+        arrays = {"checksums": result}
+        if multi:
+            arrays["combined"] = got_total
+        dump_outputs(args.dump_outputs, arrays)
+    # --full: separate single-checksum timings and the device-copy ceiling (outside the timed region, informational)
     extra = {}
-    for name, fn in (("adler32", lambda: zr.adler32_dev(buf, out)), ("crc32", lambda: zr.crc32_dev(buf, out))):
+    singles = (("adler32", lambda: zr.adler32_dev(buf, out)), ("crc32", lambda: zr.crc32_dev(buf, out))) if full else ()
+    for name, fn in singles:
         for _ in range(50):
             fn()
         torch.cuda.synchronize()
@@ -782,7 +819,7 @@ def main():
             fn()
         ms = zr.trace_end(20)
         extra[name + "_kernel_GBps"] = round(n / 1e9 / (statistics.mean(ms) / 1e3), 1)
-    measured_copy = copy_ceiling(torch, buf) if rank == 0 else None
+    measured_copy = copy_ceiling(torch, buf) if rank == 0 and full else None
 
     line = None
     if rank == 0:
@@ -829,13 +866,16 @@ def main():
                 "avg_kernel_ms": round(k_avg_ms, 5),
                 "launches_timed": len(kernel_ms),
                 "launches_sampled_every": stride,
-                "measured_copy_GBps": round(measured_copy, 1),
-                "frac_of_measured_copy": round(achieved / measured_copy, 4),
-                "measured_copy": "torch device-to-device copy of the same %d MiB buffer, 2N bytes per copy, on this box" % (n >> 20),
             },
         }
+        if measured_copy is not None:
+            line["roofline"].update({
+                "measured_copy_GBps": round(measured_copy, 1),
+                "frac_of_measured_copy": round(achieved / measured_copy, 4),
+                "measured_copy": "torch device-to-device copy of the same %d MiB buffer, 2N bytes per copy, on this GPU" % (n >> 20),
+            })
         line.update(extra)
-        if not args.no_cpu:
+        if full and not args.no_cpu:
             host = buf.cpu().numpy()
             cb, (a, c) = cpu_baseline(host, zr)
             assert [a, c] == result, "GPU result differs from the CPU checker: %r vs %r" % (result, [a, c])

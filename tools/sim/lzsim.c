@@ -1,6 +1,7 @@
 // lzsim.c -- CPU model of the level-6 class match finders, to choose the LDS search structure before writing the
 // kernel.  Not product code, not the oracle: it estimates the compressed size a finder would
 // give on a plaintext file (serial greedy + one-step-lazy parse, per-segment Shannon cost of the dynamic block).
+//   cc -O2 -o lzsim lzsim.c -lm
 //   ./lzsim file chain HBITS MAXCHAIN            hash chains (head 2^HBITS, prev deltas): round-2 kernel's structure
 //   ./lzsim file row ROWS ENTRIES TAGBITS MAXCAND   associative rows: ROWS x ENTRIES (pos16, tag) FIFO per row
 #include <math.h>
