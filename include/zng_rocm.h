@@ -314,6 +314,16 @@ int  zng_rocm_inflate_tokens_decode(const uint8_t *src, size_t src_len, zng_rocm
  * before it is "invalid distance too far back" (inffast_tpl.h:198-226 with whave = window_len) */
 int  zng_rocm_inflate_tokens_decode_window(const uint8_t *src, size_t src_len, uint32_t window_len,
                                            zng_rocm_inflate_tokens *out);
+/* Every COMPLETE block of a raw stream from bit `start_bit` of src on (a block header starts there), continuing
+ * `window_len` bytes of history.  1 = the BFINAL block was decoded, *end_bit = first bit behind it; 0 = the input ends
+ * inside a block: the tokens describe every block that ended inside src, *end_bit = the bit where the first incomplete
+ * block starts (== start_bit when none completed); -3 = Z_DATA_ERROR with the reference's text in out->msg, the tokens
+ * describe the complete blocks before the failing one, *end_bit = its start; -4 = out of memory.  `out` is zeroed and
+ * *end_bit = start_bit on every return, ZNG_ROCM_EINVAL (a refused argument, e.g. start_bit beyond 8 * src_len) included;
+ * out->msg is set on a data error only.  The streaming form of
+ * inflate's TYPEDO (inflate.c:728): what a Z_SYNC_FLUSH promises the decompressor, it gets. */
+int  zng_rocm_inflate_tokens_decode_blocks(const uint8_t *src, size_t src_len, uint64_t start_bit, uint32_t window_len,
+                                           zng_rocm_inflate_tokens *out, uint64_t *end_bit);
 void zng_rocm_inflate_tokens_free(zng_rocm_inflate_tokens *t);
 /* Device stage on device-resident token arrays.  d_symbols: workspace of out_len uint16_t;
  * d_out: out_len bytes.  Up to four launches: per-segment resolution into 16-bit symbols (a symbol
@@ -479,6 +489,16 @@ int    zng_rocm_hook_deflate_block(zng_rocm_hook *h, int level, const uint8_t *i
  * -3 (Z_DATA_ERROR) with the reference's strm->msg text in *msg; negative ZNG_ROCM_E* on a device failure. */
 int    zng_rocm_hook_inflate(zng_rocm_hook *h, const uint8_t *in, size_t in_len, int check, uint32_t *check_value,
                              const uint8_t **out, size_t *out_len, size_t *in_used, const char **msg);
+/* Streaming form of zng_rocm_hook_inflate: `in` (host) holds the stream from the byte that contains bit `start_bit`
+ * (0..7) on.  Every complete block is decoded against the history and becomes history; *out / *out_len = its plaintext
+ * (hook memory, valid until the next call), check continues *check_value over it.  Returns 1 / 0 / -3 with *end_bit as
+ * zng_rocm_inflate_tokens_decode_blocks; negative ZNG_ROCM_E* = device failure, nothing produced, history unchanged.
+ * in_len == 0 returns 0 with *end_bit = start_bit and no launch.  A refused argument returns ZNG_ROCM_EINVAL, which has
+ * the value of Z_DATA_ERROR but leaves *msg NULL (a data error always sets it).  From 4 MiB of input on the blocks are
+ * decoded in parts on the device (as zng_rocm_hook_inflate). */
+int    zng_rocm_hook_inflate_blocks(zng_rocm_hook *h, const uint8_t *in, size_t in_len, unsigned start_bit, int check,
+                                    uint32_t *check_value, const uint8_t **out, size_t *out_len, uint64_t *end_bit,
+                                    const char **msg);
 
 /* ---- measurement hooks --------------------------------------------------
  * Between trace_begin and trace_end every (sampled) launch of the DOMINANT kernel of a *_dev entry point (the

@@ -24,11 +24,13 @@ typedef struct {
 
 typedef struct {
     zng_rocm_hook *hook;
-    uint8_t *in_buf;            /* compressed bytes gathered until the stream's end is among them */
+    uint8_t *in_buf;            /* the carry: compressed bytes from the start of the first incomplete block on */
     size_t   in_len, in_cap;
+    unsigned carry_bit;         /* bit of in_buf[0] at which that block starts (0..7) */
     const uint8_t *out;         /* plaintext (memory of the hook) next_out has not had room for yet */
     size_t   out_pos, out_len;
-    uint32_t check;             /* its check value, handed to state->check once everything is delivered */
-    int      used, done, disabled;
+    uint32_t check;             /* check value of the plaintext so far, handed to state->check once the stream is delivered */
+    const char *msg;            /* bad: the reference's text, reported once the blocks in front of the error are delivered */
+    int      used, done, bad, disabled;
 } arch_inflate_state;
 #endif

@@ -1,18 +1,21 @@
 /* arch/rocm/rocm_inflate.c -- INFLATE_TYPEDO_HOOK backend of arch/rocm (inflate.c:728; precedent
  * arch/s390/dfltcc_inflate.c:52-114).  inflate() keeps the wrapper (zlib / gzip header and trailer, inflate.c:509-700,
- * :1105-1147) and the zng_stream bookkeeping; the deflate data between them is decoded by libzng_rocm (token decode on
- * the host, every match copy on the device) and its check value comes back with it (INFLATE_NEED_CHECKSUM = 0).
- * The device takes a stream whole: compressed bytes are gathered until the end of the deflate data is among them -- a
- * decode is attempted on every call that brings input, so whatever lies behind the end (the trailer, a next member) is
- * still inside the caller's current buffer and next_in is set back to it.  A caller that hands over the stream in one
- * piece pays one decode; one that trickles it pays one per call (the software path is the better choice there:
- * ROCM_INFLATE_MIN_BYTES).  Anything the device path cannot do leaves the stream to software BEFORE a byte is consumed. */
+ * :1105-1147) and the zng_stream bookkeeping; the deflate data between them is decoded by libzng_rocm (blocks found and
+ * decoded in parts on the device from 4 MiB of input on, token decode on the host below that, every match copy on the
+ * device) and its check value comes back with it (INFLATE_NEED_CHECKSUM = 0).
+ * The unit of work is the COMPLETE block: a call that brings input decodes every block whose end lies inside the bytes it
+ * has, delivers their plaintext, and keeps only the compressed bytes of the first incomplete block (from its start bit
+ * on) for the next call -- so whatever a Z_SYNC_FLUSH put in front of its marker comes out as soon as the marker is in
+ * (zlib-ng.h.in:285-288), and per call the work and the memory are one piece plus one incomplete block.  The call that
+ * completes the BFINAL block consumes only the bytes up to its end: whatever lies behind it (the trailer, a next member)
+ * stays in next_in.  Anything the device path cannot do leaves the stream to software BEFORE a byte is consumed. */
 #ifdef ZNG_ROCM_STANDALONE_CHECK
 #  include "zlibng_coarse_min.h"
 #else
 #  include "zbuild.h"
 #  include "inflate.h"
 #endif
+#include <assert.h>
 #include <stdlib.h>
 #include <string.h>
 #include "zng_rocm.h"
@@ -35,8 +38,10 @@ static void arch_free(PREFIX3(streamp) strm, void *p) {
 void Z_INTERNAL PREFIX(archrocm_reset_inflate_state)(PREFIX3(streamp) strm) {      /* INFLATE_RESET_KEEP_HOOK, inflate.c:87 */
     arch_inflate_state *a = &((struct inflate_state *)strm->state)->arch;
     a->in_len = a->out_pos = a->out_len = 0;
+    a->carry_bit = 0;
     a->out = NULL;
-    a->used = a->done = 0;
+    a->msg = NULL;
+    a->used = a->done = a->bad = 0;
     if (a->hook && zng_rocm_hook_reset(a->hook) != ZNG_ROCM_OK) a->disabled = 1;
 }
 
@@ -100,25 +105,30 @@ rocm_inflate_action Z_INTERNAL PREFIX(archrocm_inflate)(PREFIX3(streamp) strm, i
         a->disabled = 1;
         return ROCM_INFLATE_SOFTWARE;
     }
+    drain(strm, a);                                     /* plaintext of earlier blocks first */
+    if (a->out_pos < a->out_len) {                      /* next_out is full: no input is taken */
+        *ret = Z_OK;
+        return ROCM_INFLATE_BREAK;
+    }
     if (a->done) {
-        drain(strm, a);
-        if (a->out_pos < a->out_len) {                  /* next_out is full */
-            *ret = Z_OK;
-            return ROCM_INFLATE_BREAK;
-        }
         if (state->wrap & 4) strm->adler = state->check = a->check;
         state->last = 1;
         state->mode = CHECK;                            /* the trailer is inflate()'s, inflate.c:1105-1147 */
         return ROCM_INFLATE_CONTINUE;
     }
-    if (strm->avail_in == 0) {
+    if (a->bad) {                                       /* Z_DATA_ERROR with the reference's text (inflate_p.h:130-134) */
+        strm->msg = a->msg;
+        state->mode = BAD;
+        return ROCM_INFLATE_CONTINUE;
+    }
+    if (strm->avail_in == 0 || strm->avail_out == 0) {  /* no input, or no room for what a decode would produce */
         *ret = Z_OK;                                    /* inflate() turns "no progress" into Z_BUF_ERROR itself */
         return ROCM_INFLATE_BREAK;
     }
-    /* gather; nothing is marked consumed for good until the decode says where the stream ends */
-    const size_t taken = strm->avail_in;
-    if (a->in_cap < a->in_len + taken) {
-        const size_t want = (a->in_len + taken) * 2;
+    /* the carry and this call's input, one buffer; nothing is marked consumed until the decode says where blocks end */
+    const size_t taken = strm->avail_in, total = a->in_len + taken;
+    if (a->in_cap < total) {
+        const size_t want = total * 2;
         uint8_t *n = (uint8_t *)arch_alloc(strm, want);
         if (!n) {
             if (a->used) { *ret = Z_MEM_ERROR; return ROCM_INFLATE_BREAK; }
@@ -133,35 +143,41 @@ rocm_inflate_action Z_INTERNAL PREFIX(archrocm_inflate)(PREFIX3(streamp) strm, i
     memcpy(a->in_buf + a->in_len, strm->next_in, taken);
 
     const int kind = !(state->wrap & 4) ? 0 : state->flags ? 2 : 1;             /* inflate_p.h:47-49: gzip -> crc32, zlib -> adler32 */
-    uint32_t cv = state->check;
+    uint32_t cv = a->used ? a->check : state->check;
     const uint8_t *out = NULL;
-    size_t out_len = 0, used = 0;
+    size_t out_len = 0;
+    uint64_t end_bit = 0;
     const char *msg = NULL;
-    const int rc = zng_rocm_hook_inflate(a->hook, a->in_buf, a->in_len + taken, kind, &cv, &out, &out_len, &used, &msg);
-    if (rc == 1) {                                      /* Z_STREAM_END: `used` bytes were the deflate data */
-        const size_t mine = used - a->in_len;           /* > 0: the end was not among the bytes of earlier calls */
-        strm->next_in += mine;
-        strm->avail_in -= (uint32_t)mine;
-        a->in_len = 0;
+    const int rc = zng_rocm_hook_inflate_blocks(a->hook, a->in_buf, total, a->carry_bit, kind, &cv, &out, &out_len, &end_bit, &msg);
+    if (rc == 1 || rc == 0 || (rc == Z_DATA_ERROR && msg)) {     /* (-3 without a text: a refused argument) */
         a->out = out;
         a->out_pos = 0;
         a->out_len = out_len;
         a->check = cv;
-        a->used = a->done = 1;
-        return PREFIX(archrocm_inflate)(strm, flush, ret);  /* deliver */
-    }
-    if (rc == -5) {                                     /* the stream does not end here: keep the bytes, ask for more */
-        a->in_len += taken;
-        strm->next_in += taken;
-        strm->avail_in = 0;
         a->used = 1;
-        *ret = Z_OK;
-        return ROCM_INFLATE_BREAK;
-    }
-    if (rc == -3) {                                     /* Z_DATA_ERROR with the reference's text (inflate_p.h:130-134) */
-        strm->msg = msg;
-        state->mode = BAD;
-        return ROCM_INFLATE_CONTINUE;
+        if (rc == 1) {                                  /* Z_STREAM_END: the deflate data ends at end_bit */
+            /* every earlier call decoded every block that was complete, so the last one ends among this call's bytes */
+            const size_t upto = (size_t)((end_bit + 7) >> 3);
+            assert(upto > a->in_len && upto <= total);
+            const size_t mine = upto > a->in_len ? upto - a->in_len : 0;
+            strm->next_in += mine;
+            strm->avail_in -= (uint32_t)mine;
+            a->in_len = 0;
+            a->carry_bit = 0;
+            a->done = 1;
+        } else {                                        /* all of it is taken; the first incomplete block is carried */
+            const size_t from = (size_t)(end_bit >> 3);
+            strm->next_in += taken;
+            strm->avail_in = 0;
+            if (from) memmove(a->in_buf, a->in_buf + from, total - from);
+            a->in_len = total - from;
+            a->carry_bit = (unsigned)(end_bit & 7);
+            if (rc == Z_DATA_ERROR) {                   /* the blocks in front of the bad one go out first */
+                a->bad = 1;
+                a->msg = msg;
+            }
+        }
+        return PREFIX(archrocm_inflate)(strm, flush, ret);  /* deliver */
     }
     /* device trouble: nothing of this call has been consumed; a stream that never needed a second call goes to software */
     if (!a->used) {

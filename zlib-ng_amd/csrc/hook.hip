@@ -26,6 +26,9 @@ struct zng_rocm_hook {
 namespace zr {
 int inflate_large_device_only(const uint8_t *d_src, size_t src_len, const uint8_t *d_window, uint32_t window_len, uint8_t *d_dst,
                               size_t dst_cap, uint64_t *out_len, size_t *in_used, hipStream_t st);      // inflate_large.hip
+int inflate_large_blocks_device_only(const uint8_t *d_src, size_t src_len, unsigned start_bit, const uint8_t *d_window,
+                                     uint32_t window_len, uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, uint64_t *end_bit,
+                                     int *final, hipStream_t st);                                         // inflate_large.hip
 }
 
 namespace {
@@ -80,6 +83,51 @@ bool stale(const zng_rocm_hook *h) { return !zr::ctx() || !h || h->generation !=
 
 constexpr size_t kHookLargeMember = 4u << 20;         // compressed bytes from which a member is decoded on the device
 
+// the n bytes of plaintext at d_in + kHist: their check continues *check_value, they go back to the host (h_out) and become
+// the history
+int deliver_plaintext(zng_rocm_hook *h, size_t n, int check, uint32_t *check_value, const uint8_t **out, size_t *out_len) {
+    if (grow_pinned(&h->h_out, &h->h_cap, n) != ZNG_ROCM_OK) return ZNG_ROCM_ENOMEM;
+    if (check && n) {
+        const int rc = check == 1 ? zng_rocm_adler32_dev(*check_value, h->d_in + kHist, n, h->d_check, h->st)
+                                  : zng_rocm_crc32_dev(*check_value, h->d_in + kHist, n, h->d_check, h->st);
+        if (rc != ZNG_ROCM_OK) return rc;
+        ZR_HIP(hipMemcpyAsync(h->h_check, h->d_check, 4, hipMemcpyDeviceToHost, h->st));
+    }
+    if (n) ZR_HIP(hipMemcpyAsync(h->h_out, h->d_in + kHist, n, hipMemcpyDeviceToHost, h->st));
+    if (int r2 = roll_history(h, n)) return r2;
+    ZR_HIP(hipStreamSynchronize(h->st));
+    if (check && n) *check_value = h->h_check[0];
+    *out = h->h_out;
+    *out_len = n;
+    return ZNG_ROCM_OK;
+}
+
+// blocks mode on the device: 1 = done (*status = 1 or 0 as zng_rocm_inflate_tokens_decode_blocks, outputs set), 0 = leave
+// it to the host decoder, negative = error
+int hook_blocks_on_device(zng_rocm_hook *h, const uint8_t *in, size_t in_len, unsigned start_bit, int check,
+                          uint32_t *check_value, const uint8_t **out, size_t *out_len, uint64_t *end_bit, int *status) {
+    if (grow_device(&h->d_out, &h->out_cap, in_len, 0) != ZNG_ROCM_OK) return 0;          // the compressed bytes
+    if (hipMemcpyAsync(h->d_out, in, in_len, hipMemcpyHostToDevice, h->st) != hipSuccess) return 0;
+    size_t room = h->in_cap > 4 * in_len ? h->in_cap : 4 * in_len;                    // a guess; the call says what it needs
+    uint64_t n = 0, eb = start_bit;
+    int fin = 0;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        if (grow_device(&h->d_in, &h->in_cap, room, kHist) != ZNG_ROCM_OK) return 0;
+        const int rc = zr::inflate_large_blocks_device_only(h->d_out, in_len, start_bit, h->hist_len ? h->d_in + kHist - h->hist_len : nullptr,
+                                                           h->hist_len, h->d_in + kHist, h->in_cap, &n, &eb, &fin, h->st);
+        if (rc == 1) break;
+        if (rc == -5 && attempt == 0 && n > h->in_cap) {
+            room = (size_t)n;
+            continue;
+        }
+        return 0;
+    }
+    if (int rc = deliver_plaintext(h, (size_t)n, check, check_value, out, out_len)) return rc;
+    *end_bit = eb;
+    *status = fin;
+    return 1;
+}
+
 // 1 = stream end (outputs set), 0 = leave it to the host decoder, negative = error
 int hook_inflate_on_device(zng_rocm_hook *h, const uint8_t *in, size_t in_len, int check, uint32_t *check_value,
                            const uint8_t **out, size_t *out_len, size_t *in_used) {
@@ -99,19 +147,7 @@ int hook_inflate_on_device(zng_rocm_hook *h, const uint8_t *in, size_t in_len, i
         }
         return 0;
     }
-    if (grow_pinned(&h->h_out, &h->h_cap, (size_t)n) != ZNG_ROCM_OK) return ZNG_ROCM_ENOMEM;
-    if (check && n) {
-        const int rc = check == 1 ? zng_rocm_adler32_dev(*check_value, h->d_in + kHist, (size_t)n, h->d_check, h->st)
-                                  : zng_rocm_crc32_dev(*check_value, h->d_in + kHist, (size_t)n, h->d_check, h->st);
-        if (rc != ZNG_ROCM_OK) return rc;
-        ZR_HIP(hipMemcpyAsync(h->h_check, h->d_check, 4, hipMemcpyDeviceToHost, h->st));
-    }
-    if (n) ZR_HIP(hipMemcpyAsync(h->h_out, h->d_in + kHist, (size_t)n, hipMemcpyDeviceToHost, h->st));
-    if (int r2 = roll_history(h, (size_t)n)) return r2;
-    ZR_HIP(hipStreamSynchronize(h->st));
-    if (check && n) *check_value = h->h_check[0];
-    *out = h->h_out;
-    *out_len = (size_t)n;
+    if (int rc = deliver_plaintext(h, (size_t)n, check, check_value, out, out_len)) return rc;
     *in_used = used;
     return 1;
 }
@@ -257,19 +293,54 @@ int zng_rocm_hook_inflate(zng_rocm_hook *h, const uint8_t *in, size_t in_len, in
     *in_used = tk.in_used;
     zng_rocm_inflate_tokens_free(&tk);
     if (rc != ZNG_ROCM_OK) return rc;
-    if (check && n) {
-        rc = check == 1 ? zng_rocm_adler32_dev(*check_value, h->d_in + kHist, n, h->d_check, h->st)
-                        : zng_rocm_crc32_dev(*check_value, h->d_in + kHist, n, h->d_check, h->st);
-        if (rc != ZNG_ROCM_OK) return rc;
-        ZR_HIP(hipMemcpyAsync(h->h_check, h->d_check, 4, hipMemcpyDeviceToHost, h->st));
-    }
-    if (n) ZR_HIP(hipMemcpyAsync(h->h_out, h->d_in + kHist, n, hipMemcpyDeviceToHost, h->st));
-    if (int r2 = roll_history(h, n)) return r2;
-    ZR_HIP(hipStreamSynchronize(h->st));
-    if (check && n) *check_value = h->h_check[0];
-    *out = h->h_out;
-    *out_len = n;
+    if ((rc = deliver_plaintext(h, n, check, check_value, out, out_len)) != ZNG_ROCM_OK) return rc;
     return 1;                                            // Z_STREAM_END
+}
+
+int zng_rocm_hook_inflate_blocks(zng_rocm_hook *h, const uint8_t *in, size_t in_len, unsigned start_bit, int check,
+                                 uint32_t *check_value, const uint8_t **out, size_t *out_len, uint64_t *end_bit,
+                                 const char **msg) {
+    if (stale(h)) return ZNG_ROCM_ENODEV;
+    if (!out || !out_len || !end_bit || (in_len && !in) || start_bit > 7u || (check && !check_value) || check < 0 || check > 2)
+        return ZNG_ROCM_EINVAL;
+    DeviceGuard dev;
+    *out = nullptr;
+    *out_len = 0;
+    *end_bit = start_bit;
+    if (msg) *msg = nullptr;
+    if (in_len == 0) return 0;                           // no bits: no block complete, nothing consumed, no launch
+    // as zng_rocm_hook_inflate: a large piece goes to the device in parts, whatever is irregular there (a data error, a
+    // stream without findable block starts) to the host decoder, whose statuses and messages are the reference's
+    if (in_len >= kHookLargeMember) {
+        int status = 0;
+        const int rc = hook_blocks_on_device(h, in, in_len, start_bit, check, check_value, out, out_len, end_bit, &status);
+        if (rc < 0) return rc;
+        if (rc == 1) return status;
+    }
+    // (start_bit <= 7 < 8 * in_len here, and the other arguments are checked above: the decoder's ZNG_ROCM_EINVAL, which has
+    // the value of Z_DATA_ERROR, cannot come back; it would carry no message and be told apart by that)
+    zng_rocm_inflate_tokens tk;
+    memset(&tk, 0, sizeof tk);
+    uint64_t eb = start_bit;
+    const int status = zng_rocm_inflate_tokens_decode_blocks(in, in_len, start_bit, h->hist_len, &tk, &eb);
+    if ((status != 1 && status != 0 && status != -3) || (status == -3 && !tk.msg)) {
+        zng_rocm_inflate_tokens_free(&tk);
+        return status == -4 ? ZNG_ROCM_ENOMEM : ZNG_ROCM_EINVAL;
+    }
+    const char *text = tk.msg;                           // (a static string)
+    const size_t n = (size_t)tk.out_len;
+    int rc = ZNG_ROCM_OK;
+    if (n) {                                             // no block complete: no launch, the history stays
+        rc = grow_device(&h->d_in, &h->in_cap, n, kHist);
+        if (rc == ZNG_ROCM_OK)
+            rc = inflate_tokens_to_device(&tk, h->hist_len ? h->d_in + kHist - h->hist_len : nullptr, h->hist_len, h->d_in + kHist, h->st);
+    }
+    zng_rocm_inflate_tokens_free(&tk);
+    if (rc != ZNG_ROCM_OK) return rc;
+    if (n && (rc = deliver_plaintext(h, n, check, check_value, out, out_len)) != ZNG_ROCM_OK) return rc;
+    *end_bit = eb;
+    if (status == -3 && msg) *msg = text;
+    return status;
 }
 
 }  // extern "C"

@@ -649,11 +649,13 @@ __device__ __forceinline__ uint32_t long_code(LDS &L, int which, int root, const
 // inflate_resolve.hip: a byte, or 256 + k = "byte k of the 32 KiB in front of this part"; copies move symbols, so
 // unresolved references propagate by themselves, and the context chain of inflate_resolve.hip turns them into bytes.
 // Results per part: 8 words {symbols produced, end bit (lo, hi), status, message, furthest reach in front of the part,
-// index of the start it ended on, BFINAL seen}.
+// index of the start it ended on, BFINAL seen}.  `marks` (parts only, may be null): 4 words per part, the state where its
+// last block that ended inside the input ended {symbols produced, bit (lo, hi), furthest reach} -- what a part that ran
+// out of input can still deliver (the streaming hook's blocks mode).
 template <int RING, bool PART, bool COMPACT = false>
 __global__ __launch_bounds__(64)
 void inflate_streams_kernel(const InflateJobDev *__restrict__ jobs, uint32_t njobs, uint32_t *__restrict__ results,
-                            const unsigned long long *__restrict__ starts) {
+                            const unsigned long long *__restrict__ starts, uint32_t *__restrict__ marks) {
     typedef typename std::conditional<PART, uint16_t, uint8_t>::type T;
     constexpr uint32_t E = 16u / (uint32_t)sizeof(T);   // elements per 16-byte store
     constexpr uint32_t M = RING - 1;
@@ -823,6 +825,19 @@ void inflate_streams_kernel(const InflateJobDev *__restrict__ jobs, uint32_t njo
     };
     bool last = false;
     while (!last && msg == kMsgNone) {
+        if constexpr (PART) {
+            // a block starts here: everything in front of it is complete, if the bits it took are all input (the zero bits
+            // behind a truncated stream decode to something too).  Stored once per block, so no register holds it.
+            if (marks) {
+                const unsigned long long b = bit_pos();
+                if (b <= 8ull * in_len && lane == 0) {
+                    marks[4 * job + 0] = op;
+                    marks[4 * job + 1] = (uint32_t)b;
+                    marks[4 * job + 2] = (uint32_t)(b >> 32);
+                    marks[4 * job + 3] = reach;
+                }
+            }
+        }
         if (cnt < 32) append();
         last = hold & 1u;
         const uint32_t type = (uint32_t)(hold >> 1) & 3u;
@@ -1165,12 +1180,12 @@ int launch_inflate_streams_device(const InflateJobDev *d_jobs, size_t njobs, uin
         const char *r = getenv("ZNG_ROCM_INFLATE_RING");
         return r ? atoi(r) : 4096;
     }();
-    if (ring == 8192) ZR_LAUNCH_TRACED((inflate_streams_kernel<8192, false>), dim3((unsigned)njobs), dim3(64), st, d_jobs, (uint32_t)njobs, d_results, (const unsigned long long *)nullptr);
-    else if (ring == 16384) ZR_LAUNCH_TRACED((inflate_streams_kernel<16384, false>), dim3((unsigned)njobs), dim3(64), st, d_jobs, (uint32_t)njobs, d_results, (const unsigned long long *)nullptr);
-    else if (ring == 32768) ZR_LAUNCH_TRACED((inflate_streams_kernel<32768, false>), dim3((unsigned)njobs), dim3(64), st, d_jobs, (uint32_t)njobs, d_results, (const unsigned long long *)nullptr);
+    if (ring == 8192) ZR_LAUNCH_TRACED((inflate_streams_kernel<8192, false>), dim3((unsigned)njobs), dim3(64), st, d_jobs, (uint32_t)njobs, d_results, (const unsigned long long *)nullptr, (uint32_t *)nullptr);
+    else if (ring == 16384) ZR_LAUNCH_TRACED((inflate_streams_kernel<16384, false>), dim3((unsigned)njobs), dim3(64), st, d_jobs, (uint32_t)njobs, d_results, (const unsigned long long *)nullptr, (uint32_t *)nullptr);
+    else if (ring == 32768) ZR_LAUNCH_TRACED((inflate_streams_kernel<32768, false>), dim3((unsigned)njobs), dim3(64), st, d_jobs, (uint32_t)njobs, d_results, (const unsigned long long *)nullptr, (uint32_t *)nullptr);
     else
 #endif
-    ZR_LAUNCH_TRACED((inflate_streams_kernel<4096, false>), dim3((unsigned)njobs), dim3(64), st, d_jobs, (uint32_t)njobs, d_results, (const unsigned long long *)nullptr);
+    ZR_LAUNCH_TRACED((inflate_streams_kernel<4096, false>), dim3((unsigned)njobs), dim3(64), st, d_jobs, (uint32_t)njobs, d_results, (const unsigned long long *)nullptr, (uint32_t *)nullptr);
     ZR_HIP(hipGetLastError());
     return ZNG_ROCM_OK;
 }
@@ -1181,7 +1196,7 @@ int launch_inflate_streams_device(const InflateJobDev *d_jobs, size_t njobs, uin
 // call lasts as long as its longest part, and a part is faster in the plain layout among 12 (a CPython stream: 12.4
 // against 13.2 ms): two instantiations, chosen per call.
 int launch_inflate_parts_device(const InflateJobDev *d_jobs, size_t njobs, uint32_t *d_results, const unsigned long long *d_starts,
-                                bool many, hipStream_t st) {
+                                bool many, hipStream_t st, uint32_t *d_marks) {
     if (!njobs) return ZNG_ROCM_OK;
 #ifdef ZR_MEASURE_FORMS
     static const int ring = [] {
@@ -1189,15 +1204,15 @@ int launch_inflate_parts_device(const InflateJobDev *d_jobs, size_t njobs, uint3
         return r ? atoi(r) : 4096;
     }();
     if (ring == 2048 && many) {
-        ZR_LAUNCH_TRACED((inflate_streams_kernel<2048, true, true>), dim3((unsigned)njobs), dim3(64), st, d_jobs, (uint32_t)njobs, d_results, d_starts);
+        ZR_LAUNCH_TRACED((inflate_streams_kernel<2048, true, true>), dim3((unsigned)njobs), dim3(64), st, d_jobs, (uint32_t)njobs, d_results, d_starts, d_marks);
         ZR_HIP(hipGetLastError());
         return ZNG_ROCM_OK;
     }
 #endif
     if (many)
-        ZR_LAUNCH_TRACED((inflate_streams_kernel<4096, true, true>), dim3((unsigned)njobs), dim3(64), st, d_jobs, (uint32_t)njobs, d_results, d_starts);
+        ZR_LAUNCH_TRACED((inflate_streams_kernel<4096, true, true>), dim3((unsigned)njobs), dim3(64), st, d_jobs, (uint32_t)njobs, d_results, d_starts, d_marks);
     else
-        ZR_LAUNCH_TRACED((inflate_streams_kernel<4096, true, false>), dim3((unsigned)njobs), dim3(64), st, d_jobs, (uint32_t)njobs, d_results, d_starts);
+        ZR_LAUNCH_TRACED((inflate_streams_kernel<4096, true, false>), dim3((unsigned)njobs), dim3(64), st, d_jobs, (uint32_t)njobs, d_results, d_starts, d_marks);
     ZR_HIP(hipGetLastError());
     return ZNG_ROCM_OK;
 }

@@ -240,6 +240,12 @@ struct Bits {
 #define FAIL(m) do { t->status = Z_DATA_ERROR_; t->msg = (m); goto done; } while (0)
 #define STARVE() do { t->status = Z_BUF_ERROR_; t->msg = "input ended before the final block"; goto done; } while (0)
 
+struct BlockMark {                   // the decode's state where a block starts (blocks mode)
+    size_t ntokens, nliterals, nsegs;
+    uint64_t out_pos, bit, max_reach;
+    uint32_t run;
+};
+
 }  // namespace
 
 // Control block of a PARTIAL decode (the parts of the multi-threaded single-stream inflate, inflate_threads.cpp):
@@ -247,6 +253,9 @@ struct Bits {
 // exactly on one of the given ascending bit positions (stops: where other threads' decodes start).  On return
 // end_bit = first bit behind the last block decoded, max_reach = max over all matches of (distance - bytes produced
 // before the match), hit_stop = 1 when it stopped on a stop position (status Z_OK: the stream goes on there).
+// Blocks mode (ctl->blocks): the state at every block start is noted; when the input ends inside a block the arrays are cut
+// back to the last of those notes and the status is Z_OK (end_bit = that block's start), and a data error is reported
+// with the tokens of the complete blocks in front of the failing one (end_bit = its start).
 namespace {
 
 // caps: capacities (in elements: tokens, literal bytes, seg words) of the arrays `t` already owns; updated on return
@@ -280,6 +289,8 @@ int decode_stream(const uint8_t *src, size_t src_len, uint64_t window_len, zng_r
     static const uint8_t order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
     uint16_t lens[320];
     bool last = false;
+    const bool blocks = ctl && ctl->blocks;
+    BlockMark mark{0, 0, 1, 0, ctl ? ctl->start_bit : 0, 0, 0};
 
     // segment 0
     grow(o.re, (void **)&t->segs, &o.seg_cap, 6, 8, &o.oom);
@@ -297,6 +308,8 @@ int decode_stream(const uint8_t *src, size_t src_len, uint64_t window_len, zng_r
     }
 
     while (!last) {
+        if (blocks) mark = BlockMark{t->ntokens, t->nliterals, t->nsegs, o.out_pos, 8ull * (uint64_t)(b.next - src) - b.cnt,
+                                     max_reach, o.run};
         if (ctl && ctl->nstops) {
             // a block has just ended (or none has begun): is this where another thread's decode starts?
             const uint64_t pos = 8ull * (uint64_t)(b.next - src) - b.cnt;
@@ -488,6 +501,26 @@ int decode_stream(const uint8_t *src, size_t src_len, uint64_t window_len, zng_r
     t->status = Z_STREAM_END_;
 done:
     if (o.oom) goto oom;
+    if (blocks && t->status != Z_STREAM_END_) {
+        // back to the start of the block the input ended (or the error came) in: the arrays only ever grow, so what was
+        // there at that start is still there; the run of literals then open is closed below
+        t->ntokens = mark.ntokens;
+        t->nliterals = mark.nliterals;
+        t->nsegs = mark.nsegs;
+        o.out_pos = mark.out_pos;
+        o.run = mark.run;
+        max_reach = mark.max_reach;
+        if (t->status == Z_BUF_ERROR_) {
+            t->status = Z_OK_;
+            t->msg = "";
+        }
+        b.next = src + (mark.bit >> 3);              // the bit position reported below
+        b.cnt = 0;
+        if (mark.bit & 7) {
+            ++b.next;
+            b.cnt = (unsigned)(8 - (mark.bit & 7));
+        }
+    }
     flush_run(o);
     if (o.oom) goto oom;
     {
@@ -501,6 +534,7 @@ done:
     }
     t->out_len = o.out_pos;
     t->in_used = (size_t)(b.next - src) - (b.cnt >> 3);
+    if (blocks && t->status != Z_STREAM_END_) t->in_used = (size_t)(mark.bit >> 3);
     if (ctl) {
         ctl->end_bit = 8ull * (uint64_t)(b.next - src) - b.cnt;
         ctl->max_reach = max_reach;
@@ -733,6 +767,21 @@ int zng_rocm_inflate_tokens_decode_window(const uint8_t *src, size_t src_len, ui
     if (!out || (!src && src_len) || window_len > 32768u) return ZNG_ROCM_EINVAL;
     memset(out, 0, sizeof(*out));
     return decode_stream(src, src_len, window_len, out);
+}
+
+int zng_rocm_inflate_tokens_decode_blocks(const uint8_t *src, size_t src_len, uint64_t start_bit, uint32_t window_len,
+                                          zng_rocm_inflate_tokens *out, uint64_t *end_bit) {
+    // the outputs are defined on every return, a refused argument included (the caller may free `out` either way)
+    if (out) memset(out, 0, sizeof(*out));
+    if (end_bit) *end_bit = start_bit;
+    if (!out || !end_bit || (!src && src_len) || window_len > 32768u || start_bit > 8ull * src_len) return ZNG_ROCM_EINVAL;
+    ZrDecodeCtl ctl;
+    memset(&ctl, 0, sizeof ctl);
+    ctl.start_bit = start_bit;
+    ctl.blocks = 1;
+    const int rc = decode_stream(src, src_len, window_len, out, plain_realloc, nullptr, &ctl);
+    *end_bit = rc == Z_MEM_ERROR_ ? start_bit : ctl.end_bit;
+    return rc;
 }
 
 void zng_rocm_inflate_tokens_free(zng_rocm_inflate_tokens *t) {

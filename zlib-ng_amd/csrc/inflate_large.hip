@@ -440,9 +440,13 @@ static int why(const char *reason) {
     return 0;
 }
 
-// returns 1 with *out_len / *in_used set, or 0 = "irregular: use the sequential decoder", or a negative error
+// returns 1 with *out_len / *in_used set, or 0 = "irregular: use the sequential decoder", or a negative error.
+// Blocks mode (`blocks`, the streaming hook): the stream starts at bit `start_bit` of d_src, and input that ends inside a
+// block is no irregularity -- the chain stops at the first part that ran out of input, that part's complete blocks (its
+// marks) are kept, and *end_bit / *final say where the delivered blocks end and whether the BFINAL one is among them.
 static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len, const uint8_t *d_window, uint32_t window_len,
-                             uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, size_t *in_used, hipStream_t st) {
+                             uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, size_t *in_used, hipStream_t st,
+                             bool blocks = false, uint64_t start_bit = 0, uint64_t *end_bit_out = nullptr, int *final_out = nullptr) {
     if (src_len < (128u << 10) || src_len >= (1ull << 31)) return why("stream below 128 KiB (or 2 GiB and more)");
     // ---- candidates ---------------------------------------------------------------------------------------------
     const uint32_t cap1 = (uint32_t)std::min<size_t>(src_len / 64 + 4096, 64u << 20);
@@ -476,7 +480,7 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
         good.assign(h_good, h_good + n12[1]);
         for (unsigned long long &b : good) b &= ~(1ull << 63);
         std::sort(good.begin(), good.end(), [](unsigned long long x, unsigned long long y) { return (x & ~(1ull << 62)) < (y & ~(1ull << 62)); });
-        unsigned long long prev = 0;
+        unsigned long long prev = start_bit;
         for (unsigned long long b62 : good) {
             const unsigned long long b = b62 & ~(1ull << 62);
             if (b - prev > 8ull * (128u << 10)) patterns_do = false;
@@ -510,7 +514,7 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
         std::sort(good.begin(), good.end(), [](unsigned long long x, unsigned long long y) { return (x & ~(1ull << 62)) < (y & ~(1ull << 62)); });
     }
     std::vector<unsigned long long> starts;
-    starts.push_back(0);
+    starts.push_back(start_bit);                          // (candidates in front of it, or on it, fall to the spacing test)
     const unsigned long long spacing = good.size() > kPartsUnthinned ? 8ull * kSpacingBytes : 1ull;
     size_t heavy = 1;                                     // parts that are not a stored block: the ones that take time
     for (unsigned long long b62 : good) {
@@ -535,7 +539,7 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
     }
     uint8_t *sp = nullptr;
     const size_t jobs_b = (np * sizeof(InflateJobDev) + 255) & ~(size_t)255, starts_b = (np * 8 + 255) & ~(size_t)255,
-                 res_b = (np * 32 + 255) & ~(size_t)255, slots_b = slot_off[np] * 2;
+                 res_b = (np * 32 + (blocks ? np * 16 : 0) + 255) & ~(size_t)255, slots_b = slot_off[np] * 2;
     if (scratch_reserve(ws, kScrLargeParts, jobs_b + starts_b + res_b + slots_b, false, (void **)&sp) != ZNG_ROCM_OK)
         return why("no room for the part slots");
     InflateJobDev *d_jobs = (InflateJobDev *)sp;
@@ -548,14 +552,15 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
     InflateJobDev *jobs = (InflateJobDev *)hq;
     unsigned long long *h_starts = (unsigned long long *)(hq + jobs_b);
     uint32_t *res = (uint32_t *)(hq + jobs_b + starts_b);
+    uint32_t *d_marks = blocks ? d_res + 8 * np : nullptr, *marks = res + 8 * np;    // blocks mode: 4 words per part behind the results
     std::copy(starts.begin(), starts.end(), h_starts);
     for (size_t i = 0; i < np; ++i)
         jobs[i] = InflateJobDev{d_src, (uint8_t *)(d_slots + slot_off[i]), src_len, slot_off[i + 1] - slot_off[i],
                                 i == 0 ? window_len : 32768u, 0u};
     ZR_HIP(hipMemcpyAsync(d_jobs, jobs, np * sizeof(InflateJobDev), hipMemcpyHostToDevice, st));
     ZR_HIP(hipMemcpyAsync(d_starts, h_starts, np * 8, hipMemcpyHostToDevice, st));
-    if (int rc = launch_inflate_parts_device(d_jobs, np, d_res, d_starts, many, st)) return rc;
-    ZR_HIP(hipMemcpyAsync(res, d_res, np * 32, hipMemcpyDeviceToHost, st));
+    if (int rc = launch_inflate_parts_device(d_jobs, np, d_res, d_starts, many, st, d_marks)) return rc;
+    ZR_HIP(hipMemcpyAsync(res, d_res, np * (blocks ? 48 : 32), hipMemcpyDeviceToHost, st));
     ZR_HIP(hipStreamSynchronize(st));
     // parts whose slot was too small (more than kSlotRatio : 1): once more, with room for deflate's worst case (1032 : 1)
     uint8_t *bigp = nullptr;
@@ -584,8 +589,8 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
                 at += capi;
             }
             ZR_HIP(hipMemcpyAsync(d_jobs, jobs, np * sizeof(InflateJobDev), hipMemcpyHostToDevice, st));
-            if (int rc = launch_inflate_parts_device(d_jobs, np, d_res, d_starts, many, st)) return rc;
-            ZR_HIP(hipMemcpyAsync(res, d_res, np * 32, hipMemcpyDeviceToHost, st));
+            if (int rc = launch_inflate_parts_device(d_jobs, np, d_res, d_starts, many, st, d_marks)) return rc;
+            ZR_HIP(hipMemcpyAsync(res, d_res, np * (blocks ? 48 : 32), hipMemcpyDeviceToHost, st));
             ZR_HIP(hipStreamSynchronize(st));
         }
     }
@@ -598,10 +603,19 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
     std::vector<PartCopy> copies;
     uint64_t produced = 0;
     size_t cur = 0;
-    unsigned long long end_bit = 0;
+    unsigned long long end_bit = start_bit;
+    bool final = false;
     for (;;) {
         const uint32_t *r = &res[8 * cur];
         const bool ended = r[3] == 1u;
+        if (blocks && r[4] == kMsgStarved) {            // the input ends in this part: its complete blocks, and no more
+            const uint32_t *m = &marks[4 * cur];
+            if ((uint64_t)m[3] > produced + window_len) return why("a distance reaches in front of the stream");
+            if (m[0]) copies.push_back(PartCopy{slot_ptr[cur], produced, 0, m[0], 0u});
+            produced += m[0];
+            end_bit = (unsigned long long)m[1] | ((unsigned long long)m[2] << 32);
+            break;
+        }
         if (r[4] != kMsgNone || !(ended || r[6] != 0xffffffffu)) {                // error / truncation on the chain
             set_error("inflate_large: sequential decoder (part %zu of %zu at bit %llu: message %u \"%s\", %u symbols of %llu, "
                       "ended on %d)", cur, np, starts[cur], r[4], zng_rocm_inflate_message(r[4]), r[0],
@@ -612,7 +626,10 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
         copies.push_back(PartCopy{slot_ptr[cur], produced, 0, r[0], 0u});
         produced += r[0];
         end_bit = (unsigned long long)r[1] | ((unsigned long long)r[2] << 32);
-        if (ended) break;
+        if (ended) {
+            final = true;
+            break;
+        }
         cur = r[6];
         if (cur >= np) return why("bad chain link");
     }
@@ -645,6 +662,12 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
     segs.push_back(0);
     if (out_len) *out_len = produced;
     if (in_used) *in_used = (size_t)((end_bit + 7) >> 3);
+    if (end_bit_out) *end_bit_out = end_bit;
+    if (final_out) *final_out = final ? 1 : 0;
+    if (blocks && produced == 0) {                        // no block complete yet: nothing to launch
+        t_large_parts = 0;
+        return 1;
+    }
     if (produced > dst_cap) {
         set_error("inflate output (%llu bytes) exceeds dst_cap", (unsigned long long)produced);
         return -5;
@@ -702,6 +725,21 @@ int inflate_large_device_only(const uint8_t *d_src, size_t src_len, const uint8_
     if (!ws) return ZNG_ROCM_ENOMEM;
     std::lock_guard<std::mutex> use(ws->mu);
     return inflate_large_try(ws, d_src, src_len, d_window, window_len, d_dst, dst_cap, out_len, in_used, st);
+}
+
+// Blocks mode of the above (the streaming hook, hook.hip): d_src holds the stream from the byte that contains bit `start_bit`
+// (0..7) on; 1 = *out_len bytes of complete blocks at d_dst, *end_bit = where they end, *final = the BFINAL block is among
+// them; 0 = irregular (the caller's host decoder in blocks mode takes the call); -5 with *out_len = dst_cap too small.
+int inflate_large_blocks_device_only(const uint8_t *d_src, size_t src_len, unsigned start_bit, const uint8_t *d_window,
+                                     uint32_t window_len, uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, uint64_t *end_bit,
+                                     int *final, hipStream_t st) {
+    t_large_parts = 0;
+    Workspace *ws = workspace_for(st);
+    if (!ws) return ZNG_ROCM_ENOMEM;
+    std::lock_guard<std::mutex> use(ws->mu);
+    size_t used = 0;
+    return inflate_large_try(ws, d_src, src_len, d_window, window_len, d_dst, dst_cap, out_len, &used, st, true, start_bit & 7u,
+                             end_bit, final);
 }
 
 }  // namespace zr

@@ -16,6 +16,8 @@ struct ZrDecodeCtl {                 // control block of a partial decode: see i
     uint64_t        end_bit;
     uint64_t        max_reach;
     int             hit_stop;
+    int             blocks;          // blocks mode: input that ends (or a data error) inside a block gives back every complete
+                                     // block before it -- status 0 (or -3), end_bit = where the incomplete one starts
 };
 
 struct ZrPart {                      // one part of the stream: its token arrays are carried over between calls

@@ -22,13 +22,19 @@ class InflateTokens(C.Structure):
 class DecodedStream:
     """numpy views of one decoded stream (copies; the C buffers are freed immediately)"""
 
-    def __init__(self, src, window_len=0, nthreads=1):
+    def __init__(self, src, window_len=0, nthreads=1, start_bit=None):
         import numpy as np
         lib = rocm.lib()
         raw = bytes(src)
         buf = C.create_string_buffer(raw, max(len(raw), 1))
         tk = InflateTokens()
-        if nthreads == 1:
+        self.end_bit = None
+        if start_bit is not None:
+            end_bit = C.c_uint64(0)
+            self.status = lib.zng_rocm_inflate_tokens_decode_blocks(C.addressof(buf), len(raw), start_bit, window_len,
+                                                                    C.byref(tk), C.byref(end_bit))
+            self.end_bit = int(end_bit.value)
+        elif nthreads == 1:
             self.status = lib.zng_rocm_inflate_tokens_decode_window(C.addressof(buf), len(raw), window_len, C.byref(tk))
         else:
             self.status = lib.zng_rocm_inflate_tokens_decode_threads(C.addressof(buf), len(raw), window_len, nthreads,
@@ -50,6 +56,44 @@ class DecodedStream:
 def decode_tokens(src, window_len=0, nthreads=1):
     """nthreads != 1: the multi-threaded decode of ONE stream (0 = one thread per hardware thread)"""
     return DecodedStream(src, window_len, nthreads)
+
+
+def decode_blocks(src, start_bit=0, window_len=0):
+    """zng_rocm_inflate_tokens_decode_blocks: every COMPLETE block from bit `start_bit` on; .status 1 (BFINAL decoded) / 0
+    (input ends inside a block) / -3, .end_bit = where the delivered blocks end"""
+    return DecodedStream(src, window_len, start_bit=start_bit)
+
+
+class InflateHook:
+    """the device side of the streaming inflate hook (zng_rocm_hook_*): history in HBM across calls"""
+
+    def __init__(self):
+        rocm._need_init()
+        self.lib = rocm.lib()
+        self.h = C.c_void_p()
+        rocm._check(self.lib.zng_rocm_hook_create(C.byref(self.h), 1 << 20), "zng_rocm_hook_create")
+
+    def close(self):
+        if self.h:
+            self.lib.zng_rocm_hook_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def set_history(self, data):
+        data = bytes(data)
+        buf = C.create_string_buffer(data, max(len(data), 1))
+        rocm._check(self.lib.zng_rocm_hook_set_history(self.h, C.addressof(buf), len(data)), "zng_rocm_hook_set_history")
+
+    def inflate_blocks(self, data, start_bit=0, check=0, check_value=0):
+        """zng_rocm_hook_inflate_blocks on host bytes `data` (the stream from the byte that holds bit start_bit on):
+        returns (status, plaintext bytes, end_bit, check value, message)"""
+        data = bytes(data)
+        buf = C.create_string_buffer(data, max(len(data), 1))
+        cv = C.c_uint32(check_value)
+        out, out_len, end_bit, msg = C.c_void_p(), C.c_size_t(0), C.c_uint64(0), C.c_char_p()
+        st = self.lib.zng_rocm_hook_inflate_blocks(self.h, C.addressof(buf), len(data), start_bit, check, C.byref(cv),
+                                                   C.byref(out), C.byref(out_len), C.byref(end_bit), C.byref(msg))
+        plain = C.string_at(out.value, out_len.value) if out_len.value else b""
+        return st, plain, int(end_bit.value), int(cv.value), (msg.value or b"").decode()
 
 
 def resolve_dev(dec, stream=None):

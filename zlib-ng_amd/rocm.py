@@ -87,6 +87,8 @@ _PROTOS = {
     "zng_rocm_deflate_streams_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "zng_rocm_inflate_tokens_decode": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "zng_rocm_inflate_tokens_decode_window": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
+    "zng_rocm_inflate_tokens_decode_blocks": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint32, C.c_void_p,
+                                                        C.POINTER(C.c_uint64)]),
     "zng_rocm_inflate_resolve_window_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                                       C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
     "zng_rocm_inflate_raw_window": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t,
@@ -129,6 +131,9 @@ _PROTOS = {
     "zng_rocm_hook_inflate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_uint32),
                                         C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                         C.POINTER(C.c_char_p)]),
+    "zng_rocm_hook_inflate_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_int, C.POINTER(C.c_uint32),
+                                               C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64),
+                                               C.POINTER(C.c_char_p)]),
     "zng_rocm_trace_begin": (C.c_int, [C.c_int]),
     "zng_rocm_trace_end": (C.c_int, [C.POINTER(C.c_float), C.c_int]),
     "zng_rocm_adler32_combine": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_int64]),
