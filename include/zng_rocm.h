@@ -283,6 +283,23 @@ int    zng_rocm_deflate_block_dev(int level, const uint8_t *d_in, size_t in_len,
  * compressed size of stream i.  The level-1 CLASS (static Huffman, one kernel) is zng_rocm_deflate_quick_dev. */
 int    zng_rocm_deflate_streams_dev(int level, const zng_rocm_stream_job *jobs, size_t njobs, size_t *out_lens,
                                     void *stream);
+/* The same two with zlib's `strategy` (deflateInit2; zlib-ng.h.in codes): 0 Z_DEFAULT_STRATEGY and 1 Z_FILTERED give
+ * exactly the bytes of the calls above; anything outside 0..4 returns ZNG_ROCM_EINVAL with nothing launched or written.
+ * As deflate.c:1039-1043 chooses:
+ *   level 0            stored blocks, whatever the strategy;
+ *   2 Z_HUFFMAN_ONLY   every byte a literal (deflate_huff.c:16-45); the level makes no difference;
+ *   3 Z_RLE            the greedy parse of deflate_rle.c:30-86 run on every device segment: p is a match iff
+ *                      in[p-1] == in[p] == in[p+1] == in[p+2] and p + 3 <= the segment's end, of distance 1 and of the
+ *                      length of the run of in[p-1] from p on (at most 258, not past the segment's end); in[p-1] may lie
+ *                      in the previous segment or in the dict_len history; the level makes no difference;
+ *   4 Z_FIXED          the level's matcher; each block stored if that is not larger than static, otherwise static
+ *                      (trees.c:660-672 with opt_lenb = static_lenb): never a dynamic block.
+ * The blocks are valid raw RFC 1951, not bit-identical to the reference's (their boundaries differ);
+ * zng_rocm_deflate_bound(in_len) holds for every strategy. */
+int    zng_rocm_deflate_strategy_block_dev(int level, int strategy, const uint8_t *d_in, size_t in_len, uint32_t dict_len,
+                                           uint32_t flags, uint8_t *d_out, size_t out_cap, size_t *out_len, void *stream);
+int    zng_rocm_deflate_strategy_streams_dev(int level, int strategy, const zng_rocm_stream_job *jobs, size_t njobs,
+                                             size_t *out_lens, void *stream);
 
 /* ---- inflate: host bitstream decode -> token stream -> device copy resolution -------------
  * The split of slot `inflate_fast` (inffast_tpl.h:53-318): the sequential Huffman decode loop
@@ -483,6 +500,11 @@ size_t zng_rocm_hook_deflate_bound(size_t in_len);
  * continuing *check_value (what DEFLATE_NEED_CHECKSUM = 0 leaves to the backend, deflate.c:1197-1212). */
 int    zng_rocm_hook_deflate_block(zng_rocm_hook *h, int level, const uint8_t *in, size_t in_len, uint32_t flags, int check,
                                    uint32_t *check_value, uint8_t *out, size_t out_cap, size_t *out_len);
+/* the same block at zlib's `strategy` (0..4, as zng_rocm_deflate_strategy_block_dev; the strategy may change from one
+ * block to the next, as deflateParams allows); history, check value and flags as above */
+int    zng_rocm_hook_deflate_block_strategy(zng_rocm_hook *h, int level, int strategy, const uint8_t *in, size_t in_len,
+                                            uint32_t flags, int check, uint32_t *check_value, uint8_t *out, size_t out_cap,
+                                            size_t *out_len);
 /* A complete raw deflate stream (or the rest of one) at `in`, continuing the history: returns 1 (Z_STREAM_END) with the
  * plaintext at *out (host memory owned by the hook, valid until its next call), *out_len, *in_used and the check of the
  * plaintext; -5 when the stream does not end inside in_len (nothing consumed: the adapter gathers more input);

@@ -53,10 +53,10 @@ void Z_INTERNAL PREFIX(archrocm_deflate_end)(PREFIX3(streamp) strm) {           
     memset(a, 0, sizeof *a);
 }
 
-/* what the device takes: every level, the default and filtered strategies (the others prescribe a block format:
- * deflate_huff / deflate_rle / Z_FIXED), the 32 KiB window its history is kept for */
+/* what the device takes: every level, every strategy (default, filtered, Z_HUFFMAN_ONLY, Z_RLE, Z_FIXED --
+ * zng_rocm_deflate_strategy_block_dev), the 32 KiB window its history is kept for */
 static int params_ok(int level, unsigned w_bits, int strategy) {
-    return level >= 0 && level <= 9 && w_bits == 15 && (strategy == Z_DEFAULT_STRATEGY || strategy == Z_FILTERED);
+    return level >= 0 && level <= 9 && w_bits == 15 && strategy >= ROCM_Z_DEFAULT_STRATEGY && strategy <= ROCM_Z_FIXED;
 }
 
 int Z_INTERNAL PREFIX(archrocm_can_deflate)(PREFIX3(streamp) strm) {
@@ -113,8 +113,9 @@ static int produce(PREFIX3(streamp) strm, deflate_state *s, arch_deflate_state *
     size_t clen = 0;
     int rc = ZNG_ROCM_ENODEV;
     if (!a->disabled)
-        rc = zng_rocm_hook_deflate_block(a->hook, s->level, a->in_buf, a->in_len, final ? 0u : ZNG_ROCM_BLOCK_NOT_FINAL,
-                                         s->wrap, &cv, a->out_buf, a->out_cap, &clen);
+        rc = zng_rocm_hook_deflate_block_strategy(a->hook, s->level, s->strategy, a->in_buf, a->in_len,
+                                                  final ? 0u : ZNG_ROCM_BLOCK_NOT_FINAL, s->wrap, &cv, a->out_buf, a->out_cap,
+                                                  &clen);
     if (rc != ZNG_ROCM_OK) {                            /* degrade, never surface */
         a->disabled = 1;
         clen = stored_block(a->in_buf, a->in_len, final, a->out_buf);
@@ -182,8 +183,10 @@ int Z_INTERNAL PREFIX(archrocm_deflate)(PREFIX3(streamp) strm, int flush, block_
     return 1;
 }
 
-/* DEFLATE_PARAMS_HOOK (deflate.c:649): the level is read per block, so a change between settings the device takes needs
- * nothing; leaving them mid-stream would need the history back in the software window -- not supported */
+/* DEFLATE_PARAMS_HOOK (deflate.c:649): level and strategy are read per block, and the Z_BLOCK flush deflateParams makes
+ * in front of a change (deflate.c:651-660) has closed the device block on a byte boundary, so a change between settings
+ * the device takes needs nothing; leaving them mid-stream (another window size) would need the history back in the
+ * software window -- not supported */
 int Z_INTERNAL PREFIX(archrocm_deflate_params)(PREFIX3(streamp) strm, int level, int strategy, int *flush) {
     deflate_state *s = (deflate_state *)strm->state;
     (void)flush;

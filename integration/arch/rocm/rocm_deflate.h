@@ -8,6 +8,19 @@
 #define ROCM_DEFLATE_H_
 #include "rocm_common.h"
 
+/* zlib's strategy codes (zlib-ng.h.in) under names of the adapter's own: tests/c/zlibng_coarse_min.h, the strict-C11
+ * stand-in for the reference's headers, defines only the first two */
+#define ROCM_Z_DEFAULT_STRATEGY 0
+#define ROCM_Z_FILTERED 1
+#define ROCM_Z_HUFFMAN_ONLY 2
+#define ROCM_Z_RLE 3
+#define ROCM_Z_FIXED 4
+#ifndef ZNG_ROCM_STANDALONE_CHECK
+_Static_assert(ROCM_Z_DEFAULT_STRATEGY == Z_DEFAULT_STRATEGY && ROCM_Z_FILTERED == Z_FILTERED &&
+               ROCM_Z_HUFFMAN_ONLY == Z_HUFFMAN_ONLY && ROCM_Z_RLE == Z_RLE && ROCM_Z_FIXED == Z_FIXED,
+               "arch/rocm strategy codes differ from zlib-ng.h");
+#endif
+
 void Z_INTERNAL PREFIX(archrocm_reset_deflate_state)(PREFIX3(streamp) strm);
 void Z_INTERNAL PREFIX(archrocm_deflate_end)(PREFIX3(streamp) strm);
 int  Z_INTERNAL PREFIX(archrocm_can_deflate)(PREFIX3(streamp) strm);

@@ -427,6 +427,9 @@ __device__ __forceinline__ uint32_t next_start_rel(const unsigned long long *bm,
     return hi_rel;
 }
 
+// kForceStatic: the Z_FIXED strategy -- no code lengths are built, the block is stored if that is not larger than
+// static, otherwise static (trees.c:660-672 with opt_lenb = static_lenb); a dynamic block is never written.
+template <bool kForceStatic>
 __global__ __launch_bounds__(256)
 void emit_dynamic_kernel(const BlkJob *__restrict__ jobs, const unsigned long long *__restrict__ bm_base,
                          const uint16_t *__restrict__ d16_base, const uint32_t *__restrict__ hist_in,
@@ -467,53 +470,57 @@ void emit_dynamic_kernel(const BlkJob *__restrict__ jobs, const unsigned long lo
     if (t == 0) T.cost_dyn = T.cost_static = 0;
 
     // 2. code lengths and codes
-    huff_lengths(&T, T.lfreq, 286, 15, T.llen, t);
-    huff_lengths(&T, T.dfreq, 30, 15, T.dlen, t);
-    huff_codes(T.llen, 286, T.lcode, t);
-    huff_codes(T.dlen, 30, T.dcode, t);
+    if constexpr (!kForceStatic) {
+        huff_lengths(&T, T.lfreq, 286, 15, T.llen, t);
+        huff_lengths(&T, T.dfreq, 30, 15, T.dlen, t);
+        huff_codes(T.llen, 286, T.lcode, t);
+        huff_codes(T.dlen, 30, T.dcode, t);
 
-    // 3. run-length code the lengths (scan_tree / send_tree of trees.c; RFC 1951 3.2.7)
-    if (t == 0) {
-        int hlit = 286, hdist = 30;
-        while (hlit > 257 && T.llen[hlit - 1] == 0) --hlit;
-        while (hdist > 1 && T.dlen[hdist - 1] == 0) --hdist;
-        T.hlit = hlit;
-        T.hdist = hdist;
-        for (int i = 0; i < 19; ++i) T.clfreq[i] = 0;
-        const int total = hlit + hdist;
-        int ncl = 0, i = 0;
-        while (i < total) {
-            const int v = i < hlit ? T.llen[i] : T.dlen[i - hlit];
-            int run = 1;
-            while (i + run < total && (i + run < hlit ? T.llen[i + run] : T.dlen[i + run - hlit]) == v) ++run;
-            i += run;
-            if (v == 0) {
-                while (run >= 11) {
-                    const int r = run > 138 ? 138 : run;
-                    T.clsym[ncl] = 18; T.clext[ncl++] = (uint8_t)(r - 11); T.clfreq[18]++;
-                    run -= r;
+        // 3. run-length code the lengths (scan_tree / send_tree of trees.c; RFC 1951 3.2.7)
+        if (t == 0) {
+            int hlit = 286, hdist = 30;
+            while (hlit > 257 && T.llen[hlit - 1] == 0) --hlit;
+            while (hdist > 1 && T.dlen[hdist - 1] == 0) --hdist;
+            T.hlit = hlit;
+            T.hdist = hdist;
+            for (int i = 0; i < 19; ++i) T.clfreq[i] = 0;
+            const int total = hlit + hdist;
+            int ncl = 0, i = 0;
+            while (i < total) {
+                const int v = i < hlit ? T.llen[i] : T.dlen[i - hlit];
+                int run = 1;
+                while (i + run < total && (i + run < hlit ? T.llen[i + run] : T.dlen[i + run - hlit]) == v) ++run;
+                i += run;
+                if (v == 0) {
+                    while (run >= 11) {
+                        const int r = run > 138 ? 138 : run;
+                        T.clsym[ncl] = 18; T.clext[ncl++] = (uint8_t)(r - 11); T.clfreq[18]++;
+                        run -= r;
+                    }
+                    if (run >= 3) {
+                        T.clsym[ncl] = 17; T.clext[ncl++] = (uint8_t)(run - 3); T.clfreq[17]++;
+                        run = 0;
+                    }
+                    while (run-- > 0) { T.clsym[ncl] = 0; T.clext[ncl++] = 0; T.clfreq[0]++; }
+                } else {
+                    T.clsym[ncl] = (uint8_t)v; T.clext[ncl++] = 0; T.clfreq[v]++;
+                    --run;
+                    while (run >= 3) {
+                        const int r = run > 6 ? 6 : run;
+                        T.clsym[ncl] = 16; T.clext[ncl++] = (uint8_t)(r - 3); T.clfreq[16]++;
+                        run -= r;
+                    }
+                    while (run-- > 0) { T.clsym[ncl] = (uint8_t)v; T.clext[ncl++] = 0; T.clfreq[v]++; }
                 }
-                if (run >= 3) {
-                    T.clsym[ncl] = 17; T.clext[ncl++] = (uint8_t)(run - 3); T.clfreq[17]++;
-                    run = 0;
-                }
-                while (run-- > 0) { T.clsym[ncl] = 0; T.clext[ncl++] = 0; T.clfreq[0]++; }
-            } else {
-                T.clsym[ncl] = (uint8_t)v; T.clext[ncl++] = 0; T.clfreq[v]++;
-                --run;
-                while (run >= 3) {
-                    const int r = run > 6 ? 6 : run;
-                    T.clsym[ncl] = 16; T.clext[ncl++] = (uint8_t)(r - 3); T.clfreq[16]++;
-                    run -= r;
-                }
-                while (run-- > 0) { T.clsym[ncl] = (uint8_t)v; T.clext[ncl++] = 0; T.clfreq[v]++; }
             }
+            T.ncl = ncl;
         }
-        T.ncl = ncl;
+        __syncthreads();
+        huff_lengths(&T, T.clfreq, 19, 7, T.cllen, t);
+        huff_codes(T.cllen, 19, T.clcode, t);
+    } else {
+        __syncthreads();                               // the counts above and cost_static's zero before the sums below
     }
-    __syncthreads();
-    huff_lengths(&T, T.clfreq, 19, 7, T.cllen, t);
-    huff_codes(T.cllen, 19, T.clcode, t);
 
     // 3b. which block type?  Body cost under both code sets from the histograms (extra bits included), the
     //     dynamic header from its run-length form, the stored size exactly -- the comparison zng_tr_flush_block
@@ -525,14 +532,14 @@ void emit_dynamic_kernel(const BlkJob *__restrict__ jobs, const unsigned long lo
             if (f) {
                 const uint32_t eb = (sy < 265 || sy == 285) ? 0u : (uint32_t)(sy - 261) >> 2;
                 const uint32_t sl = sy < 144 ? 8u : (sy < 256 ? 9u : (sy < 280 ? 7u : 8u));   // RFC 1951 3.2.6
-                cd += f * (T.llen[sy] + eb);
+                if constexpr (!kForceStatic) cd += f * (T.llen[sy] + eb);
                 cs += f * (sl + eb);
             }
         }
         if (t < 30) {
             const uint32_t f = T.dfreq0[t];
             const uint32_t eb = t < 4 ? 0u : ((uint32_t)t >> 1) - 1u;
-            cd += f * (T.dlen[t] + eb);
+            if constexpr (!kForceStatic) cd += f * (T.dlen[t] + eb);
             cs += f * (5u + eb);
         }
         if (cd) atomicAdd(&T.cost_dyn, cd);
@@ -542,7 +549,10 @@ void emit_dynamic_kernel(const BlkJob *__restrict__ jobs, const unsigned long lo
     __syncthreads();
     const uint32_t nbytes = hi - lo;
     const uint32_t nstored = nbytes ? (nbytes + 65534u) / 65535u : 1u;     // stored blocks hold <= 65535 bytes
-    if (t == 0) {
+    if (kForceStatic && t == 0) {
+        const uint32_t static_lenb = (3u + T.cost_static + 7u) >> 3;
+        T.mode = nbytes + 5u * nstored <= static_lenb ? 2u : 1u;
+    } else if (t == 0) {
         static const uint8_t order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
         int hclen = 19;
         while (hclen > 4 && T.cllen[order[hclen - 1]] == 0) --hclen;
@@ -841,10 +851,19 @@ unsigned long long *g_rows_stamps = nullptr;      // ZR_ROWS_STAMPS builds: devi
 // links at levels 2..6); level 1 = deflate_quick's single probe (deflate_quick.c:89-97)
 static const uint32_t kLevelCand[10] = {0, 1, 2, 3, 6, 8, 16, 16, 16, 16};
 
+}  // namespace zr
+
+#include "deflate_rle.h"      // K1 of Z_RLE / Z_HUFFMAN_ONLY: writes the scratch of SegJob / kMaxSub / kHistWords above
+
+namespace zr {
+
+// zlib-ng's strategy codes (zlib-ng.h.in); Z_FILTERED (1) runs as the default strategy, as it always has here
+constexpr int kZHuffmanOnly = 2, kZRle = 3, kZFixed = 4;
+
 // The launches of one round: `njobs` streams, all their segments in one job list.  Asynchronous on `st`; *results =
 // pinned host words {compressed size, does-not-fit flag} per stream, valid once the stream has been synchronised.
 // cap_override: out_cap of job 0 when the caller's job struct cannot hold it (a single stream of >= 4 GiB of room).
-static int deflate_rows_enqueue(int level, const zng_rocm_stream_job *sjobs, size_t njobs, const size_t *cap_override,
+static int deflate_rows_enqueue(int level, int strategy, const zng_rocm_stream_job *sjobs, size_t njobs, const size_t *cap_override,
                                 uint32_t seg_bytes, Workspace *ws, hipStream_t st, unsigned long long **results,
                                 unsigned long long *d_results_copy = nullptr) {
     size_t nseg = 0;
@@ -940,9 +959,18 @@ static int deflate_rows_enqueue(int level, const zng_rocm_stream_job *sjobs, siz
     for (size_t i = 0; i < nb; ++i) blk[i].out = d_slots + (size_t)blk[i].out;
     ZR_HIP(hipMemcpyAsync(d_jobs, jobs, seg_tab + nb * sizeof(BlkJob), hipMemcpyHostToDevice, st));
 
-    ZR_LAUNCH_TRACED(lz_rows_kernel, dim3((unsigned)nseg), dim3(kRowBatch), st, d_jobs, d_bm, d_d16, d_hist, kLevelCand[level], g_rows_stamps);
+    // K1: the level's matcher, or the strategy's own front end (the same scratch either way)
+    if (strategy == kZHuffmanOnly)
+        ZR_LAUNCH_TRACED(rle_rows_kernel<true>, dim3((unsigned)nseg), dim3(kRleThreads), st, d_jobs, d_bm, d_d16, d_hist);
+    else if (strategy == kZRle)
+        ZR_LAUNCH_TRACED(rle_rows_kernel<false>, dim3((unsigned)nseg), dim3(kRleThreads), st, d_jobs, d_bm, d_d16, d_hist);
+    else
+        ZR_LAUNCH_TRACED(lz_rows_kernel, dim3((unsigned)nseg), dim3(kRowBatch), st, d_jobs, d_bm, d_d16, d_hist, kLevelCand[level], g_rows_stamps);
     ZR_HIP(hipGetLastError());
-    hipLaunchKernelGGL(emit_dynamic_kernel, dim3((unsigned)nb), dim3(256), 0, st, d_blk, d_bm, d_d16, d_hist, d_seg_len);
+    if (strategy == kZFixed)
+        hipLaunchKernelGGL(emit_dynamic_kernel<true>, dim3((unsigned)nb), dim3(256), 0, st, d_blk, d_bm, d_d16, d_hist, d_seg_len);
+    else
+        hipLaunchKernelGGL(emit_dynamic_kernel<false>, dim3((unsigned)nb), dim3(256), 0, st, d_blk, d_bm, d_d16, d_hist, d_seg_len);
     ZR_HIP(hipGetLastError());
     hipLaunchKernelGGL(segments_scan_kernel, dim3(1), dim3(1024), 0, st, d_blk, d_seg_len, (uint32_t)nb, d_excl, d_dst_off, d_res);
     ZR_HIP(hipGetLastError());
@@ -982,6 +1010,13 @@ int zng_rocm_deflate_dev(int level, const uint8_t *d_in, size_t in_len, uint8_t 
 
 int zng_rocm_deflate_block_dev(int level, const uint8_t *d_in, size_t in_len, uint32_t dict_len, uint32_t flags,
                                uint8_t *d_out, size_t out_cap, size_t *out_len, void *stream) {
+    return zng_rocm_deflate_strategy_block_dev(level, 0, d_in, in_len, dict_len, flags, d_out, out_cap, out_len, stream);
+}
+
+// Level 0 is stored blocks whatever the strategy (deflate.c:1039-1043 tests the level first); Z_HUFFMAN_ONLY and Z_RLE
+// replace the matcher (deflate_rle.h), Z_FIXED restricts the block types to stored / static (emit_dynamic_kernel<true>).
+int zng_rocm_deflate_strategy_block_dev(int level, int strategy, const uint8_t *d_in, size_t in_len, uint32_t dict_len,
+                                        uint32_t flags, uint8_t *d_out, size_t out_cap, size_t *out_len, void *stream) {
     if (!ctx()) {
         set_error("zng_rocm_init() has not succeeded");
         return ZNG_ROCM_ENODEV;
@@ -989,6 +1024,10 @@ int zng_rocm_deflate_block_dev(int level, const uint8_t *d_in, size_t in_len, ui
     if (!out_len || !d_out || (!d_in && in_len)) return ZNG_ROCM_EINVAL;
     if (level < 0 || level > 9) {
         set_error("level %d is outside 0..9", level);
+        return ZNG_ROCM_EINVAL;
+    }
+    if (strategy < 0 || strategy > kZFixed) {
+        set_error("strategy %d is outside 0..4", strategy);
         return ZNG_ROCM_EINVAL;
     }
     if (dict_len > kPrime || (flags & ~(uint32_t)(ZNG_ROCM_BLOCK_NOT_FINAL | ZNG_ROCM_BLOCK_SYNC_FLUSH))) {
@@ -1042,7 +1081,7 @@ int zng_rocm_deflate_block_dev(int level, const uint8_t *d_in, size_t in_len, ui
     one.dict_len = dict_len;
     one.flags = flags;
     unsigned long long *res = nullptr;
-    if (int rc = deflate_rows_enqueue(level, &one, 1, &out_cap, (uint32_t)seg_bytes, ws, st, &res)) return rc;
+    if (int rc = deflate_rows_enqueue(level, strategy, &one, 1, &out_cap, (uint32_t)seg_bytes, ws, st, &res)) return rc;
     ZR_HIP(hipStreamSynchronize(st));
     if (res[1]) {
         set_error("compressed size %llu exceeds out_cap", res[0]);
@@ -1081,7 +1120,7 @@ int zng_rocm_deflate_async_dev(int level, const uint8_t *d_in, size_t in_len, ui
     one.dict_len = dict_len;
     one.flags = flags;
     unsigned long long *res = nullptr;
-    return deflate_rows_enqueue(level, &one, 1, &out_cap, segment_bytes(in_len, ctx()->cus), ws, st, &res,
+    return deflate_rows_enqueue(level, 0, &one, 1, &out_cap, segment_bytes(in_len, ctx()->cus), ws, st, &res,
                                 (unsigned long long *)d_result);
 }
 
@@ -1090,9 +1129,18 @@ int zng_rocm_deflate_async_dev(int level, const uint8_t *d_in, size_t in_len, ui
 // streams go through ONE set of launches per round (a round holds up to ~4 GiB of plaintext).  Synchronous, like
 // zng_rocm_deflate_block_dev; out_lens is a host array.
 int zng_rocm_deflate_streams_dev(int level, const zng_rocm_stream_job *sjobs, size_t njobs, size_t *out_lens, void *stream) {
+    return zng_rocm_deflate_strategy_streams_dev(level, 0, sjobs, njobs, out_lens, stream);
+}
+
+int zng_rocm_deflate_strategy_streams_dev(int level, int strategy, const zng_rocm_stream_job *sjobs, size_t njobs,
+                                          size_t *out_lens, void *stream) {
     if (!ctx()) {
         set_error("zng_rocm_init() has not succeeded");
         return ZNG_ROCM_ENODEV;
+    }
+    if (strategy < 0 || strategy > kZFixed) {
+        set_error("strategy %d is outside 0..4", strategy);
+        return ZNG_ROCM_EINVAL;
     }
     if (!njobs) return ZNG_ROCM_OK;
     if (!sjobs || !out_lens) return ZNG_ROCM_EINVAL;
@@ -1131,7 +1179,7 @@ int zng_rocm_deflate_streams_dev(int level, const zng_rocm_stream_job *sjobs, si
             ++last;
         }
         unsigned long long *res = nullptr;
-        if (int rc = deflate_rows_enqueue(level, sjobs + first, last - first, nullptr, seg_bytes, ws, st, &res)) return rc;
+        if (int rc = deflate_rows_enqueue(level, strategy, sjobs + first, last - first, nullptr, seg_bytes, ws, st, &res)) return rc;
         ZR_HIP(hipStreamSynchronize(st));
         for (size_t s = first; s < last; ++s) {
             if (res[2 * (s - first) + 1]) {

@@ -142,9 +142,15 @@ class StreamsBatch:
             self.jobs[i].out_cap = self.bounds[i]
         self.out_lens = (C.c_size_t * self.n)()
 
-    def run(self, level=6, stream=None):
-        rocm._check(rocm.lib().zng_rocm_deflate_streams_dev(level, C.byref(self.jobs), self.n, C.byref(self.out_lens),
-                                                            rocm._stream_ptr(stream)), "zng_rocm_deflate_streams_dev")
+    def run(self, level=6, stream=None, strategy=0):
+        """strategy: zlib's (Z_DEFAULT_STRATEGY 0, Z_FILTERED 1, Z_HUFFMAN_ONLY 2, Z_RLE 3, Z_FIXED 4)"""
+        if strategy:
+            rc = rocm.lib().zng_rocm_deflate_strategy_streams_dev(level, strategy, C.byref(self.jobs), self.n,
+                                                                   C.byref(self.out_lens), rocm._stream_ptr(stream))
+            rocm._check(rc, "zng_rocm_deflate_strategy_streams_dev")
+        else:
+            rocm._check(rocm.lib().zng_rocm_deflate_streams_dev(level, C.byref(self.jobs), self.n, C.byref(self.out_lens),
+                                                                rocm._stream_ptr(stream)), "zng_rocm_deflate_streams_dev")
         return [int(v) for v in self.out_lens]
 
     def compressed(self, i):
@@ -152,19 +158,25 @@ class StreamsBatch:
         return self.dst[o:o + int(self.out_lens[i])].cpu().numpy().tobytes()
 
 
-def deflate_dev(src, level=6, length=None, offset=0, stream=None, dict_len=0, flags=0):
+def deflate_dev(src, level=6, length=None, offset=0, stream=None, dict_len=0, flags=0, strategy=0):
     """one large device-resident stream (or, with dict_len / flags, one BLOCK of a longer stream whose dict_len
     bytes of history sit in src in front of `offset`) -> (uint8 CUDA tensor with raw deflate, compressed length).
-    level 0 = stored, 1 = single probe, 2..9 = chain walk."""
+    level 0 = stored, 1 = single probe, 2..9 = chain walk.  strategy: zlib's (0 default, 1 Z_FILTERED, 2 Z_HUFFMAN_ONLY,
+    3 Z_RLE, 4 Z_FIXED; zng_rocm_deflate_strategy_block_dev)."""
     import torch
     rocm._need_init()
     n = src.numel() - offset if length is None else length
     cap = deflate_bound(n)
     dst = torch.empty(cap, dtype=torch.uint8, device=src.device)
     out_len = C.c_size_t(0)
-    rc = rocm.lib().zng_rocm_deflate_block_dev(level, rocm._dev_ptr(src, offset), n, dict_len, flags, rocm._dev_ptr(dst),
-                                               cap, C.byref(out_len), rocm._stream_ptr(stream))
-    rocm._check(rc, "zng_rocm_deflate_block_dev")
+    if strategy:
+        rc = rocm.lib().zng_rocm_deflate_strategy_block_dev(level, strategy, rocm._dev_ptr(src, offset), n, dict_len, flags,
+                                                            rocm._dev_ptr(dst), cap, C.byref(out_len), rocm._stream_ptr(stream))
+        rocm._check(rc, "zng_rocm_deflate_strategy_block_dev")
+    else:
+        rc = rocm.lib().zng_rocm_deflate_block_dev(level, rocm._dev_ptr(src, offset), n, dict_len, flags, rocm._dev_ptr(dst),
+                                                   cap, C.byref(out_len), rocm._stream_ptr(stream))
+        rocm._check(rc, "zng_rocm_deflate_block_dev")
     return dst, out_len.value
 
 

@@ -85,6 +85,9 @@ _PROTOS = {
     "zng_rocm_deflate_quick_bound": (C.c_size_t, [C.c_size_t]),
     "zng_rocm_deflate_quick_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "zng_rocm_deflate_streams_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "zng_rocm_deflate_strategy_block_dev": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
+                                                      C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]),
+    "zng_rocm_deflate_strategy_streams_dev": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "zng_rocm_inflate_tokens_decode": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "zng_rocm_inflate_tokens_decode_window": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
     "zng_rocm_inflate_tokens_decode_blocks": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint32, C.c_void_p,
@@ -128,6 +131,9 @@ _PROTOS = {
     "zng_rocm_hook_deflate_bound": (C.c_size_t, [C.c_size_t]),
     "zng_rocm_hook_deflate_block": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_uint32, C.c_int,
                                               C.POINTER(C.c_uint32), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "zng_rocm_hook_deflate_block_strategy": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_uint32,
+                                                       C.c_int, C.POINTER(C.c_uint32), C.c_void_p, C.c_size_t,
+                                                       C.POINTER(C.c_size_t)]),
     "zng_rocm_hook_inflate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_uint32),
                                         C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                         C.POINTER(C.c_char_p)]),
