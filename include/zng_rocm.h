@@ -394,6 +394,33 @@ int  zng_rocm_inflate_large_dev(const uint8_t *d_src, size_t src_len, const uint
  * sequential decoder did it) */
 int  zng_rocm_inflate_large_last_parts(void);
 
+/* zng_rocm_inflate_large_ex_dev flags */
+#define ZNG_ROCM_INFLATE_SUBBLOCK 1u   /* parts may also begin INSIDE a block */
+/* zng_rocm_inflate_large_dev with flags.  flags == 0 is exactly zng_rocm_inflate_large_dev (same path, bytes, status, part
+ * count).  ZNG_ROCM_INFLATE_SUBBLOCK also cuts the stream inside blocks, which is what a stream of fixed-Huffman blocks
+ * (level-1 class writers, Z_FIXED, zng_rocm_deflate_quick_dev) needs to be decoded in parts at all, and what evens out a
+ * foreign stream whose blocks expand very unequally.  Guesses are placed in the stretches between the block starts found;
+ * a dry parse of 128 symbols from each (with the fixed codes, or the tables of the dynamic header the stretch begins with)
+ * gives a bit B on the symbol grid of that block.  A part hands off at B only when it is decoding a block of the same
+ * identity (fixed codes; or the dynamic block with that header), stands at a symbol boundary and its bit position is
+ * exactly B: the part from B then decodes what the stream has there (inffast_tpl.h:151-298 from B on; the headers around
+ * it inflate.c:735-917).  A part that began inside a fixed-code block does not know that block's BFINAL; the part in front
+ * of it does, and when it is set the stream ends at the first end of block behind B (so *in_used is the reference's
+ * also with bytes behind the stream).  Everything irregular goes to the sequential decoder as in zng_rocm_inflate_large_dev.
+ * Unknown flag bits return ZNG_ROCM_EINVAL with nothing launched or written to d_dst; that value equals Z_DATA_ERROR, and
+ * such a refusal is told apart by *out_len = *in_used = 0 and zng_rocm_last_error() naming the flag bits (a data error
+ * of the stream says the reference's message instead).  Synchronous. */
+int  zng_rocm_inflate_large_ex_dev(const uint8_t *d_src, size_t src_len, const uint8_t *d_window, uint32_t window_len,
+                                   uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, size_t *in_used, uint32_t flags,
+                                   void *stream);
+/* of the parts on the calling thread's last chain, how many began inside a block (0: none did, or the sequential decoder
+ * did the work); thread-local like zng_rocm_inflate_large_last_parts */
+int  zng_rocm_inflate_large_last_subparts(void);
+/* how many sub-starts (bit positions inside blocks, after the dry parse) the calling thread's last
+ * ZNG_ROCM_INFLATE_SUBBLOCK call placed, whether or not the sequential decoder did the work in the end; with
+ * zng_rocm_inflate_large_last_subparts() it gives the share that a genuine decode landed on */
+int  zng_rocm_inflate_large_last_substarts(void);
+
 /* Many independent raw streams at once: `nthreads` host threads (<= 0: as many as the host gives us) take the jobs in
  * order, each decoding on the host and resolving on the device on its own HIP stream, so that the sequential decode
  * -- where an inflate spends its time -- runs on all the cores the caller allows while the device work of one stream

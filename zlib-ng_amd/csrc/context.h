@@ -76,6 +76,8 @@ enum ScratchSlot {
     kScrLargeSrc,           // device: the compressed bytes of a large HOST-resident stream (zng_rocm_inflate_raw*)
     kScrLargeCandHost,      // pinned: the finder's counts and the first candidates
     kScrLargePartsHost,     // pinned: jobs | starts | results of the parts
+    kScrLargeSub,           // device: regions | guesses' symbol boundaries | their keys (ZNG_ROCM_INFLATE_SUBBLOCK)
+    kScrLargeSubHost,       // pinned: the same
     kScrCount
 };
 

@@ -27,7 +27,21 @@ int launch_inflate_streams_device(const InflateJobDev *d_jobs, size_t njobs, uin
 
 // the parts of ONE large stream, 16-bit symbols out (inflate_large.hip); results: 8 words per part; d_marks (or null):
 // 4 words per part, where its last block inside the input ended
+// d_side (or null): starts inside blocks -- d_starts then holds njobs keys behind the njobs bits (0 a block start, 1 inside a
+// fixed-code block, H + 2 inside the dynamic block at H), and d_side takes 8 words per part (inflate_streams_kernel<..., SUB>)
 int launch_inflate_parts_device(const InflateJobDev *d_jobs, size_t njobs, uint32_t *d_results, const unsigned long long *d_starts,
-                                bool many, hipStream_t stream, uint32_t *d_marks = nullptr);
+                                bool many, hipStream_t stream, uint32_t *d_marks = nullptr, uint32_t *d_side = nullptr);
+
+// a region of the stream that starts at a block start the finder gave (one work item: at most 64 guesses, so a long region
+// is several items): `n` guesses at start + (k0 + k) * spacing, k = 1 .. n, written to out_bit / out_key [first + 2 (k - 1)] (a symbol boundary B and its key, or ~0 = none) and, when the region's
+// block does not have fixed codes and `fixed_too` is set, [first + 2 (k - 1) + 1] with fixed codes (a noise start inside a
+// fixed-code block reads as a dynamic header or a stored block's pattern); `dynamic` = 0: no guesses with a dynamic block's
+// tables
+struct SubRegionDev {
+    unsigned long long start, spacing;
+    uint32_t           first, n, dynamic, fixed_too, k0;
+};
+int launch_subblock_sync(const uint8_t *d_src, size_t src_len, const SubRegionDev *d_regions, size_t nregions,
+                         unsigned long long *d_bit, unsigned long long *d_key, hipStream_t stream);
 
 }  // namespace zr

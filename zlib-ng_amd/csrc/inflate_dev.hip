@@ -277,7 +277,7 @@ __device__ __forceinline__ uint32_t long_code(LDS &L, int which, int root, const
 // Hazards (the assembler inserts no wait states into inline asm): on gfx950 a VALU write of an SGPR/VCC needs two
 // instructions before a VALU reads it -- the v_cmp / masked-operation pairs below are spaced accordingly; LDS operations
 // of one wave execute in order, so a ds_read after a ds_write of the same bytes needs no wait.
-#define ZR_INFLATE_FAST_LOOP(RD, WR, GL, BEFORE)                                                                       \
+#define ZR_INFLATE_FAST_LOOP(RD, WR, GL, BEFORE, WLIM)                                                                     \
     "s_mov_b32 s43, 0\n\t"                                                                                             \
     /* Inside the loop the two counters the literal path tests live BIASED, so that the instruction that updates them    \
        sets SCC and no compare is needed (the scalar unit is what sixteen streams per CU share): cnt as cnt - 32 (a       \
@@ -287,7 +287,7 @@ __device__ __forceinline__ uint32_t long_code(LDS &L, int which, int root, const
     "s_cmp_lt_i32 %[cnt], 0\n\t"                                                                                       \
     "s_cbranch_scc0 L_look_%=\n\t"                                                                                     \
     "L_refill_%=:\n\t"                                                                                                 \
-    "s_cmp_eq_u32 %[widx], 64\n\t"                                                                                     \
+    "s_cmp_eq_u32 %[widx], " WLIM "\n\t"                                                                              \
     "s_cbranch_scc1 L_exit0_%=\n\t"                                                                                    \
     "v_readlane_b32 s42, %[cur], %[widx]\n\t"                                                                          \
     "s_add_u32 %[widx], %[widx], 1\n\t"                                                                                \
@@ -345,7 +345,7 @@ __device__ __forceinline__ uint32_t long_code(LDS &L, int which, int root, const
     "L_havelen_%=:\n\t"                                                                                                \
     "s_cmp_lt_i32 %[cnt], 0\n\t"                                                                                       \
     "s_cbranch_scc0 L_dist_%=\n\t"                                                                                     \
-    "s_cmp_eq_u32 %[widx], 64\n\t"                                                                                     \
+    "s_cmp_eq_u32 %[widx], " WLIM "\n\t"                                                                              \
     "s_cbranch_scc1 L_exit1_%=\n\t"                                                                                    \
     "v_readlane_b32 s42, %[cur], %[widx]\n\t"                                                                          \
     "s_add_u32 %[widx], %[widx], 1\n\t"                                                                                \
@@ -652,7 +652,15 @@ __device__ __forceinline__ uint32_t long_code(LDS &L, int which, int root, const
 // index of the start it ended on, BFINAL seen}.  `marks` (parts only, may be null): 4 words per part, the state where its
 // last block that ended inside the input ended {symbols produced, bit (lo, hi), furthest reach} -- what a part that ran
 // out of input can still deliver (the streaming hook's blocks mode).
-template <int RING, bool PART, bool COMPACT = false>
+// SUB (parts only, zng_rocm_inflate_large_ex_dev with ZNG_ROCM_INFLATE_SUBBLOCK): a start may lie INSIDE a block.  keys[job]
+// names the start: 0 a block start, 1 a symbol boundary inside a fixed-code block, H + 2 one inside the dynamic block whose
+// header is at bit H.  A part hands off at such a sub-start -- stops there, `hit` = its index -- only when it decodes a
+// block of the same identity (fixed; or the dynamic block whose header it read at H), stands at a symbol boundary and its
+// bit position is exactly the start's: decoding on from there with the same tables is what the sub-part does.  A block end
+// stops a part only on a block start (key 0).  The keys follow the njobs start bits in `starts`.  `marks` is then `side`: 8 words per part {symbols, bit (lo, hi), reach where its FIRST
+// block ended (fixed-code sub-parts only: ~0 = not reached), handed off at a sub-start, BFINAL of the block it handed off
+// in (2 = unknown: a fixed-code sub-part still in its first block), 0, 0}.
+template <int RING, bool PART, bool COMPACT = false, bool SUB = false>
 __global__ __launch_bounds__(64)
 void inflate_streams_kernel(const InflateJobDev *__restrict__ jobs, uint32_t njobs, uint32_t *__restrict__ results,
                             const unsigned long long *__restrict__ starts, uint32_t *__restrict__ marks) {
@@ -717,8 +725,21 @@ void inflate_streams_kernel(const InflateJobDev *__restrict__ jobs, uint32_t njo
         return 32ull * wnext - 8ull * lead - cnt;
     };
     uint32_t reach = 0, hit = 0xffffffffu;               // PART: furthest source in front of the part; the start it ended on
+    // SUB: the part's own key; the identity of the block being decoded (1 fixed, H + 2 dynamic) and the next sub-start of
+    // that identity ahead (its bit, its index; ~0 = none); handed off; a fixed-code sub-part still in its first block
+    const unsigned long long *const keys = starts + njobs;
+    uint32_t *const side = marks;
+    unsigned long long entry = 0, cur_id = 0, nextB = ~0ull;
+    uint32_t pidx = 0;
+    bool handed = false, entering = false, first_open = false;
+    if constexpr (SUB) {
+        entry = keys[job];
+        entering = entry != 0;
+        first_open = entry == 1;
+        if (lane == 0) side[8 * job + 0] = 0xffffffffu;
+    }
     if (PART) {
-        const unsigned long long sb = starts[job];
+        const unsigned long long sb = SUB && entry >= 2 ? entry - 2 : starts[job];     // (a dynamic sub-part reads its header first)
         seek((uint32_t)(sb >> 3));
         hold >>= (uint32_t)(sb & 7ull);
         cnt -= (uint32_t)(sb & 7ull);
@@ -817,18 +838,41 @@ void inflate_streams_kernel(const InflateJobDev *__restrict__ jobs, uint32_t njo
             if (starts[mid] < b) lo = mid + 1u;
             else hi = mid;
         }
-        if (lo < njobs && starts[lo] == b) {
+        if (lo < njobs && starts[lo] == b && (!SUB || keys[lo] == 0)) {     // (a block start sorts first among equal bits)
             hit = lo;
             return true;
         }
         return false;
+    };
+    // SUB: the first start at index >= i with the current block's identity and a bit >= b (a bounded look: the starts of
+    // one identity are consecutive but for a noise candidate now and then; one that is missed only makes a part longer)
+    auto next_sub = [&](uint32_t i, unsigned long long b) __attribute__((always_inline)) {
+        nextB = ~0ull;
+        for (uint32_t k = 0; k < 32u && i < njobs; ++k, ++i) {
+            const unsigned long long sbit = starts[i];
+            if (sbit >= b && keys[i] == cur_id) {
+                nextB = sbit;
+                pidx = i;
+                break;
+            }
+        }
+    };
+    // SUB, at a symbol boundary: move past a pending sub-start that lies behind, then hand off when the boundary is it
+    auto lands = [&]() __attribute__((always_inline)) -> bool {
+        if (nextB == ~0ull) return false;
+        const unsigned long long b = bit_pos();
+        if (b > nextB) next_sub(pidx + 1u, b);
+        if (b != nextB) return false;
+        hit = pidx;
+        handed = true;
+        return true;
     };
     bool last = false;
     while (!last && msg == kMsgNone) {
         if constexpr (PART) {
             // a block starts here: everything in front of it is complete, if the bits it took are all input (the zero bits
             // behind a truncated stream decode to something too).  Stored once per block, so no register holds it.
-            if (marks) {
+            if (!SUB && marks) {
                 const unsigned long long b = bit_pos();
                 if (b <= 8ull * in_len && lane == 0) {
                     marks[4 * job + 0] = op;
@@ -838,12 +882,18 @@ void inflate_streams_kernel(const InflateJobDev *__restrict__ jobs, uint32_t njo
                 }
             }
         }
-        if (cnt < 32) append();
-        last = hold & 1u;
-        const uint32_t type = (uint32_t)(hold >> 1) & 3u;
-        hold >>= 3;
-        cnt -= 3;
+        uint32_t type = 1;
+        unsigned long long hdr_bit = 0;
+        if (!(SUB && entering && entry == 1)) {          // (a fixed-code sub-part starts behind a header it never sees)
+            if constexpr (SUB) hdr_bit = bit_pos();
+            if (cnt < 32) append();
+            last = hold & 1u;
+            type = (uint32_t)(hold >> 1) & 3u;
+            hold >>= 3;
+            cnt -= 3;
+        }
         if (type == 3) { msg = kMsgBlockType; break; }
+        if (SUB && entering && type != (entry == 1 ? 1u : 2u)) { msg = kMsgBlockType; break; }
         if (type == 0) {
             // stored block (inflate.c:759-800): LEN / NLEN at the next byte boundary, then LEN raw bytes
             service();
@@ -959,6 +1009,28 @@ void inflate_streams_kernel(const InflateJobDev *__restrict__ jobs, uint32_t njo
             }
             widen_distances();
         }
+        if constexpr (SUB) {
+            cur_id = type == 1 ? 1ull : hdr_bit + 2ull;
+            if (entering) {                              // into the block at the sub-start's bit
+                entering = false;
+                const unsigned long long sb = starts[job];
+                if (bit_pos() > sb) { msg = kMsgBlockType; break; }
+                if (type == 2) {
+                    seek((uint32_t)(sb >> 3));
+                    hold >>= (uint32_t)(sb & 7ull);
+                    cnt -= (uint32_t)(sb & 7ull);
+                }
+            }
+            // the first later start of this block's identity (binary search for the bit, then a short look)
+            const unsigned long long b = bit_pos();
+            uint32_t lo = job + 1u, hi = njobs;
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (starts[mid] < b) lo = mid + 1u;
+                else hi = mid;
+            }
+            next_sub(lo, b);
+        }
 
         // ---- symbol loop: the decode AND store halves of inflate_fast (inffast_tpl.h:140-300) -----------------------
         // Each round: the hand-written fast loop (ZR_INFLATE_FAST_LOOP) runs until a symbol needs more than it does, then
@@ -967,12 +1039,29 @@ void inflate_streams_kernel(const InflateJobDev *__restrict__ jobs, uint32_t njo
                        lds_dist = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void *)L.dist,
                        lds_ring = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void *)L.ring;
         for (;;) {
+            if constexpr (SUB) {
+                if (lands()) break;                     // a symbol boundary
+            }
             if (npend == 64) {
                 service();
                 if (msg != kMsgNone) break;
             }
             uint32_t stage, len = 0, dist = 0;
-            {
+            // SUB: the fast loop must not start a symbol at or behind a pending sub-start: it takes no word that ends more
+            // than 31 bits behind it (it starts a symbol only with 32 bits in the buffer), and is skipped when the buffer
+            // already holds such a word -- those symbols go one at a time through the code below
+            bool fast = true;
+            uint32_t wlim = 64;
+            if constexpr (SUB) {
+                if (nextB != ~0ull) {
+                    const unsigned long long wB = (nextB + 31ull + 8ull * lead) >> 5;
+                    if (wB <= (unsigned long long)wnext) fast = false;
+                    else if (wB - cbase < 64ull) wlim = (uint32_t)(wB - cbase);
+                }
+            }
+            if (!fast) {
+                stage = 0;
+            } else {
                 uint32_t widx = wnext - cbase, opb = op - npend + 64u, t0, t1, t2, ee, opx, va, vb, vr, vd0, vd1, vd2, vd3, vd4;
                 // no flush is due and the match fits `out` while op + len <= oplim (what service() would test)
                 const uint32_t fl = flushed + kFlushAt - 1u, oplim = out_cap < fl ? out_cap : fl;
@@ -983,8 +1072,19 @@ void inflate_streams_kernel(const InflateJobDev *__restrict__ jobs, uint32_t njo
 #ifdef ZR_INFLATE_STATS
                 const unsigned long long zr_t0 = __builtin_readcyclecounter();
 #endif
-                if constexpr (sizeof(T) == 1) {
-                    asm volatile(ZR_INFLATE_FAST_LOOP("ds_read_u8", "ds_write_b8", "global_load_ubyte", ZR_INFLATE_BEFORE_STREAM)
+                if constexpr (SUB) {
+                    asm volatile(ZR_INFLATE_FAST_LOOP("ds_read_u16", "ds_write_b16", "global_load_ushort", ZR_INFLATE_BEFORE_PART, "%[wlim]")
+                                 : "+{s[40:41]}"(hold), [cnt] "+s"(cnt), [widx] "+s"(widx), [npend] "+s"(npend), [opb] "+s"(opb),
+                                   [lit] "+v"(litbuf), [reach] "+s"(reach), [stage] "=&s"(stage), [len] "=&s"(len), [dist] "=&s"(dist), [e] "=&s"(ee),
+                                   [t0] "=&s"(t0), [t1] "=&s"(t1), [t2] "=&s"(t2), [op] "=&s"(opx), [va] "=&v"(va), [vb] "=&v"(vb), [vr] "=&v"(vr), [vd0] "=&v"(vd0), [vd1] "=&v"(vd1),
+                                   [vd2] "=&v"(vd2), [vd3] "=&v"(vd3), [vd4] "=&v"(vd4)
+                                 : [lane] "v"(lane), [laneb] "v"(laneb), [cur] "v"(cur), [a0] "s"(a0), [a0m] "s"(a0 - 64u), [oplim] "s"(oplim), [litb] "s"(lds_lit),
+                                   [distb] "s"(lds_dist), [ringb] "s"(lds_ring), [outp] "s"(out_addr), [dictlen] "s"(dict_len), [near] "n"(kNear), [mask] "n"(M), [sh] "n"(1),
+                                   [litroot] "n"(kLitRoot), [distroot] "n"(kDistRoot), [o1] "n"(64 * sizeof(T)), [o2] "n"(128 * sizeof(T)),
+                                   [o3] "n"(192 * sizeof(T)), [o4] "n"(256 * sizeof(T)), [wlim] "s"(wlim)
+                                 : "scc", "vcc", "memory", "s42", "s43", "s44", "s45");
+                } else if constexpr (sizeof(T) == 1) {
+                    asm volatile(ZR_INFLATE_FAST_LOOP("ds_read_u8", "ds_write_b8", "global_load_ubyte", ZR_INFLATE_BEFORE_STREAM, "64")
                                  : "+{s[40:41]}"(hold), [cnt] "+s"(cnt), [widx] "+s"(widx), [npend] "+s"(npend), [opb] "+s"(opb),
                                    [lit] "+v"(litbuf), [reach] "+s"(reach), [stage] "=&s"(stage), [len] "=&s"(len), [dist] "=&s"(dist), [e] "=&s"(ee),
                                    [t0] "=&s"(t0), [t1] "=&s"(t1), [t2] "=&s"(t2), [op] "=&s"(opx), [va] "=&v"(va), [vb] "=&v"(vb), [vr] "=&v"(vr), [vd0] "=&v"(vd0), [vd1] "=&v"(vd1),
@@ -995,7 +1095,7 @@ void inflate_streams_kernel(const InflateJobDev *__restrict__ jobs, uint32_t njo
                                    [o3] "n"(192 * sizeof(T)), [o4] "n"(256 * sizeof(T))
                                  : "scc", "vcc", "memory", "s42", "s43", "s44", "s45");
                 } else {
-                    asm volatile(ZR_INFLATE_FAST_LOOP("ds_read_u16", "ds_write_b16", "global_load_ushort", ZR_INFLATE_BEFORE_PART)
+                    asm volatile(ZR_INFLATE_FAST_LOOP("ds_read_u16", "ds_write_b16", "global_load_ushort", ZR_INFLATE_BEFORE_PART, "64")
                                  : "+{s[40:41]}"(hold), [cnt] "+s"(cnt), [widx] "+s"(widx), [npend] "+s"(npend), [opb] "+s"(opb),
                                    [lit] "+v"(litbuf), [reach] "+s"(reach), [stage] "=&s"(stage), [len] "=&s"(len), [dist] "=&s"(dist), [e] "=&s"(ee),
                                    [t0] "=&s"(t0), [t1] "=&s"(t1), [t2] "=&s"(t2), [op] "=&s"(opx), [va] "=&v"(va), [vb] "=&v"(vb), [vr] "=&v"(vr), [vd0] "=&v"(vd0), [vd1] "=&v"(vd1),
@@ -1024,6 +1124,11 @@ void inflate_streams_kernel(const InflateJobDev *__restrict__ jobs, uint32_t njo
                 if (stage == 1) ZR_STAT(widx == 64 ? 4 : 5);                          // words used up / long or bad distance code
                 if (stage == 2) ZR_STAT(len > 64 ? 6 : op + len > oplim ? 7 : dist > op ? 8 : dist < len ? 9 : 10);
                 if (stage == 0 && npend == 64) continue;
+                if constexpr (SUB) {
+                    // the word limit stops the fast loop at the last boundary in front of the pending sub-start's word,
+                    // and that boundary is often the sub-start itself: compare before the symbol there is decoded
+                    if (stage == 0 && lands()) break;
+                }
             }
             if (stage == 0) {
                 if (cnt < 32) append();
@@ -1045,7 +1150,21 @@ void inflate_streams_kernel(const InflateJobDev *__restrict__ jobs, uint32_t njo
                 }
                 hold >>= nb;
                 cnt -= nb;
-                if (sym == 256u) break;                                               // end of block
+                if (sym == 256u) {                                                    // end of block
+                    if constexpr (SUB) {
+                        if (first_open) {                    // a fixed-code sub-part's first block: where it ended
+                            first_open = false;
+                            const unsigned long long b = bit_pos();
+                            if (lane == 0) {
+                                side[8 * job + 0] = op;
+                                side[8 * job + 1] = (uint32_t)b;
+                                side[8 * job + 2] = (uint32_t)(b >> 32);
+                                side[8 * job + 3] = reach;
+                            }
+                        }
+                    }
+                    break;
+                }
                 // length: base and extra bits from the symbol (RFC 1951 3.2.5; inftrees.c:38-45 tabulate the same)
                 const uint32_t k = sym - 257u;
                 if (k < 8u) {
@@ -1128,6 +1247,7 @@ void inflate_streams_kernel(const InflateJobDev *__restrict__ jobs, uint32_t njo
             }
             op += len;
         }
+        if (SUB && handed) break;
         if (PART && !last && msg == kMsgNone && block_end_stop()) break;
     }
 #ifdef ZR_INFLATE_STATS
@@ -1153,11 +1273,15 @@ void inflate_streams_kernel(const InflateJobDev *__restrict__ jobs, uint32_t njo
             results[8 * job + 0] = op;
             results[8 * job + 1] = (uint32_t)b;
             results[8 * job + 2] = (uint32_t)(b >> 32);
-            results[8 * job + 3] = msg == kMsgNone ? (last ? 1u : 0u) : (msg == kMsgStarved || msg == kMsgOutFull) ? (uint32_t)-5 : (uint32_t)-3;
+            results[8 * job + 3] = msg == kMsgNone ? (last && !handed ? 1u : 0u) : (msg == kMsgStarved || msg == kMsgOutFull) ? (uint32_t)-5 : (uint32_t)-3;
             results[8 * job + 4] = msg;
             results[8 * job + 5] = reach;
             results[8 * job + 6] = hit;
             results[8 * job + 7] = last ? 1u : 0u;
+            if constexpr (SUB) {
+                side[8 * job + 4] = handed ? 1u : 0u;
+                side[8 * job + 5] = first_open ? 2u : last ? 1u : 0u;
+            }
         }
         return;
     }
@@ -1196,8 +1320,16 @@ int launch_inflate_streams_device(const InflateJobDev *d_jobs, size_t njobs, uin
 // call lasts as long as its longest part, and a part is faster in the plain layout among 12 (a CPython stream: 12.4
 // against 13.2 ms): two instantiations, chosen per call.
 int launch_inflate_parts_device(const InflateJobDev *d_jobs, size_t njobs, uint32_t *d_results, const unsigned long long *d_starts,
-                                bool many, hipStream_t st, uint32_t *d_marks) {
+                                bool many, hipStream_t st, uint32_t *d_marks, uint32_t *d_side) {
     if (!njobs) return ZNG_ROCM_OK;
+    if (d_side) {                                        // starts inside blocks (SUB): instantiations of their own
+        if (many)
+            ZR_LAUNCH_TRACED((inflate_streams_kernel<4096, true, true, true>), dim3((unsigned)njobs), dim3(64), st, d_jobs, (uint32_t)njobs, d_results, d_starts, d_side);
+        else
+            ZR_LAUNCH_TRACED((inflate_streams_kernel<4096, true, false, true>), dim3((unsigned)njobs), dim3(64), st, d_jobs, (uint32_t)njobs, d_results, d_starts, d_side);
+        ZR_HIP(hipGetLastError());
+        return ZNG_ROCM_OK;
+    }
 #ifdef ZR_MEASURE_FORMS
     static const int ring = [] {
         const char *r = getenv("ZNG_ROCM_PART_RING");
@@ -1213,6 +1345,214 @@ int launch_inflate_parts_device(const InflateJobDev *d_jobs, size_t njobs, uint3
         ZR_LAUNCH_TRACED((inflate_streams_kernel<4096, true, true>), dim3((unsigned)njobs), dim3(64), st, d_jobs, (uint32_t)njobs, d_results, d_starts, d_marks);
     else
         ZR_LAUNCH_TRACED((inflate_streams_kernel<4096, true, false>), dim3((unsigned)njobs), dim3(64), st, d_jobs, (uint32_t)njobs, d_results, d_starts, d_marks);
+    ZR_HIP(hipGetLastError());
+    return ZNG_ROCM_OK;
+}
+
+
+// ---- sub-starts: the dry parse that turns a guessed bit into a symbol boundary (zng_rocm_inflate_large_ex_dev) ----------
+// A region of the stream begins at a start the finder gave (inflate_large.hip); the block there (or, behind a stored block,
+// the next one) is read once: fixed codes, or a dynamic header decoded and its tables built in LDS with the part kernel's
+// builder.  Then each lane takes one guess G
+// inside the region and parses kSyncSymbols symbols from it with those tables, writing nothing: a parse that starts
+// off the symbol grid falls onto it within a few symbols (codes of a prefix code resynchronise), so the bit it ends on
+// is, with high probability, a true symbol boundary B of the block -- and where it is not, nothing is lost: a part hands
+// off only where a genuine decode stands exactly on B with the same tables (inflate_streams_kernel<..., SUB>).  A code the
+// tables do not have (fixed: literal/length 286, 287, distance 30, 31; dynamic: the hole of an incomplete code), or an
+// end-of-block code within the first kSyncSymbols / 2 symbols, means the parse is off the grid (or outside the block): it
+// starts again one bit further on, up to kSyncRestarts times, and then reports no start.  An end-of-block code after that
+// ends the parse on the boundary in front of it.  K = 128: on fixed-code data 99.9 % of guesses end on a true boundary,
+// against 98.9 % with 64 (tests/test_subblock_sync_cpu.py walks a stream and checks).
+constexpr int kSyncSymbols = 128, kSyncRestarts = 32;
+
+__device__ __forceinline__ unsigned long long sync_bits_at(const uint8_t *src, unsigned long long src_len, unsigned long long bit) {
+    const unsigned long long byte = bit >> 3;
+    unsigned long long lo = 0, hi = 0;
+    if (byte + 16 <= src_len) {
+        const u32x4_unaligned v = load_u128(src + byte);
+        lo = (unsigned long long)v.x | ((unsigned long long)v.y << 32);
+        hi = (unsigned long long)v.z | ((unsigned long long)v.w << 32);
+    } else {
+        for (unsigned k = 0; k < 16 && byte + k < src_len; ++k) {
+            const unsigned long long b = load_u8(src + byte + k);
+            if (k < 8) lo |= b << (8 * k);
+            else hi |= b << (8 * (k - 8));
+        }
+    }
+    const unsigned s = (unsigned)(bit & 7ull);
+    return s ? (lo >> s) | (hi << (64 - s)) : lo;
+}
+
+// a code longer than the root, per lane (long_code is the wave-uniform form)
+template <typename LDS>
+__device__ __forceinline__ uint32_t lane_long_code(LDS &L, int which, int root, const uint16_t *sorted, unsigned long long w) {
+    const uint32_t rev15 = __builtin_bitreverse32((uint32_t)w & 0x7fffu) >> 17;
+    const int max = (int)L.cnt(which)[0];
+    for (int len = root + 1; len <= max; ++len) {
+        const uint32_t d = (rev15 >> (15 - len)) - L.first(which)[len];
+        if (d < L.cnt(which)[len]) return make_entry((uint32_t)len, sorted[ZR_IDX(L.offs(which)[len] + d, which == kCodeLit ? 288 : 32)]);
+    }
+    return kBadMark;
+}
+
+__global__ __launch_bounds__(64)
+void subblock_sync_kernel(const uint8_t *__restrict__ src, unsigned long long src_len, const SubRegionDev *__restrict__ regions,
+                          uint32_t nregions, unsigned long long *__restrict__ out_bit, unsigned long long *__restrict__ out_key) {
+    constexpr int kLR = kLitRootStream, kDR = kDistRootStream;
+    __shared__ InflateLdsStream<16, uint8_t, kDR, kLR> L;
+    const int lane = threadIdx.x;
+    const uint32_t r = blockIdx.x;
+    if (r >= nregions) return;
+    const SubRegionDev R = regions[r];
+    unsigned long long s0 = R.start;
+    uint32_t type = (uint32_t)(sync_bits_at(src, src_len, s0) >> 1) & 3u;
+    if (type == 0u) {
+        // a stored block (the last of a chain the finder's byte pattern gave): the block behind it is the region's
+        const unsigned long long q = (s0 + 3ull + 7ull) & ~7ull;
+        s0 = q + 32ull + 8ull * ((uint32_t)sync_bits_at(src, src_len, q) & 0xffffu);
+        type = (s0 >> 3) + 16 <= src_len ? (uint32_t)(sync_bits_at(src, src_len, s0) >> 1) & 3u : 3u;
+    }
+    bool ok = type == 1u || type == 2u;
+    unsigned long long pos = s0 + 3;
+    if (type == 2u) {
+        // the dynamic header (inflate.c:814-917), wave-uniform, as the part kernel reads it
+        unsigned long long w = sync_bits_at(src, src_len, pos);
+        const uint32_t nlen = ((uint32_t)w & 31u) + 257u, ndist = ((uint32_t)(w >> 5) & 31u) + 1u, ncode = ((uint32_t)(w >> 10) & 15u) + 4u;
+        pos += 14;
+        if (nlen > 286 || ndist > 30) ok = false;
+        if (lane < 19) L.cl_lens()[lane] = 0;
+        wave_sync();
+        w = sync_bits_at(src, src_len, pos);
+        if (lane == 0)
+            for (uint32_t i = 0; i < ncode; ++i) L.cl_lens()[kClOrder[i]] = (uint8_t)((w >> (3 * i)) & 7u);
+        pos += 3ull * ncode;
+        wave_sync();
+        if (ok && uni((uint32_t)build_code(L, kCodeCl, L.cl_lens(), 19, kClRoot, L.cl(), L.sorted_cl(), lane))) ok = false;
+        uint32_t have = 0;
+        while (ok && have < nlen + ndist) {
+            w = sync_bits_at(src, src_len, pos);
+            const uint32_t e = uni(L.cl()[(uint32_t)w & ((1u << kClRoot) - 1u)]);
+            const uint32_t nb = e & 15u, sym = e >> 4;
+            pos += nb;
+            w >>= nb;
+            if (sym < 16) {
+                if (lane == 0) L.lens[ZR_IDX(have, 320)] = (uint8_t)sym;
+                ++have;
+                continue;
+            }
+            uint32_t rep, val = 0;
+            if (sym == 16) {
+                rep = 3u + ((uint32_t)w & 3u);
+                pos += 2;
+                if (have == 0) { ok = false; break; }
+                wave_sync();
+                val = uni(L.lens[have - 1]);
+            } else if (sym == 17) {
+                rep = 3u + ((uint32_t)w & 7u);
+                pos += 3;
+            } else {
+                rep = 11u + ((uint32_t)w & 127u);
+                pos += 7;
+            }
+            if (have + rep > nlen + ndist) { ok = false; break; }
+            for (uint32_t k = (uint32_t)lane; k < rep; k += 64) L.lens[ZR_IDX(have + k, 320)] = (uint8_t)val;
+            have += rep;
+        }
+        wave_sync();
+        if (ok && uni(L.lens[256]) == 0) ok = false;
+        if (ok && uni((uint32_t)build_code(L, kCodeLit, L.lens, (int)nlen, kLR, L.lit, L.sorted_lit, lane))) ok = false;
+        if (ok && uni((uint32_t)build_code(L, kCodeDist, L.lens + nlen, (int)ndist, kDR, reinterpret_cast<uint16_t *>(L.dist),
+                                           L.sorted_dist, lane)))
+            ok = false;
+        if ((pos >> 3) > src_len) ok = false;
+    }
+    const uint16_t *dist16 = reinterpret_cast<const uint16_t *>(L.dist);
+    // fixed codes in the odd slots when the region does not begin with them itself (a noise start inside fixed-code data
+    // reads as a dynamic header, a stored block's pattern, or nothing valid at all)
+    const bool fixed_too = type != 1u && R.fixed_too;
+    if (type == 2u && !R.dynamic) ok = false;
+    for (uint32_t t = (uint32_t)lane; t < 2u * R.n; t += 64) {
+        const uint32_t g = t >> 1, ty = (t & 1u) ? 1u : type;       // odd slots: fixed codes in a dynamic region
+        const unsigned long long key = ty == 1u ? 1ull : s0 + 2ull;
+        unsigned long long g0 = R.start + (unsigned long long)(R.k0 + g + 1u) * R.spacing, B = ~0ull;
+        const bool go = (t & 1u) ? fixed_too : ok;
+        const unsigned long long lo = (t & 1u) ? R.start + 3ull : pos;
+        for (int again = 0; go && g0 >= lo && B == ~0ull && again <= kSyncRestarts; ++again, ++g0) {
+            unsigned long long p = g0;
+            // 32 bytes per load, refilled when fewer than 48 bits (one symbol at most) are left: the parse is a chain of
+            // dependent loads, and one per symbol made the kernel as long as its slowest lane's 128 load latencies
+            unsigned long long q0 = 0, q1 = 0, q2 = 0, q3 = 0, wbase = 0;
+            int k = 0;
+            for (; k < kSyncSymbols; ++k) {
+                if ((p >> 3) + 16 > src_len) break;
+                if (k == 0 || p - wbase > 256 - 48 - 7) {
+                    wbase = p & ~7ull;
+                    const unsigned long long byte = p >> 3;
+                    if (byte + 32 <= src_len) {
+                        const u32x4_unaligned a = load_u128(src + byte), b = load_u128(src + byte + 16);
+                        q0 = (unsigned long long)a.x | ((unsigned long long)a.y << 32);
+                        q1 = (unsigned long long)a.z | ((unsigned long long)a.w << 32);
+                        q2 = (unsigned long long)b.x | ((unsigned long long)b.y << 32);
+                        q3 = (unsigned long long)b.z | ((unsigned long long)b.w << 32);
+                    } else {
+                        q0 = sync_bits_at(src, src_len, wbase);
+                        q1 = sync_bits_at(src, src_len, wbase + 64);
+                        q2 = q3 = 0;
+                    }
+                }
+                const unsigned o = (unsigned)(p - wbase);              // < 256 - 48: the 64 bits at p lie in q0..q3
+                const unsigned long long x0 = o < 64 ? q0 : o < 128 ? q1 : o < 192 ? q2 : q3;
+                const unsigned long long x1 = o < 64 ? q1 : o < 128 ? q2 : q3;
+                const unsigned sh = o & 63u;
+                unsigned long long w = sh ? (x0 >> sh) | (x1 << (64 - sh)) : x0;
+                uint32_t sym, nb;
+                if (ty == 1u) {                            // fixed codes (RFC 1951 3.2.6) from the first 9 bits, MSB first
+                    const uint32_t r9 = __builtin_bitreverse32((uint32_t)w & 0x1ffu) >> 23;
+                    if ((r9 >> 2) < 24u) { sym = 256u + (r9 >> 2); nb = 7; }
+                    else if ((r9 >> 1) < 0xc0u) { sym = (r9 >> 1) - 0x30u; nb = 8; }
+                    else if ((r9 >> 1) < 0xc8u) { sym = 280u + (r9 >> 1) - 0xc0u; nb = 8; }
+                    else { sym = 144u + r9 - 0x190u; nb = 9; }
+                } else {
+                    uint32_t e = L.lit[(uint32_t)w & ((1u << kLR) - 1u)];
+                    if (e == kLongMark) e = lane_long_code(L, kCodeLit, kLR, L.sorted_lit, w);
+                    sym = e >> 4;
+                    nb = e & 15u;
+                }
+                if (sym == 256u) break;                    // end of block: the boundary in front of it, if enough came before
+                if (sym > 285u) { k = -1; break; }         // (includes the builder's marks for "no code")
+                p += nb;
+                w >>= nb;
+                if (sym < 256u) continue;
+                const uint32_t lk = sym - 257u;
+                const uint32_t lx = lk < 8u || lk == 28u ? 0u : (lk - 4u) >> 2;
+                p += lx;
+                w >>= lx;
+                uint32_t dsym, dnb;
+                if (ty == 1u) {
+                    dsym = __builtin_bitreverse32((uint32_t)w & 31u) >> 27;
+                    dnb = 5;
+                } else {
+                    uint32_t e = dist16[(uint32_t)w & ((1u << kDR) - 1u)];
+                    if (e == kLongMark) e = lane_long_code(L, kCodeDist, kDR, L.sorted_dist, w);
+                    dsym = e >> 4;
+                    dnb = e & 15u;
+                }
+                if (dsym > 29u) { k = -1; break; }
+                p += dnb + (dsym < 4u ? 0u : (dsym - 2u) >> 1);
+            }
+            if (k >= kSyncSymbols / 2) B = p;
+            else if (k >= 0 && (p >> 3) + 16 > src_len) break;     // the input's end, not the grid: no start
+        }
+        out_bit[R.first + t] = B;
+        out_key[R.first + t] = key;
+    }
+}
+
+int launch_subblock_sync(const uint8_t *d_src, size_t src_len, const SubRegionDev *d_regions, size_t nregions,
+                         unsigned long long *d_bit, unsigned long long *d_key, hipStream_t st) {
+    if (!nregions) return ZNG_ROCM_OK;
+    ZR_LAUNCH_TRACED(subblock_sync_kernel, dim3((unsigned)nregions), dim3(64), st, d_src, (unsigned long long)src_len, d_regions,
+                     (uint32_t)nregions, d_bit, d_key);
     ZR_HIP(hipGetLastError());
     return ZNG_ROCM_OK;
 }

@@ -45,6 +45,11 @@ constexpr uint32_t kSegmentBytes = 40u << 10;     // parts are grouped into segm
                                                   // context chain (which looks one segment back: >= 32 KiB each)
 constexpr uint32_t kSlotRatio = 64;               // symbols of slot per compressed byte of the part ...
 constexpr uint32_t kSlotSlack = 640u << 10;       // ... plus this (a 512 KiB run of one byte is ~600 bytes of deflate data)
+// SUBBLOCK (zng_rocm_inflate_large_ex_dev): guesses for starts inside blocks, one every `step` compressed bits of a region,
+// step = the stream's bits / (kSubPerSlot x the chip's resident parts), at least kSubMinStep bits -- so that a block of any
+// length is cut into pieces of about the same compressed size, whatever it expands to
+constexpr uint32_t kSubPerSlot = 4;
+constexpr uint64_t kSubMinStep = 8ull * (2u << 10);
 
 // 64 bits of the stream starting at `bit` (bits beyond the end read 0)
 __device__ __forceinline__ unsigned long long bits_at_dev(const uint8_t *src, unsigned long long src_len, unsigned long long bit) {
@@ -429,6 +434,8 @@ int inflate_resolve_symbols(const uint64_t *d_segs, size_t nsegs, uint16_t *sym,
                             uint32_t window_len, hipStream_t st);
 
 static thread_local int t_large_parts = 0;
+static thread_local int t_large_subparts = 0;           // of them, parts that began inside a block
+static thread_local int t_large_substarts = 0;          // SUBBLOCK: sub-starts placed (the sync kernel's boundaries, deduplicated)
 #ifdef ZR_INFLATE_STATS
 static std::vector<unsigned long long> g_dbg_starts;     // diagnostic builds: the last call's part starts and result words
 static std::vector<uint32_t> g_dbg_res;
@@ -444,9 +451,12 @@ static int why(const char *reason) {
 // Blocks mode (`blocks`, the streaming hook): the stream starts at bit `start_bit` of d_src, and input that ends inside a
 // block is no irregularity -- the chain stops at the first part that ran out of input, that part's complete blocks (its
 // marks) are kept, and *end_bit / *final say where the delivered blocks end and whether the BFINAL one is among them.
+// `sub` (ZNG_ROCM_INFLATE_SUBBLOCK; never with `blocks`): starts inside blocks too -- guesses in the gaps the finder leaves, the
+// sync kernel's dry parse, hand-offs on the chain (inflate_dev.hip, inflate_streams_kernel<..., SUB>).
 static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len, const uint8_t *d_window, uint32_t window_len,
                              uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, size_t *in_used, hipStream_t st,
-                             bool blocks = false, uint64_t start_bit = 0, uint64_t *end_bit_out = nullptr, int *final_out = nullptr) {
+                             bool blocks = false, uint64_t start_bit = 0, uint64_t *end_bit_out = nullptr, int *final_out = nullptr,
+                             bool sub = false) {
     if (src_len < (128u << 10) || src_len >= (1ull << 31)) return why("stream below 128 KiB (or 2 GiB and more)");
     // ---- candidates ---------------------------------------------------------------------------------------------
     const uint32_t cap1 = (uint32_t)std::min<size_t>(src_len / 64 + 4096, 64u << 20);
@@ -495,11 +505,13 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
         hipLaunchKernelGGL(validate_headers_kernel, dim3(8192), dim3(kValLanes), 0, st, d_src, (unsigned long long)src_len, d_cand,
                            d_n, cap1, d_good, d_n + 1, cap2);
         ZR_HIP(hipGetLastError());
-        // the counts and (what is almost always all of) the list in one round trip
+        // the counts and (what is almost always all of) the list in one round trip (SUBBLOCK: and the first block's header)
         ZR_HIP(hipMemcpyAsync(n12, d_n, 8, hipMemcpyDeviceToHost, st));
+        if (sub) ZR_HIP(hipMemcpyAsync(hp + 8, d_src + (start_bit >> 3), 2, hipMemcpyDeviceToHost, st));
         ZR_HIP(hipMemcpyAsync(h_good, d_good, (size_t)first * 8, hipMemcpyDeviceToHost, st));
         ZR_HIP(hipStreamSynchronize(st));
-        if (n12[0] == 0 || n12[0] > cap1) return why("no candidate block starts, or far more than a deflate stream has");
+        // (SUBBLOCK goes on without candidates: a stream of fixed-code blocks is cut inside them)
+        if ((n12[0] == 0 && !sub) || n12[0] > cap1) return why("no candidate block starts, or far more than a deflate stream has");
         if (n12[1] <= cap2) good.assign(h_good, h_good + std::min(n12[1], first));
     }
     const uint32_t n2 = n12[1];
@@ -524,6 +536,68 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
             heavy += !(b62 >> 62);
         }
     }
+    // ---- SUBBLOCK: starts inside blocks ---------------------------------------------------------------------------
+    // Guesses go into every gap between two starts found (and behind the last) -- none when the pattern pass alone cut the
+    // stream: its writer (this library's level-6 class, pigz) already closed a block every few tens of KiB, and that
+    // kernel is bound by throughput, not by a long part.  The sync kernel reads the block at the gap's start (fixed codes,
+    // or a dynamic header and its tables) and turns each guess into a symbol boundary B with that identity.  Dynamic
+    // blocks are split while the Huffman starts found are no more than the chip's resident parts (12 per CU): the 256 MiB
+    // CPython level-6 stream (about 2700 of them) takes 10.3 ms split against 10.6 ms whole; with more
+    // starts than slots the chip is full without splitting.  When the stream's first block has
+    // fixed codes, every gap that does not begin with fixed codes gets fixed-code guesses as well: about one bit position in
+    // 10^6 of fixed-code data passes F1 + F2 and one byte in 2^23 looks like a stored block's header, and the gap behind
+    // such a noise start would otherwise be one long part.
+    std::vector<unsigned long long> keys;                 // per start: 0 a block start, 1 inside a fixed-code block, H + 2 inside the dynamic block at H
+    if (sub) {
+        keys.assign(starts.size(), 0ull);
+        const unsigned long long total = 8ull * src_len - start_bit;
+        const unsigned long long step = std::max<unsigned long long>(kSubMinStep, total / (kSubPerSlot * 12ull * (unsigned long long)ctx()->cus));
+        std::vector<SubRegionDev> regions;
+        uint32_t nguess = 0;                              // guess slots: two per guess
+        const uint8_t *b0 = hp + 8;                        // (copied with the finder's counts when F1 + F2 ran)
+        const bool fixed_first = !patterns_do && ((((unsigned)b0[0] | ((unsigned)b0[1] << 8)) >> ((start_bit & 7u) + 1u)) & 3u) == 1u;
+        const uint32_t split_dynamic = heavy <= 12u * (size_t)ctx()->cus ? 1u : 0u;
+        for (size_t i = 0; i < starts.size() && !patterns_do && (split_dynamic || fixed_first); ++i) {
+            const unsigned long long s0 = starts[i], e0 = i + 1 < starts.size() ? starts[i + 1] : 8ull * src_len;
+            const unsigned long long pieces = (e0 - s0 + step / 2) / step;
+            if (pieces < 2) continue;
+            // one work item (wavefront) per 64 guesses: a long gap is not one wavefront's serial work
+            for (uint32_t k0 = 0; k0 < (uint32_t)(pieces - 1); k0 += 64u) {
+                const uint32_t n = std::min<uint32_t>(64u, (uint32_t)(pieces - 1) - k0);
+                regions.push_back(SubRegionDev{s0, (e0 - s0) / pieces, nguess, n, split_dynamic, fixed_first ? 1u : 0u, k0});
+                nguess += 2u * n;
+            }
+        }
+        if (nguess) {
+            const size_t reg_b = (regions.size() * sizeof(SubRegionDev) + 255) & ~(size_t)255, out_b = (size_t)nguess * 16;
+            uint8_t *dp = nullptr, *hp2 = nullptr;
+            if (int rc = scratch_reserve(ws, kScrLargeSub, reg_b + out_b, false, (void **)&dp)) return rc;
+            if (int rc = scratch_reserve(ws, kScrLargeSubHost, reg_b + out_b, true, (void **)&hp2)) return rc;
+            std::copy(regions.begin(), regions.end(), (SubRegionDev *)hp2);
+            unsigned long long *d_bit = (unsigned long long *)(dp + reg_b), *h_bit = (unsigned long long *)(hp2 + reg_b);
+            ZR_HIP(hipMemcpyAsync(dp, hp2, regions.size() * sizeof(SubRegionDev), hipMemcpyHostToDevice, st));
+            if (int rc = launch_subblock_sync(d_src, src_len, (const SubRegionDev *)dp, regions.size(), d_bit, d_bit + nguess, st)) return rc;
+            ZR_HIP(hipMemcpyAsync(h_bit, d_bit, out_b, hipMemcpyDeviceToHost, st));
+            ZR_HIP(hipStreamSynchronize(st));
+            std::vector<std::pair<unsigned long long, unsigned long long>> all;
+            all.reserve(starts.size() + nguess);
+            for (unsigned long long b : starts) all.emplace_back(b, 0ull);
+            for (uint32_t g = 0; g < nguess; ++g) {
+                const unsigned long long b = h_bit[g];
+                if (b != ~0ull && b > start_bit && (b >> 3) + 16 < src_len) all.emplace_back(b, h_bit[nguess + g]);
+            }
+            std::sort(all.begin(), all.end());
+            all.erase(std::unique(all.begin(), all.end()), all.end());
+            starts.clear();
+            keys.clear();
+            for (const auto &a : all) {
+                starts.push_back(a.first);
+                keys.push_back(a.second);
+                heavy += a.second != 0;
+                t_large_substarts += a.second != 0;
+            }
+        }
+    }
     const size_t np = starts.size();
     const bool many = heavy > 12u * (size_t)ctx()->cus;
     if (np < 4) return why("fewer than four block starts found");
@@ -538,8 +612,9 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
         slot_off[i + 1] = slot_off[i] + capi;
     }
     uint8_t *sp = nullptr;
-    const size_t jobs_b = (np * sizeof(InflateJobDev) + 255) & ~(size_t)255, starts_b = (np * 8 + 255) & ~(size_t)255,
-                 res_b = (np * 32 + (blocks ? np * 16 : 0) + 255) & ~(size_t)255, slots_b = slot_off[np] * 2;
+    // (SUBBLOCK: the keys follow the start bits, and 8 words per part follow the results)
+    const size_t jobs_b = (np * sizeof(InflateJobDev) + 255) & ~(size_t)255, starts_b = (np * (sub ? 16 : 8) + 255) & ~(size_t)255,
+                 res_b = (np * 32 + (blocks ? np * 16 : 0) + (sub ? np * 32 : 0) + 255) & ~(size_t)255, slots_b = slot_off[np] * 2;
     if (scratch_reserve(ws, kScrLargeParts, jobs_b + starts_b + res_b + slots_b, false, (void **)&sp) != ZNG_ROCM_OK)
         return why("no room for the part slots");
     InflateJobDev *d_jobs = (InflateJobDev *)sp;
@@ -553,14 +628,17 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
     unsigned long long *h_starts = (unsigned long long *)(hq + jobs_b);
     uint32_t *res = (uint32_t *)(hq + jobs_b + starts_b);
     uint32_t *d_marks = blocks ? d_res + 8 * np : nullptr, *marks = res + 8 * np;    // blocks mode: 4 words per part behind the results
+    uint32_t *d_side = sub ? d_res + 8 * np : nullptr, *side = res + 8 * np;        // SUBBLOCK: 8 words per part behind the results
+    const size_t res_words = blocks ? 12 : sub ? 16 : 8;
     std::copy(starts.begin(), starts.end(), h_starts);
+    if (sub) std::copy(keys.begin(), keys.end(), h_starts + np);
     for (size_t i = 0; i < np; ++i)
         jobs[i] = InflateJobDev{d_src, (uint8_t *)(d_slots + slot_off[i]), src_len, slot_off[i + 1] - slot_off[i],
                                 i == 0 ? window_len : 32768u, 0u};
     ZR_HIP(hipMemcpyAsync(d_jobs, jobs, np * sizeof(InflateJobDev), hipMemcpyHostToDevice, st));
-    ZR_HIP(hipMemcpyAsync(d_starts, h_starts, np * 8, hipMemcpyHostToDevice, st));
-    if (int rc = launch_inflate_parts_device(d_jobs, np, d_res, d_starts, many, st, d_marks)) return rc;
-    ZR_HIP(hipMemcpyAsync(res, d_res, np * (blocks ? 48 : 32), hipMemcpyDeviceToHost, st));
+    ZR_HIP(hipMemcpyAsync(d_starts, h_starts, np * (sub ? 16 : 8), hipMemcpyHostToDevice, st));
+    if (int rc = launch_inflate_parts_device(d_jobs, np, d_res, d_starts, many, st, d_marks, d_side)) return rc;
+    ZR_HIP(hipMemcpyAsync(res, d_res, np * 4 * res_words, hipMemcpyDeviceToHost, st));
     ZR_HIP(hipStreamSynchronize(st));
     // parts whose slot was too small (more than kSlotRatio : 1): once more, with room for deflate's worst case (1032 : 1)
     uint8_t *bigp = nullptr;
@@ -589,8 +667,8 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
                 at += capi;
             }
             ZR_HIP(hipMemcpyAsync(d_jobs, jobs, np * sizeof(InflateJobDev), hipMemcpyHostToDevice, st));
-            if (int rc = launch_inflate_parts_device(d_jobs, np, d_res, d_starts, many, st, d_marks)) return rc;
-            ZR_HIP(hipMemcpyAsync(res, d_res, np * (blocks ? 48 : 32), hipMemcpyDeviceToHost, st));
+            if (int rc = launch_inflate_parts_device(d_jobs, np, d_res, d_starts, many, st, d_marks, d_side)) return rc;
+            ZR_HIP(hipMemcpyAsync(res, d_res, np * 4 * res_words, hipMemcpyDeviceToHost, st));
             ZR_HIP(hipStreamSynchronize(st));
         }
     }
@@ -605,9 +683,24 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
     size_t cur = 0;
     unsigned long long end_bit = start_bit;
     bool final = false;
+    int fin = -1;                                         // SUBBLOCK: BFINAL of the block the current part began inside
+    size_t subparts = 0;
     for (;;) {
         const uint32_t *r = &res[8 * cur];
         const bool ended = r[3] == 1u;
+        if (sub && keys[cur] == 1u && fin == 1 && side[8 * cur] != 0xffffffffu) {
+            // a fixed-code sub-part inside the FINAL block (its header, read by a part in front, said so): the stream ends
+            // where its first block ended, whatever it decoded behind that
+            const uint32_t *s = &side[8 * cur];
+            end_bit = (unsigned long long)s[1] | ((unsigned long long)s[2] << 32);
+            if (end_bit > 8ull * src_len) return why("the final block runs past the input");
+            if ((uint64_t)s[3] > produced + window_len) return why("a distance reaches in front of the stream");
+            if (s[0]) copies.push_back(PartCopy{slot_ptr[cur], produced, 0, s[0], 0u});
+            produced += s[0];
+            ++subparts;
+            final = true;
+            break;
+        }
         if (blocks && r[4] == kMsgStarved) {            // the input ends in this part: its complete blocks, and no more
             const uint32_t *m = &marks[4 * cur];
             if ((uint64_t)m[3] > produced + window_len) return why("a distance reaches in front of the stream");
@@ -617,9 +710,14 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
             break;
         }
         if (r[4] != kMsgNone || !(ended || r[6] != 0xffffffffu)) {                // error / truncation on the chain
-            set_error("inflate_large: sequential decoder (part %zu of %zu at bit %llu: message %u \"%s\", %u symbols of %llu, "
-                      "ended on %d)", cur, np, starts[cur], r[4], zng_rocm_inflate_message(r[4]), r[0],
-                      (unsigned long long)jobs[cur].out_cap, (int)r[6]);
+            if (!sub)
+                set_error("inflate_large: sequential decoder (part %zu of %zu at bit %llu: message %u \"%s\", %u symbols of %llu, "
+                          "ended on %d)", cur, np, starts[cur], r[4], zng_rocm_inflate_message(r[4]), r[0],
+                          (unsigned long long)jobs[cur].out_cap, (int)r[6]);
+            else                                          // (and where the part began: 0 a block start, 1 fixed, H + 2 dynamic)
+                set_error("inflate_large: sequential decoder (part %zu of %zu at bit %llu, key %llu: message %u \"%s\", %u symbols "
+                          "of %llu, ended on %d)", cur, np, starts[cur], keys[cur], r[4], zng_rocm_inflate_message(r[4]), r[0],
+                          (unsigned long long)jobs[cur].out_cap, (int)r[6]);
             return 0;
         }
         if ((uint64_t)r[5] > produced + window_len) return why("a distance reaches in front of the stream");
@@ -629,6 +727,13 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
         if (ended) {
             final = true;
             break;
+        }
+        if (sub) {
+            subparts += keys[cur] != 0;
+            // handed off inside a block: the next part starts there and learns that block's BFINAL from here (2: this part
+            // did not know it either -- a fixed-code sub-part still in its first block -- so it stays what it was)
+            if (side[8 * cur + 4]) fin = side[8 * cur + 5] == 2u ? fin : (int)side[8 * cur + 5];
+            else fin = -1;
         }
         cur = r[6];
         if (cur >= np) return why("bad chain link");
@@ -666,6 +771,7 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
     if (final_out) *final_out = final ? 1 : 0;
     if (blocks && produced == 0) {                        // no block complete yet: nothing to launch
         t_large_parts = 0;
+        t_large_subparts = 0;
         return 1;
     }
     if (produced > dst_cap) {
@@ -689,10 +795,15 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
     if (int rc = inflate_resolve_symbols(d_segs, nsegs, sym, d_dst, d_window, window_len, st)) return rc;
     ZR_HIP(hipStreamSynchronize(st));
     t_large_parts = (int)nparts;
+    t_large_subparts = (int)subparts;
     return 1;
 }
 
-void inflate_large_forget_parts() { t_large_parts = 0; }
+void inflate_large_forget_parts() {
+    t_large_parts = 0;
+    t_large_subparts = 0;
+    t_large_substarts = 0;
+}
 
 // A large stream that is in HOST memory (zng_rocm_inflate_raw*, and with them uncompress2 and the gzip / zlib one-shots):
 // up over PCIe once and through the device path; 0 = not done here (the caller's sequential decoder takes it).
@@ -721,6 +832,8 @@ int inflate_large_from_host(const uint8_t *src, size_t src_len, const uint8_t *d
 int inflate_large_device_only(const uint8_t *d_src, size_t src_len, const uint8_t *d_window, uint32_t window_len, uint8_t *d_dst,
                               size_t dst_cap, uint64_t *out_len, size_t *in_used, hipStream_t st) {
     t_large_parts = 0;
+    t_large_subparts = 0;
+    t_large_substarts = 0;
     Workspace *ws = workspace_for(st);
     if (!ws) return ZNG_ROCM_ENOMEM;
     std::lock_guard<std::mutex> use(ws->mu);
@@ -734,6 +847,8 @@ int inflate_large_blocks_device_only(const uint8_t *d_src, size_t src_len, unsig
                                      uint32_t window_len, uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, uint64_t *end_bit,
                                      int *final, hipStream_t st) {
     t_large_parts = 0;
+    t_large_subparts = 0;
+    t_large_substarts = 0;
     Workspace *ws = workspace_for(st);
     if (!ws) return ZNG_ROCM_ENOMEM;
     std::lock_guard<std::mutex> use(ws->mu);
@@ -749,6 +864,8 @@ using namespace zr;
 extern "C" {
 
 int zng_rocm_inflate_large_last_parts(void) { return t_large_parts; }
+int zng_rocm_inflate_large_last_subparts(void) { return t_large_subparts; }
+int zng_rocm_inflate_large_last_substarts(void) { return t_large_substarts; }
 #ifdef ZR_INFLATE_STATS
 unsigned zng_rocm_debug_large_parts(unsigned long long *starts, uint32_t *res8, unsigned cap) {
     const unsigned n = (unsigned)std::min<size_t>(cap, g_dbg_starts.size());
@@ -760,8 +877,11 @@ unsigned zng_rocm_debug_large_parts(unsigned long long *starts, uint32_t *res8, 
 }
 #endif
 
-int zng_rocm_inflate_large_dev(const uint8_t *d_src, size_t src_len, const uint8_t *d_window, uint32_t window_len,
-                               uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, size_t *in_used, void *stream) {
+}  // extern "C"
+
+// zng_rocm_inflate_large_dev, and zng_rocm_inflate_large_ex_dev with `sub` = ZNG_ROCM_INFLATE_SUBBLOCK
+static int inflate_large_call(const uint8_t *d_src, size_t src_len, const uint8_t *d_window, uint32_t window_len,
+                              uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, size_t *in_used, void *stream, bool sub) {
     if (!ctx()) {
         set_error("zng_rocm_init() has not succeeded");
         return ZNG_ROCM_ENODEV;
@@ -770,11 +890,14 @@ int zng_rocm_inflate_large_dev(const uint8_t *d_src, size_t src_len, const uint8
     DeviceGuard dev;
     hipStream_t st = (hipStream_t)stream;
     t_large_parts = 0;
+    t_large_subparts = 0;
+    t_large_substarts = 0;
     {
         Workspace *ws = workspace_for(st);               // scratch is keyed by the caller's HIP stream (context.h)
         if (!ws) return ZNG_ROCM_ENOMEM;
         std::lock_guard<std::mutex> use(ws->mu);
-        const int rc = inflate_large_try(ws, d_src, src_len, d_window, window_len, d_dst, dst_cap, out_len, in_used, st);
+        const int rc = inflate_large_try(ws, d_src, src_len, d_window, window_len, d_dst, dst_cap, out_len, in_used, st, false, 0,
+                                         nullptr, nullptr, sub);
         if (rc != 0) return rc;
     }
     // irregular: the sequential decoder on a host copy of the stream says exactly what the reference would
@@ -784,6 +907,24 @@ int zng_rocm_inflate_large_dev(const uint8_t *d_src, size_t src_len, const uint8
         ZR_HIP(hipStreamSynchronize(st));
     }
     return inflate_raw_window_sequential(host.data(), src_len, d_window, window_len, d_dst, dst_cap, out_len, in_used, st);
+}
+
+extern "C" {
+
+int zng_rocm_inflate_large_dev(const uint8_t *d_src, size_t src_len, const uint8_t *d_window, uint32_t window_len,
+                               uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, size_t *in_used, void *stream) {
+    return inflate_large_call(d_src, src_len, d_window, window_len, d_dst, dst_cap, out_len, in_used, stream, false);
+}
+
+int zng_rocm_inflate_large_ex_dev(const uint8_t *d_src, size_t src_len, const uint8_t *d_window, uint32_t window_len,
+                                  uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, size_t *in_used, uint32_t flags, void *stream) {
+    if (flags & ~ZNG_ROCM_INFLATE_SUBBLOCK) {
+        if (out_len) *out_len = 0;
+        if (in_used) *in_used = 0;
+        set_error("zng_rocm_inflate_large_ex_dev: unknown flag bits 0x%x", flags & ~ZNG_ROCM_INFLATE_SUBBLOCK);
+        return ZNG_ROCM_EINVAL;
+    }
+    return inflate_large_call(d_src, src_len, d_window, window_len, d_dst, dst_cap, out_len, in_used, stream, flags != 0);
 }
 
 }  // extern "C"

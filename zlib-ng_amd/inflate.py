@@ -258,16 +258,34 @@ class InflateDevBatch:
         return [(row[2], row[0], row[1], inflate_message(row[3])) for row in r]
 
 
-def inflate_large_dev(src_dev, dst, window=None, stream=None):
+SUBBLOCK = 1                                              # ZNG_ROCM_INFLATE_SUBBLOCK
+
+
+def inflate_large_dev(src_dev, dst, window=None, stream=None, subblock=False):
     """zng_rocm_inflate_large_dev: ONE large raw stream that is already in device memory (`src_dev`: uint8 CUDA tensor),
     cut into parts and decoded on the device; plaintext into the CUDA tensor `dst`, optional history `window` (CUDA tensor,
     <= 32768 bytes).  Returns (zlib status, bytes produced, compressed bytes used, parts on the chain -- 0 when the
-    sequential decoder did it)."""
+    sequential decoder did it).  subblock=True: zng_rocm_inflate_large_ex_dev with ZNG_ROCM_INFLATE_SUBBLOCK -- parts may
+    also begin inside a block (inflate_large_last_subparts() says how many did)."""
     rocm._need_init()
     lib = rocm.lib()
     out_len, in_used = C.c_uint64(0), C.c_size_t(0)
     wl = 0 if window is None else int(window.numel())
-    st = lib.zng_rocm_inflate_large_dev(rocm._dev_ptr(src_dev), int(src_dev.numel()),
-                                        rocm._dev_ptr(window) if wl else None, wl, rocm._dev_ptr(dst), int(dst.numel()),
-                                        C.byref(out_len), C.byref(in_used), rocm._stream_ptr(stream))
+    args = (rocm._dev_ptr(src_dev), int(src_dev.numel()), rocm._dev_ptr(window) if wl else None, wl, rocm._dev_ptr(dst),
+            int(dst.numel()), C.byref(out_len), C.byref(in_used))
+    if subblock:
+        st = lib.zng_rocm_inflate_large_ex_dev(*args, SUBBLOCK, rocm._stream_ptr(stream))
+    else:
+        st = lib.zng_rocm_inflate_large_dev(*args, rocm._stream_ptr(stream))
     return st, int(out_len.value), int(in_used.value), int(lib.zng_rocm_inflate_large_last_parts())
+
+
+def inflate_large_last_subparts():
+    """zng_rocm_inflate_large_last_subparts: of the parts on the calling thread's last chain, how many began inside a
+    block (0 when none did or the sequential decoder did the work)."""
+    return int(rocm.lib().zng_rocm_inflate_large_last_subparts())
+
+
+def inflate_large_last_substarts():
+    """zng_rocm_inflate_large_last_substarts: sub-starts the calling thread's last SUBBLOCK call placed"""
+    return int(rocm.lib().zng_rocm_inflate_large_last_substarts())
