@@ -61,6 +61,8 @@ int         zng_rocm_shutdown(void);
  * releases that state first with this call (it synchronises the stream).  The host-pointer slots use one stream
  * per host thread and release it themselves when the thread ends. */
 int         zng_rocm_stream_release(void *stream);
+/* device bytes the per-stream state of `stream` holds now (its scratch and staging buffers; 0 when it has none) */
+size_t      zng_rocm_workspace_bytes(void *stream);
 /* The checksum kernels run one workgroup per CU for the whole pass.  A caller that overlaps them with work on
  * other HIP streams of the same device (an RCCL collective, the combine of the previous step) asks for `n` CUs
  * to be left out of that grid, so the other stream's kernels do not have to displace a workgroup the whole pass
@@ -420,6 +422,32 @@ int  zng_rocm_inflate_large_last_subparts(void);
  * ZNG_ROCM_INFLATE_SUBBLOCK call placed, whether or not the sequential decoder did the work in the end; with
  * zng_rocm_inflate_large_last_subparts() it gives the share that a genuine decode landed on */
 int  zng_rocm_inflate_large_last_substarts(void);
+/* zng_rocm_inflate_large_ex_dev piece by piece: the same arguments, flags (0 or ZNG_ROCM_INFLATE_SUBBLOCK) and results,
+ * for a stream of any length (src_len and the output may pass 4 GiB), with device scratch that does not grow with it.
+ * The stream is decoded in device passes over pieces of at most `piece_bytes` compressed bytes (0 = 64 MiB; otherwise
+ * 4 MiB .. 1 GiB).  A pass that does not reach the stream's end delivers the parts in front of the first one that ran out of
+ * the piece's input, and the next piece begins exactly where that part began (a block start, or with
+ * ZNG_ROCM_INFLATE_SUBBLOCK a start inside a block that the part in front landed on).  Each pass has the 32 KiB in front
+ * of its output as history (the caller's window spliced with d_dst while fewer bytes were produced).  A piece the device
+ * cannot do -- no start behind its own is landed on, a data error, a truncated end -- goes to the sequential decoder
+ * from the last block start delivered: complete blocks, behind which the device goes on; a data error or the end of the
+ * input is decoded there once more in the stream form.  So for every stream zng_rocm_inflate_large_ex_dev accepts with a
+ * dst_cap that holds the output, the return value, *out_len, *in_used, the bytes at d_dst[0, *out_len) and the
+ * zng_rocm_last_error() text of a data error are the same.
+ * dst_cap too small: -5, nothing written at or beyond d_dst + dst_cap; *out_len is the output decoded until then, more than
+ * dst_cap but possibly less than the whole stream's (which zng_rocm_inflate_large_ex_dev reports), *in_used where it ended.
+ * Scratch: the device bytes the call adds to the workspace of `stream` (zng_rocm_workspace_bytes) are at most
+ * 256 x piece_bytes + 640 MiB, whatever src_len is; a pass over scratch caps is run again on half the piece, down to 4 MiB.
+ * Unknown flag bits or a piece_bytes outside 4 MiB .. 1 GiB return ZNG_ROCM_EINVAL with nothing launched or written and
+ * *out_len = *in_used = 0.  The part counters (last_parts / _subparts / _substarts) are sums over the pieces.
+ * Synchronous. */
+int  zng_rocm_inflate_large_pieces_dev(const uint8_t *d_src, size_t src_len, const uint8_t *d_window, uint32_t window_len,
+                                       uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, size_t *in_used, size_t piece_bytes,
+                                       uint32_t flags, void *stream);
+/* device passes of the calling thread's last zng_rocm_inflate_large_pieces_dev call */
+int  zng_rocm_inflate_large_last_pieces(void);
+/* compressed bytes of the calling thread's last zng_rocm_inflate_large_pieces_dev call that the sequential decoder took */
+uint64_t zng_rocm_inflate_large_last_host_bytes(void);
 
 /* Many independent raw streams at once: `nthreads` host threads (<= 0: as many as the host gives us) take the jobs in
  * order, each decoding on the host and resolving on the device on its own HIP stream, so that the sequential decode

@@ -78,6 +78,7 @@ enum ScratchSlot {
     kScrLargePartsHost,     // pinned: jobs | starts | results of the parts
     kScrLargeSub,           // device: regions | guesses' symbol boundaries | their keys (ZNG_ROCM_INFLATE_SUBBLOCK)
     kScrLargeSubHost,       // pinned: the same
+    kScrLargeHist,          // device: the 32 KiB history of a piece, spliced from the caller's window and the output
     kScrCount
 };
 

@@ -269,6 +269,22 @@ int zng_rocm_trace_stride(int n) {
     return ZNG_ROCM_OK;
 }
 
+size_t zng_rocm_workspace_bytes(void *stream) {
+    if (!ctx()) return 0;
+    Workspace *ws = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(g_mu);
+        auto it = g_ws.find((hipStream_t)stream);
+        if (it == g_ws.end()) return 0;
+        ws = it->second;
+    }
+    std::lock_guard<std::mutex> use(ws->mu);
+    size_t n = ws->stage_bytes;
+    for (const Scratch &sc : ws->scratch)
+        if (sc.p && !sc.host) n += sc.cap;
+    return n;
+}
+
 int zng_rocm_stream_release(void *stream) {
     Context *c = ctx();
     if (!c) return ZNG_ROCM_OK;

@@ -754,6 +754,16 @@ int zr_inflate_decode_reuse(const uint8_t *src, size_t src_len, uint32_t window_
     return decode_stream(src, src_len, window_len, t, re, caps);
 }
 
+// (inflate_large.hip: a piece the device cannot do, after the blocks form met a data error or the end of the input)
+int zr_inflate_decode_from(const uint8_t *src, size_t src_len, uint64_t start_bit, uint32_t window_len, zng_rocm_inflate_tokens *t) {
+    memset(t, 0, sizeof(*t));
+    if ((!src && src_len) || window_len > 32768u || start_bit > 8ull * src_len) return ZNG_ROCM_EINVAL;
+    ZrDecodeCtl ctl;
+    memset(&ctl, 0, sizeof ctl);
+    ctl.start_bit = start_bit;
+    return decode_stream(src, src_len, window_len, t, plain_realloc, nullptr, &ctl);
+}
+
 extern "C" {
 
 int zng_rocm_inflate_tokens_decode(const uint8_t *src, size_t src_len, zng_rocm_inflate_tokens *out) {

@@ -33,6 +33,7 @@
 #include "context.h"
 #include "deflate_dev.h"
 #include "inflate_dev.h"
+#include "inflate_threads.h"
 
 namespace zr {
 
@@ -436,6 +437,8 @@ int inflate_resolve_symbols(const uint64_t *d_segs, size_t nsegs, uint16_t *sym,
 static thread_local int t_large_parts = 0;
 static thread_local int t_large_subparts = 0;           // of them, parts that began inside a block
 static thread_local int t_large_substarts = 0;          // SUBBLOCK: sub-starts placed (the sync kernel's boundaries, deduplicated)
+static thread_local int t_large_pieces = 0;             // pieces: device passes of the last call
+static thread_local uint64_t t_large_host_bytes = 0;    // pieces: compressed bytes the sequential decoder took
 #ifdef ZR_INFLATE_STATS
 static std::vector<unsigned long long> g_dbg_starts;     // diagnostic builds: the last call's part starts and result words
 static std::vector<uint32_t> g_dbg_res;
@@ -447,6 +450,29 @@ static int why(const char *reason) {
     return 0;
 }
 
+// One device pass of zng_rocm_inflate_large_pieces_dev over a piece of the stream.  The pass's buffer (d_src, src_len of
+// inflate_large_try) begins at or in front of the piece -- at the header of the dynamic block a sub-start lies in, when it
+// does -- and ends at the piece's end; the finder scans from `scan_lo` on.  Scratch is checked against caps that depend on
+// the piece size alone (`q` = the largest piece, in compressed bytes); a pass that would need more asks to be run again
+// with half the piece.
+struct PiecePass {
+    uint64_t scan_lo = 0;         // byte of the buffer where the piece (and the finder's scan) begins
+    uint64_t key0 = 0;            // key of the first start: 0 a block start, 1 inside a fixed-code block, H + 2 (buffer bits)
+    int      fin0 = -1;           // BFINAL of the fixed-code block a key-1 first start lies in (-1 unknown)
+    bool     last = false;        // the piece reaches the end of the stream: stream mode (truncation, in_used, errors)
+    uint64_t q = 0;
+    // out
+    bool     stopped = false;     // the chain stopped at a part that ran out of the piece: the next piece starts there
+    uint64_t next_bit = 0, next_key = 0;
+    int      next_fin = -1;
+    bool     halve = false;       // the scratch caps were exceeded
+};
+// caps of one pass in bytes, q = piece bytes (the device scratch of a pieces call is their sum: DESIGN 3.10, zng_rocm.h)
+constexpr uint32_t kPieceMaxParts = 65535;                      // also the compaction grid's y limit
+inline uint64_t piece_cap_sub(uint64_t q) { return q / 8 + (1u << 20); }
+inline uint64_t piece_cap_retry(uint64_t q) { return 32 * q; }
+inline uint64_t piece_cap_sym(uint64_t q) { return 48 * q; }
+
 // returns 1 with *out_len / *in_used set, or 0 = "irregular: use the sequential decoder", or a negative error.
 // Blocks mode (`blocks`, the streaming hook): the stream starts at bit `start_bit` of d_src, and input that ends inside a
 // block is no irregularity -- the chain stops at the first part that ran out of input, that part's complete blocks (its
@@ -456,11 +482,15 @@ static int why(const char *reason) {
 static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len, const uint8_t *d_window, uint32_t window_len,
                              uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, size_t *in_used, hipStream_t st,
                              bool blocks = false, uint64_t start_bit = 0, uint64_t *end_bit_out = nullptr, int *final_out = nullptr,
-                             bool sub = false) {
+                             bool sub = false, PiecePass *pp = nullptr) {
     if (src_len < (128u << 10) || src_len >= (1ull << 31)) return why("stream below 128 KiB (or 2 GiB and more)");
+    const bool piece = pp && !pp->last;                   // the input ends at the piece's end, not the stream's
     // ---- candidates ---------------------------------------------------------------------------------------------
-    const uint32_t cap1 = (uint32_t)std::min<size_t>(src_len / 64 + 4096, 64u << 20);
-    const uint32_t cap2 = (uint32_t)std::min<size_t>(src_len / 512 + 4096, 8u << 20);      // starts are >= 2 KiB apart in the end
+    // (pieces: the finder scans the piece alone, from scan_lo; its bit positions are moved to the buffer's by `lo_bits`)
+    const size_t scan_lo = pp ? (size_t)pp->scan_lo : 0, scan_len = src_len - scan_lo;
+    const unsigned long long lo_bits = 8ull * scan_lo;
+    const uint32_t cap1 = (uint32_t)std::min<size_t>(scan_len / 64 + 4096, 64u << 20);
+    const uint32_t cap2 = (uint32_t)std::min<size_t>(scan_len / 512 + 4096, 8u << 20);      // starts are >= 2 KiB apart in the end
     uint8_t *fp = nullptr;
     if (int rc = scratch_reserve(ws, kScrLargeCand, ((size_t)cap1 + cap2) * 8 + 64, false, (void **)&fp)) return rc;
     unsigned long long *d_cand = (unsigned long long *)fp, *d_good = d_cand + cap1;
@@ -478,7 +508,8 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
     unsigned long long *h_good = (unsigned long long *)(hp + 64);
     n12[0] = n12[1] = 0;
     ZR_HIP(hipMemsetAsync(d_n, 0, 8, st));
-    hipLaunchKernelGGL(find_headers_kernel<true>, dim3(4096), dim3(256), 0, st, d_src, (unsigned long long)src_len, d_good, d_n + 1, cap2);
+    hipLaunchKernelGGL(find_headers_kernel<true>, dim3(4096), dim3(256), 0, st, d_src + scan_lo, (unsigned long long)scan_len, d_good,
+                       d_n + 1, cap2);
     ZR_HIP(hipGetLastError());
     ZR_HIP(hipMemcpyAsync(n12, d_n, 8, hipMemcpyDeviceToHost, st));
     ZR_HIP(hipMemcpyAsync(h_good, d_good, (size_t)first * 8, hipMemcpyDeviceToHost, st));
@@ -488,7 +519,7 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
     bool patterns_do = n12[1] >= 64u && n12[1] <= first;
     if (patterns_do) {
         good.assign(h_good, h_good + n12[1]);
-        for (unsigned long long &b : good) b &= ~(1ull << 63);
+        for (unsigned long long &b : good) b = (b & ~(1ull << 63)) + lo_bits;
         std::sort(good.begin(), good.end(), [](unsigned long long x, unsigned long long y) { return (x & ~(1ull << 62)) < (y & ~(1ull << 62)); });
         unsigned long long prev = start_bit;
         for (unsigned long long b62 : good) {
@@ -500,10 +531,11 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
     }
     if (!patterns_do) {
         ZR_HIP(hipMemsetAsync(d_n, 0, 8, st));
-        hipLaunchKernelGGL(find_headers_kernel<false>, dim3(4096), dim3(256), 0, st, d_src, (unsigned long long)src_len, d_cand, d_n, cap1);
+        hipLaunchKernelGGL(find_headers_kernel<false>, dim3(4096), dim3(256), 0, st, d_src + scan_lo, (unsigned long long)scan_len,
+                           d_cand, d_n, cap1);
         ZR_HIP(hipGetLastError());
-        hipLaunchKernelGGL(validate_headers_kernel, dim3(8192), dim3(kValLanes), 0, st, d_src, (unsigned long long)src_len, d_cand,
-                           d_n, cap1, d_good, d_n + 1, cap2);
+        hipLaunchKernelGGL(validate_headers_kernel, dim3(8192), dim3(kValLanes), 0, st, d_src + scan_lo, (unsigned long long)scan_len,
+                           d_cand, d_n, cap1, d_good, d_n + 1, cap2);
         ZR_HIP(hipGetLastError());
         // the counts and (what is almost always all of) the list in one round trip (SUBBLOCK: and the first block's header)
         ZR_HIP(hipMemcpyAsync(n12, d_n, 8, hipMemcpyDeviceToHost, st));
@@ -522,7 +554,7 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
         ZR_HIP(hipStreamSynchronize(st));
     }
     if (!patterns_do) {                                              // (the patterns' list has been sorted above)
-        for (unsigned long long &b : good) b &= ~(1ull << 63);
+        for (unsigned long long &b : good) b = (b & ~(1ull << 63)) + lo_bits;
         std::sort(good.begin(), good.end(), [](unsigned long long x, unsigned long long y) { return (x & ~(1ull << 62)) < (y & ~(1ull << 62)); });
     }
     std::vector<unsigned long long> starts;
@@ -548,28 +580,47 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
     // 10^6 of fixed-code data passes F1 + F2 and one byte in 2^23 looks like a stored block's header, and the gap behind
     // such a noise start would otherwise be one long part.
     std::vector<unsigned long long> keys;                 // per start: 0 a block start, 1 inside a fixed-code block, H + 2 inside the dynamic block at H
+    // (pieces: the first start may lie inside a block itself -- a key-1 one gets fixed-code guesses, a key-(H + 2) one the
+    // tables of the header at H, with the guesses placed behind it)
+    const unsigned long long key0 = pp ? pp->key0 : 0ull;
     if (sub) {
         keys.assign(starts.size(), 0ull);
+        keys[0] = key0;
         const unsigned long long total = 8ull * src_len - start_bit;
         const unsigned long long step = std::max<unsigned long long>(kSubMinStep, total / (kSubPerSlot * 12ull * (unsigned long long)ctx()->cus));
         std::vector<SubRegionDev> regions;
         uint32_t nguess = 0;                              // guess slots: two per guess
         const uint8_t *b0 = hp + 8;                        // (copied with the finder's counts when F1 + F2 ran)
-        const bool fixed_first = !patterns_do && ((((unsigned)b0[0] | ((unsigned)b0[1] << 8)) >> ((start_bit & 7u) + 1u)) & 3u) == 1u;
+        const bool fixed_first = !patterns_do && (key0 == 1u || (key0 == 0u &&
+                                 ((((unsigned)b0[0] | ((unsigned)b0[1] << 8)) >> ((start_bit & 7u) + 1u)) & 3u) == 1u));
         const uint32_t split_dynamic = heavy <= 12u * (size_t)ctx()->cus ? 1u : 0u;
         for (size_t i = 0; i < starts.size() && !patterns_do && (split_dynamic || fixed_first); ++i) {
             const unsigned long long s0 = starts[i], e0 = i + 1 < starts.size() ? starts[i + 1] : 8ull * src_len;
             const unsigned long long pieces = (e0 - s0 + step / 2) / step;
             if (pieces < 2) continue;
+            unsigned long long rs = s0;
+            const unsigned long long spacing = (e0 - s0) / pieces;
+            uint32_t j0 = 0, dyn = split_dynamic, ft = fixed_first ? 1u : 0u;
+            if (i == 0 && key0 == 1u) {                   // (what the sync kernel reads at s0 is no header: fixed guesses)
+                dyn = 0u;
+                ft = 1u;
+            } else if (i == 0 && key0 >= 2u) {            // the region reads the header at H; its guesses begin behind s0
+                rs = key0 - 2u;
+                j0 = (uint32_t)((s0 - rs) / spacing);
+            }
             // one work item (wavefront) per 64 guesses: a long gap is not one wavefront's serial work
             for (uint32_t k0 = 0; k0 < (uint32_t)(pieces - 1); k0 += 64u) {
                 const uint32_t n = std::min<uint32_t>(64u, (uint32_t)(pieces - 1) - k0);
-                regions.push_back(SubRegionDev{s0, (e0 - s0) / pieces, nguess, n, split_dynamic, fixed_first ? 1u : 0u, k0});
+                regions.push_back(SubRegionDev{rs, spacing, nguess, n, dyn, ft, j0 + k0});
                 nguess += 2u * n;
             }
         }
         if (nguess) {
             const size_t reg_b = (regions.size() * sizeof(SubRegionDev) + 255) & ~(size_t)255, out_b = (size_t)nguess * 16;
+            if (pp && reg_b + out_b > piece_cap_sub(pp->q)) {
+                pp->halve = true;
+                return why("the piece's sub-starts need more scratch than its cap");
+            }
             uint8_t *dp = nullptr, *hp2 = nullptr;
             if (int rc = scratch_reserve(ws, kScrLargeSub, reg_b + out_b, false, (void **)&dp)) return rc;
             if (int rc = scratch_reserve(ws, kScrLargeSubHost, reg_b + out_b, true, (void **)&hp2)) return rc;
@@ -581,7 +632,7 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
             ZR_HIP(hipStreamSynchronize(st));
             std::vector<std::pair<unsigned long long, unsigned long long>> all;
             all.reserve(starts.size() + nguess);
-            for (unsigned long long b : starts) all.emplace_back(b, 0ull);
+            for (size_t i = 0; i < starts.size(); ++i) all.emplace_back(starts[i], keys[i]);       // (keys[0]: a piece's key0)
             for (uint32_t g = 0; g < nguess; ++g) {
                 const unsigned long long b = h_bit[g];
                 if (b != ~0ull && b > start_bit && (b >> 3) + 16 < src_len) all.emplace_back(b, h_bit[nguess + g]);
@@ -601,10 +652,16 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
     const size_t np = starts.size();
     const bool many = heavy > 12u * (size_t)ctx()->cus;
     if (np < 4) return why("fewer than four block starts found");
+    if (pp && np > kPieceMaxParts) {
+        pp->halve = true;
+        return why("more parts in the piece than one launch takes");
+    }
 
     // ---- parts ----------------------------------------------------------------------------------------------------
+    // (pieces: the parts' slack together stays within 8 symbols per compressed byte of the largest piece, 4 Ki at least)
     std::vector<uint64_t> slot_off(np + 1, 0);
-    const uint64_t slack = std::max<uint64_t>(64u << 10, std::min<uint64_t>(kSlotSlack, (2ull << 30) / np));
+    const uint64_t slack = pp ? std::max<uint64_t>(4u << 10, std::min<uint64_t>(kSlotSlack, 8 * pp->q / np))
+                              : std::max<uint64_t>(64u << 10, std::min<uint64_t>(kSlotSlack, (2ull << 30) / np));
     for (size_t i = 0; i < np; ++i) {
         const uint64_t bytes = ((i + 1 < np ? starts[i + 1] : 8ull * src_len) - starts[i] + 7) >> 3;
         uint64_t capi = bytes * kSlotRatio + slack;
@@ -654,6 +711,10 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
                 need += (bytes * 1032u + kSlotSlack + 7) & ~7ull;
             }
         if (!again.empty()) {
+            if (pp && need * 2 > piece_cap_retry(pp->q)) {
+                pp->halve = true;
+                return why("the piece's parts above a ratio of 64 need more scratch than its cap");
+            }
             if (need * 2 > (24ull << 30) || scratch_reserve(ws, kScrLargeRetry, need * 2, false, (void **)&bigp) != ZNG_ROCM_OK)
                 return why("parts with a ratio above 64 need more scratch than is reasonable");
             for (size_t i = 0; i < np; ++i) jobs[i].out_cap = 0;
@@ -683,12 +744,15 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
     size_t cur = 0;
     unsigned long long end_bit = start_bit;
     bool final = false;
-    int fin = -1;                                         // SUBBLOCK: BFINAL of the block the current part began inside
+    int fin = pp ? pp->fin0 : -1;                         // SUBBLOCK: BFINAL of the block the current part began inside
     size_t subparts = 0;
     for (;;) {
         const uint32_t *r = &res[8 * cur];
         const bool ended = r[3] == 1u;
-        if (sub && keys[cur] == 1u && fin == 1 && side[8 * cur] != 0xffffffffu) {
+        // (pieces: an end behind the piece's input is no end yet -- the next piece decodes that part again)
+        const bool past = piece && sub && side[8 * cur] != 0xffffffffu &&
+                          ((unsigned long long)side[8 * cur + 1] | ((unsigned long long)side[8 * cur + 2] << 32)) > 8ull * src_len;
+        if (sub && keys[cur] == 1u && fin == 1 && side[8 * cur] != 0xffffffffu && !past) {
             // a fixed-code sub-part inside the FINAL block (its header, read by a part in front, said so): the stream ends
             // where its first block ended, whatever it decoded behind that
             const uint32_t *s = &side[8 * cur];
@@ -700,6 +764,25 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
             ++subparts;
             final = true;
             break;
+        }
+        if (pp) {
+            // pieces: the first part on the chain that ran out of the piece's input is where the next piece begins; so is a
+            // part whose symbols would take the symbol array past its cap (in the last piece too)
+            const bool full = r[4] == kMsgNone && ((produced + r[0] + 32768 + 64) * 2 + 64 * (copies.size() + 1) + 512 >
+                                                   piece_cap_sym(pp->q));
+            if ((piece && r[4] == kMsgStarved) || full || (past && keys[cur] == 1u && fin == 1)) {
+                if (cur == 0) {
+                    pp->halve = full;
+                    return why(full ? "the piece's first part needs more scratch than its cap"
+                                    : "no start behind the piece's first is landed on");
+                }
+                pp->stopped = true;
+                pp->next_bit = starts[cur];
+                pp->next_key = sub ? keys[cur] : 0ull;
+                pp->next_fin = fin;
+                end_bit = starts[cur];
+                break;
+            }
         }
         if (blocks && r[4] == kMsgStarved) {            // the input ends in this part: its complete blocks, and no more
             const uint32_t *m = &marks[4 * cur];
@@ -769,7 +852,7 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
     if (in_used) *in_used = (size_t)((end_bit + 7) >> 3);
     if (end_bit_out) *end_bit_out = end_bit;
     if (final_out) *final_out = final ? 1 : 0;
-    if (blocks && produced == 0) {                        // no block complete yet: nothing to launch
+    if ((blocks || (pp && pp->stopped)) && produced == 0) {       // no block complete yet (pieces: no symbol): nothing to launch
         t_large_parts = 0;
         t_large_subparts = 0;
         return 1;
@@ -866,6 +949,8 @@ extern "C" {
 int zng_rocm_inflate_large_last_parts(void) { return t_large_parts; }
 int zng_rocm_inflate_large_last_subparts(void) { return t_large_subparts; }
 int zng_rocm_inflate_large_last_substarts(void) { return t_large_substarts; }
+int zng_rocm_inflate_large_last_pieces(void) { return t_large_pieces; }
+uint64_t zng_rocm_inflate_large_last_host_bytes(void) { return t_large_host_bytes; }
 #ifdef ZR_INFLATE_STATS
 unsigned zng_rocm_debug_large_parts(unsigned long long *starts, uint32_t *res8, unsigned cap) {
     const unsigned n = (unsigned)std::min<size_t>(cap, g_dbg_starts.size());
@@ -909,7 +994,226 @@ static int inflate_large_call(const uint8_t *d_src, size_t src_len, const uint8_
     return inflate_raw_window_sequential(host.data(), src_len, d_window, window_len, d_dst, dst_cap, out_len, in_used, st);
 }
 
+// ---- pieces: zng_rocm_inflate_large_pieces_dev --------------------------------------------------------------------------
+// The stream is decoded in passes over pieces of at most `piece_bytes` compressed bytes.  A pass that does not reach the
+// stream's end takes the piece's end as the end of the input: the chain stops at the first part that ran out of it, the
+// parts in front are delivered, and the next piece begins exactly at that part's start (a start the part in front landed
+// on), with its key and the BFINAL the chain carried to it.  Each pass gets the 32 KiB in front of its output as history.
+// A piece the device cannot do (no start behind its own is landed on, a data error on the chain, a truncated end) goes to
+// the sequential decoder from the last block start delivered: complete blocks first, and the loop goes on behind them; a
+// data error or the end of the input there is decoded once more in the stream form, whose status, message and counts
+// are then the reference's.
+constexpr size_t kPieceMin = 4u << 20;                  // the least piece (the hook's device threshold, hook.hip)
+constexpr size_t kPieceDefault = 64u << 20;
+constexpr size_t kPieceMax = 1u << 30;                  // the largest (a pass's buffer stays below inflate_large_try's 2 GiB)
+
+static int inflate_pieces_call(const uint8_t *d_src, size_t src_len, const uint8_t *d_window, uint32_t window_len,
+                               uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, size_t *in_used, size_t piece_bytes, bool sub,
+                               hipStream_t st) {
+    Workspace *ws = workspace_for(st);                   // scratch is keyed by the caller's HIP stream (context.h)
+    if (!ws) return ZNG_ROCM_ENOMEM;
+    std::unique_lock<std::mutex> use(ws->mu);            // (let go while the sequential decoder works on the host)
+    uint8_t *d_hist = nullptr;
+    if (int rc = scratch_reserve(ws, kScrLargeHist, 32768 + 64, false, (void **)&d_hist)) return rc;
+    // the last min(32768, pos + window_len) bytes in front of output position `pos`: in d_dst, or spliced from the caller's
+    // window and d_dst while pos < 32768
+    auto history = [&](uint64_t pos, const uint8_t **h, uint32_t *hl) -> int {
+        const uint64_t n = std::min<uint64_t>(32768u, pos + window_len);
+        *hl = (uint32_t)n;
+        *h = pos >= n ? d_dst + (pos - n) : d_window;
+        if (pos >= n || pos == 0) return ZNG_ROCM_OK;
+        if (int rc = scratch_reserve(ws, kScrLargeHist, 32768 + 64, false, (void **)&d_hist)) return rc;   // (under the lock)
+        const uint64_t from_window = n - pos;
+        ZR_HIP(hipMemcpyAsync(d_hist, d_window + (window_len - from_window), from_window, hipMemcpyDeviceToDevice, st));
+        ZR_HIP(hipMemcpyAsync(d_hist + from_window, d_dst, pos, hipMemcpyDeviceToDevice, st));
+        *h = d_hist;
+        return ZNG_ROCM_OK;
+    };
+    uint64_t bit = 0, key = 0, produced = 0;              // where the next piece begins, its key; bytes delivered
+    uint64_t abit = 0, aout = 0;                          // the last block start delivered up to (the sequential decoder's start)
+    int fin = -1;
+    size_t p = piece_bytes;
+    int parts = 0, subparts = 0, passes = 0;
+    uint64_t host_bytes = 0;
+    auto done = [&](int rc) {
+        t_large_parts = parts;
+        t_large_subparts = subparts;
+        t_large_pieces = passes;
+        t_large_host_bytes = host_bytes;
+        return rc;
+    };
+    for (;;) {
+        const uint64_t sbyte = bit >> 3;
+        if (sbyte < src_len) {
+            // the piece [sbyte, end); one that would leave less than a quarter piece behind it ends a quarter piece early
+            uint64_t end = sbyte + p;
+            if (end >= src_len) end = src_len;
+            else if (src_len - end < p / 4) end = src_len - p / 4;
+            // the pass's buffer begins at the piece, or at the header of the dynamic block its first start lies in
+            const uint64_t base = (key >= 2 ? std::min<uint64_t>(sbyte, (key - 2) >> 3) : sbyte) & ~(uint64_t)255;
+            PiecePass pp;
+            pp.scan_lo = sbyte - base;
+            pp.key0 = key >= 2 ? key - 8 * base : key;
+            pp.fin0 = fin;
+            pp.last = end == src_len;
+            pp.q = piece_bytes;
+            const uint8_t *h = nullptr;
+            uint32_t hl = 0;
+            if (int rc = history(produced, &h, &hl)) return done(rc);
+            const int substarts0 = t_large_substarts;
+            uint64_t n = 0;
+            size_t used = 0;
+            const int rc = inflate_large_try(ws, d_src + base, (size_t)(end - base), h, hl, d_dst + produced,
+                                             dst_cap > produced ? dst_cap - produced : 0, &n, &used, st, false, bit - 8 * base,
+                                             nullptr, nullptr, sub, &pp);
+            if (rc == 1) {
+                ++passes;
+                parts += t_large_parts;
+                subparts += t_large_subparts;
+                produced += n;
+                if (!pp.stopped) {                        // the stream ended in this piece
+                    *out_len = produced;
+                    *in_used = (size_t)(base + used);
+                    return done(1);
+                }
+                bit = pp.next_bit + 8 * base;
+                key = pp.next_key >= 2 ? pp.next_key + 8 * base : pp.next_key;
+                fin = pp.next_fin;
+                if (key == 0) {
+                    abit = bit;
+                    aout = produced;
+                }
+                p = piece_bytes;
+                continue;
+            }
+            if (rc == -5) {                               // the piece's output does not fit behind what is there
+                *out_len = produced + n;
+                *in_used = (size_t)(base + used);
+                set_error("inflate output (%llu bytes) exceeds dst_cap", (unsigned long long)(produced + n));
+                return done(-5);
+            }
+            if (rc < 0) return done(rc);
+            if (pp.halve && p / 2 >= kPieceMin) {         // over a scratch cap: the same start with half the piece
+                p /= 2;
+                t_large_substarts = substarts0;
+                continue;
+            }
+        }
+        // the sequential decoder from the last block start delivered, with the history in front of it; complete blocks of at
+        // least two pieces of input, more while none completes.  The workspace is not used while it decodes: the lock is let
+        // go, and taken again to splice the history (d_hist) and upload what was decoded.
+        const uint64_t a0 = abit >> 3, sb = abit & 7u;
+        const uint8_t *h = nullptr;
+        uint32_t hl = (uint32_t)std::min<uint64_t>(32768u, aout + window_len);
+        use.unlock();
+        std::vector<uint8_t> host;
+        uint64_t span = std::max<uint64_t>(2ull * p, sbyte - a0 + p), len = 0, eb = sb;
+        zng_rocm_inflate_tokens tk;
+        int status = 0;
+        for (;;) {
+            len = std::min<uint64_t>(src_len - a0, span);
+            host.resize(len ? (size_t)len : 1);
+            if (len) {
+                ZR_HIP(hipMemcpyAsync(host.data(), d_src + a0, (size_t)len, hipMemcpyDeviceToHost, st));
+                ZR_HIP(hipStreamSynchronize(st));
+            }
+            status = zng_rocm_inflate_tokens_decode_blocks(host.data(), (size_t)len, sb, hl, &tk, &eb);
+            if (status == 0 && eb == sb && len < src_len - a0) {
+                zng_rocm_inflate_tokens_free(&tk);
+                span *= 2;
+                continue;
+            }
+            break;
+        }
+        // a data error, or the end of the input inside a block: the stream form from the same bit (still without the lock)
+        const bool stream_form = status != 1 && !(status == 0 && eb != sb) && status != -4;
+        if (stream_form) {
+            zng_rocm_inflate_tokens_free(&tk);
+            status = zr_inflate_decode_from(host.data(), (size_t)len, sb, hl, &tk);
+        }
+        use.lock();
+        // (sb <= 7 < 8 * len unless len = 0 and sb = 0: the decoder's ZNG_ROCM_EINVAL, which has the value of Z_DATA_ERROR,
+        // cannot come back)
+        if (status == -4) {
+            zng_rocm_inflate_tokens_free(&tk);
+            return done(ZNG_ROCM_ENOMEM);
+        }
+        if (!stream_form) {                              // complete blocks: delivered, and the device goes on behind them
+            const uint64_t total = aout + tk.out_len;
+            host_bytes += (eb + 7) >> 3;
+            if (total > dst_cap) {
+                *out_len = total;
+                *in_used = (size_t)(a0 + ((eb + 7) >> 3));
+                set_error("inflate output (%llu bytes) exceeds dst_cap", (unsigned long long)total);
+                zng_rocm_inflate_tokens_free(&tk);
+                return done(-5);
+            }
+            int rc = history(aout, &h, &hl);
+            if (rc == ZNG_ROCM_OK) rc = inflate_tokens_to_device(&tk, h, hl, d_dst + aout, st);
+            const size_t tk_used = tk.in_used;
+            zng_rocm_inflate_tokens_free(&tk);
+            if (rc != ZNG_ROCM_OK) return done(rc);
+            produced = total;
+            if (status == 1) {
+                *out_len = produced;
+                *in_used = (size_t)(a0 + tk_used);
+                return done(1);
+            }
+            bit = 8 * a0 + eb;
+            key = 0;
+            fin = -1;
+            abit = bit;
+            aout = produced;
+            p = piece_bytes;
+            continue;
+        }
+        // the stream form (decoded above): its status, message and counts are the one-shot's
+        const uint64_t total = aout + tk.out_len;
+        *out_len = total;
+        *in_used = (size_t)(a0 + tk.in_used);
+        host_bytes += tk.in_used;
+        if (total > dst_cap) {
+            set_error("inflate output (%llu bytes) exceeds dst_cap", (unsigned long long)total);
+            zng_rocm_inflate_tokens_free(&tk);
+            return done(-5);
+        }
+        if (status < 0) set_error("%s", tk.msg);
+        int rc = history(aout, &h, &hl);
+        if (rc == ZNG_ROCM_OK) rc = inflate_tokens_to_device(&tk, h, hl, d_dst + aout, st);
+        zng_rocm_inflate_tokens_free(&tk);
+        return done(rc != ZNG_ROCM_OK ? rc : status);
+    }
+}
+
 extern "C" {
+
+int zng_rocm_inflate_large_pieces_dev(const uint8_t *d_src, size_t src_len, const uint8_t *d_window, uint32_t window_len,
+                                      uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, size_t *in_used, size_t piece_bytes,
+                                      uint32_t flags, void *stream) {
+    t_large_parts = 0;
+    t_large_subparts = 0;
+    t_large_substarts = 0;
+    t_large_pieces = 0;
+    t_large_host_bytes = 0;
+    if (out_len) *out_len = 0;
+    if (in_used) *in_used = 0;
+    if (!ctx()) {
+        set_error("zng_rocm_init() has not succeeded");
+        return ZNG_ROCM_ENODEV;
+    }
+    if (flags & ~ZNG_ROCM_INFLATE_SUBBLOCK) {
+        set_error("zng_rocm_inflate_large_pieces_dev: unknown flag bits 0x%x", flags & ~ZNG_ROCM_INFLATE_SUBBLOCK);
+        return ZNG_ROCM_EINVAL;
+    }
+    if (piece_bytes && (piece_bytes < kPieceMin || piece_bytes > kPieceMax)) {
+        set_error("zng_rocm_inflate_large_pieces_dev: piece_bytes %zu outside %zu .. %zu", piece_bytes, kPieceMin, kPieceMax);
+        return ZNG_ROCM_EINVAL;
+    }
+    if ((!d_src && src_len) || window_len > 32768u || (window_len && !d_window) || !out_len || !in_used) return ZNG_ROCM_EINVAL;
+    DeviceGuard dev;
+    return inflate_pieces_call(d_src, src_len, d_window, window_len, d_dst, dst_cap, out_len, in_used,
+                               piece_bytes ? piece_bytes : kPieceDefault, flags != 0, (hipStream_t)stream);
+}
 
 int zng_rocm_inflate_large_dev(const uint8_t *d_src, size_t src_len, const uint8_t *d_window, uint32_t window_len,
                                uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, size_t *in_used, void *stream) {

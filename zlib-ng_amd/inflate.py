@@ -280,6 +280,28 @@ def inflate_large_dev(src_dev, dst, window=None, stream=None, subblock=False):
     return st, int(out_len.value), int(in_used.value), int(lib.zng_rocm_inflate_large_last_parts())
 
 
+def inflate_large_pieces_dev(src_dev, dst, piece_bytes=0, window=None, stream=None, subblock=False, flags=None):
+    """zng_rocm_inflate_large_pieces_dev: inflate_large_dev for a stream of any length, decoded on the device in pieces of at
+    most `piece_bytes` compressed bytes (0 = the library's default) with scratch that does not grow with the stream.
+    Returns (zlib status, bytes produced, compressed bytes used, parts on the chains, device passes, compressed bytes the
+    sequential decoder took).  `flags` overrides subblock (raw flag word)."""
+    rocm._need_init()
+    lib = rocm.lib()
+    out_len, in_used = C.c_uint64(0), C.c_size_t(0)
+    wl = 0 if window is None else int(window.numel())
+    fl = (SUBBLOCK if subblock else 0) if flags is None else int(flags)
+    st = lib.zng_rocm_inflate_large_pieces_dev(rocm._dev_ptr(src_dev), int(src_dev.numel()), rocm._dev_ptr(window) if wl else None,
+                                               wl, rocm._dev_ptr(dst), int(dst.numel()), C.byref(out_len), C.byref(in_used),
+                                               int(piece_bytes), fl, rocm._stream_ptr(stream))
+    return (st, int(out_len.value), int(in_used.value), int(lib.zng_rocm_inflate_large_last_parts()),
+            int(lib.zng_rocm_inflate_large_last_pieces()), int(lib.zng_rocm_inflate_large_last_host_bytes()))
+
+
+def workspace_bytes(stream=None):
+    """zng_rocm_workspace_bytes: device bytes the library's per-stream state of `stream` holds now"""
+    return int(rocm.lib().zng_rocm_workspace_bytes(rocm._stream_ptr(stream)))
+
+
 def inflate_large_last_subparts():
     """zng_rocm_inflate_large_last_subparts: of the parts on the calling thread's last chain, how many began inside a
     block (0 when none did or the sequential decoder did the work)."""
