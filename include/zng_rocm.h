@@ -449,6 +449,45 @@ int  zng_rocm_inflate_large_last_pieces(void);
 /* compressed bytes of the calling thread's last zng_rocm_inflate_large_pieces_dev call that the sequential decoder took */
 uint64_t zng_rocm_inflate_large_last_host_bytes(void);
 
+/* MANY large raw streams that are already in device memory, in one set of launches: what zng_rocm_inflate_large_ex_dev
+ * does for one stream -- finder, parts, chain, compaction, resolve -- runs once per ROUND over the parts of all the round's
+ * streams, so that the long parts of one stream run under the short parts of the others and the host round trips between
+ * the kernels are paid per round, not per stream (a shard set of a few to a few hundred streams of 1 .. 64 MiB each).
+ * Per job, on return: `status` as the return value of zng_rocm_inflate_large_ex_dev for this job alone (1 = Z_STREAM_END,
+ * -3 with the reference's text in `msg`, -5 input ended early or dst_cap too small -- then nothing is written at or behind
+ * d_dst + dst_cap --, negative ZNG_ROCM_E*), `out_len` / `in_used` as there, and on status 1 the same bytes at
+ * d_dst[0, out_len).  `parts` = parts of this job on its chain (0: the sequential decoder did it), `subparts` = of them,
+ * parts that began inside a block.  A job the device path cannot do (below 128 KiB or from 2 GiB on, fewer than four starts,
+ * anything irregular on its chain) leaves its round and is decoded as zng_rocm_inflate_large_ex_dev decodes it (host copy,
+ * sequential decoder) behind the round's device work; the round's other jobs do not notice.
+ * Rounds: jobs are taken in order until their compressed bytes would pass `round_bytes` (0 = 256 MiB; otherwise 4 MiB up
+ * to, not including, 2 GiB) or their parts 65535; a job larger than round_bytes is a round of its own.  Rounds run one
+ * after the other; device scratch (zng_rocm_workspace_bytes of `stream`) is sized by the largest round: 128 bytes of part
+ * slots per compressed byte plus slack, 2 bytes of symbols per output byte plus 64 KiB per stream.  Per round the call
+ * synchronises a fixed number of times, whatever the number of streams in it.
+ * flags: 0 or ZNG_ROCM_INFLATE_SUBBLOCK, as for zng_rocm_inflate_large_ex_dev (the guess step is derived from the round's
+ * bits).  Unknown flag bits, a window_len above 32768, a null buffer with a non-zero length or a round_bytes outside the
+ * range return ZNG_ROCM_EINVAL with nothing launched and nothing written to any job's output fields or d_dst.
+ * Synchronous.  Returns 0 or the first device error; a stream's own trouble is its job's status alone. */
+typedef struct zng_rocm_inflate_large_job {
+    const uint8_t *d_src;     size_t   src_len;      /* device: raw deflate stream */
+    const uint8_t *d_window;  uint32_t window_len;   /* device: <= 32768 bytes of history, or NULL / 0 */
+    uint8_t       *d_dst;     size_t   dst_cap;      /* device: plaintext */
+    /* out */
+    int            status;
+    uint64_t       out_len;
+    size_t         in_used;
+    const char    *msg;       /* reference's strm->msg text on a data error, else NULL (static storage) */
+    uint32_t       parts;
+    uint32_t       subparts;
+} zng_rocm_inflate_large_job;
+int  zng_rocm_inflate_large_streams_dev(zng_rocm_inflate_large_job *jobs, size_t njobs, size_t round_bytes, uint32_t flags,
+                                        void *stream);
+/* rounds of the calling thread's last zng_rocm_inflate_large_streams_dev call (thread-local, like the other last_* counters) */
+int  zng_rocm_inflate_large_last_rounds(void);
+/* part-kernel launches of that call, reruns of overflowed parts included: at most two per round */
+int  zng_rocm_inflate_large_last_part_launches(void);
+
 /* Many independent raw streams at once: `nthreads` host threads (<= 0: as many as the host gives us) take the jobs in
  * order, each decoding on the host and resolving on the device on its own HIP stream, so that the sequential decode
  * -- where an inflate spends its time -- runs on all the cores the caller allows while the device work of one stream

@@ -26,6 +26,8 @@ enum InflateMsg : uint32_t {
 int launch_inflate_streams_device(const InflateJobDev *d_jobs, size_t njobs, uint32_t *d_results, hipStream_t stream);
 
 // the parts of ONE large stream, 16-bit symbols out (inflate_large.hip); results: 8 words per part; d_marks (or null):
+// (or of several streams, each stream's starts together and in order: then every job carries in `flags` the index one past
+// its own stream's last start -- 0 means njobs -- and a part ends only on a start in front of that)
 // 4 words per part, where its last block inside the input ended
 // d_side (or null): starts inside blocks -- d_starts then holds njobs keys behind the njobs bits (0 a block start, 1 inside a
 // fixed-code block, H + 2 inside the dynamic block at H), and d_side takes 8 words per part (inflate_streams_kernel<..., SUB>)
@@ -40,6 +42,9 @@ int launch_inflate_parts_device(const InflateJobDev *d_jobs, size_t njobs, uint3
 struct SubRegionDev {
     unsigned long long start, spacing;
     uint32_t           first, n, dynamic, fixed_too, k0;
+    uint32_t           pad = 0;
+    const uint8_t     *src = nullptr;      // a batch of streams in one launch: the region's own stream (null: the launch's)
+    unsigned long long src_len = 0;
 };
 int launch_subblock_sync(const uint8_t *d_src, size_t src_len, const SubRegionDev *d_regions, size_t nregions,
                          unsigned long long *d_bit, unsigned long long *d_key, hipStream_t stream);

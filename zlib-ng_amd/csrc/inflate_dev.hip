@@ -728,6 +728,9 @@ void inflate_streams_kernel(const InflateJobDev *__restrict__ jobs, uint32_t njo
     // SUB: the part's own key; the identity of the block being decoded (1 fixed, H + 2 dynamic) and the next sub-start of
     // that identity ahead (its bit, its index; ~0 = none); handed off; a fixed-code sub-part still in its first block
     const unsigned long long *const keys = starts + njobs;
+    // one past the last start of this part's own stream: njobs, or (a batch of streams in one launch, their starts one
+    // stream behind the other) what the job carries in `flags` -- a block end or a sub-start is looked for in front of it only
+    const uint32_t jend = PART && J.flags ? J.flags : njobs;
     uint32_t *const side = marks;
     unsigned long long entry = 0, cur_id = 0, nextB = ~0ull;
     uint32_t pidx = 0;
@@ -832,13 +835,13 @@ void inflate_streams_kernel(const InflateJobDev *__restrict__ jobs, uint32_t njo
     // PART: does the block that just ended end exactly on a later start?  (binary search, wave-uniform)
     auto block_end_stop = [&]() __attribute__((always_inline)) -> bool {
         const unsigned long long b = bit_pos();
-        uint32_t lo = job + 1u, hi = njobs;
+        uint32_t lo = job + 1u, hi = jend;
         while (lo < hi) {
             const uint32_t mid = (lo + hi) >> 1;
             if (starts[mid] < b) lo = mid + 1u;
             else hi = mid;
         }
-        if (lo < njobs && starts[lo] == b && (!SUB || keys[lo] == 0)) {     // (a block start sorts first among equal bits)
+        if (lo < jend && starts[lo] == b && (!SUB || keys[lo] == 0)) {     // (a block start sorts first among equal bits)
             hit = lo;
             return true;
         }
@@ -848,7 +851,7 @@ void inflate_streams_kernel(const InflateJobDev *__restrict__ jobs, uint32_t njo
     // one identity are consecutive but for a noise candidate now and then; one that is missed only makes a part longer)
     auto next_sub = [&](uint32_t i, unsigned long long b) __attribute__((always_inline)) {
         nextB = ~0ull;
-        for (uint32_t k = 0; k < 32u && i < njobs; ++k, ++i) {
+        for (uint32_t k = 0; k < 32u && i < jend; ++k, ++i) {
             const unsigned long long sbit = starts[i];
             if (sbit >= b && keys[i] == cur_id) {
                 nextB = sbit;
@@ -1023,7 +1026,7 @@ void inflate_streams_kernel(const InflateJobDev *__restrict__ jobs, uint32_t njo
             }
             // the first later start of this block's identity (binary search for the bit, then a short look)
             const unsigned long long b = bit_pos();
-            uint32_t lo = job + 1u, hi = njobs;
+            uint32_t lo = job + 1u, hi = jend;
             while (lo < hi) {
                 const uint32_t mid = (lo + hi) >> 1;
                 if (starts[mid] < b) lo = mid + 1u;
@@ -1396,7 +1399,7 @@ __device__ __forceinline__ uint32_t lane_long_code(LDS &L, int which, int root, 
 }
 
 __global__ __launch_bounds__(64)
-void subblock_sync_kernel(const uint8_t *__restrict__ src, unsigned long long src_len, const SubRegionDev *__restrict__ regions,
+void subblock_sync_kernel(const uint8_t *__restrict__ src0, unsigned long long src_len0, const SubRegionDev *__restrict__ regions,
                           uint32_t nregions, unsigned long long *__restrict__ out_bit, unsigned long long *__restrict__ out_key) {
     constexpr int kLR = kLitRootStream, kDR = kDistRootStream;
     __shared__ InflateLdsStream<16, uint8_t, kDR, kLR> L;
@@ -1404,6 +1407,9 @@ void subblock_sync_kernel(const uint8_t *__restrict__ src, unsigned long long sr
     const uint32_t r = blockIdx.x;
     if (r >= nregions) return;
     const SubRegionDev R = regions[r];
+    // (a batch of streams: the region names its own; bit positions and keys are that stream's)
+    const uint8_t *const src = R.src ? R.src : src0;
+    const unsigned long long src_len = R.src ? R.src_len : src_len0;
     unsigned long long s0 = R.start;
     uint32_t type = (uint32_t)(sync_bits_at(src, src_len, s0) >> 1) & 3u;
     if (type == 0u) {

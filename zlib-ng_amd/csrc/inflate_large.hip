@@ -26,7 +26,11 @@
 //        K2 / K3 of inflate_resolve.hip resolve and translate.
 // Anything irregular on the chain -- a data error, a truncated stream, a distance too far back, no candidates (a stream of fixed-Huffman blocks only) -- sends the call to the sequential host decoder, which
 // then reports exactly what the reference would (status, message, bytes produced, bytes consumed).
+// A BATCH of such streams (zng_rocm_inflate_large_streams_dev, at the end of this file) runs the same steps once per round
+// over the parts of all its streams: the finder over a table of (stream, range) items, one part launch, one compaction,
+// one resolve.
 #include <algorithm>
+#include <cstring>
 #include <mutex>
 #include <vector>
 
@@ -78,11 +82,17 @@ __device__ __forceinline__ unsigned long long bits_at_dev(const uint8_t *src, un
 // PATTERNS = true: the two byte patterns only (no bit position is tested): the first pass -- a stream whose encoder left a
 // sync marker or a stored block every few tens of KiB (this library's level-6 class, pigz) offers enough starts that way.
 constexpr uint32_t kFindLocal = 2048;
+// The scan itself, bytes [lo_b, hi_b) of one stream: find_headers_kernel gives every workgroup an equal share of ONE stream,
+// find_headers_table_kernel a (stream, range) pair of a table; `tag` (0, or the stream's index << kFindTagShift) is set in
+// every survivor.
+constexpr unsigned kFindTagShift = 40;                   // a bit position takes 34 bits, the marks bits 62 and 63
+constexpr unsigned long long kFindTagMask = 0x3fffffull << kFindTagShift;
 template <bool PATTERNS>
-__global__ __launch_bounds__(256)
-void find_headers_kernel(const uint8_t *__restrict__ src, unsigned long long src_len, unsigned long long *__restrict__ cand,
-                         uint32_t *__restrict__ ncand, uint32_t cap) {
-    __shared__ uint8_t kraft9[512];             // three 3-bit code lengths -> their share of the Kraft sum, in 1/128
+__device__ __forceinline__ void find_headers_range(const uint8_t *__restrict__ src, const unsigned long long src_len,
+                                                   const unsigned long long lo_b, const unsigned long long hi_b,
+                                                   const unsigned long long tag, unsigned long long *__restrict__ cand,
+                                                   uint32_t *__restrict__ ncand, uint32_t cap) {
+    __shared__ uint8_t kraft9[512];            // three 3-bit code lengths -> their share of the Kraft sum, in 1/128
     __shared__ unsigned long long local[kFindLocal];
     __shared__ uint32_t nlocal, gbase;
     for (int v = threadIdx.x; v < 512 && !PATTERNS; v += 256) {
@@ -106,8 +116,6 @@ void find_headers_kernel(const uint8_t *__restrict__ src, unsigned long long src
         if (threadIdx.x == 0) nlocal = 0;
         __syncthreads();
     };
-    const unsigned long long per = (src_len + gridDim.x - 1) / gridDim.x;
-    const unsigned long long lo_b = per * blockIdx.x, hi_b = lo_b + per < src_len ? lo_b + per : src_len;
     if constexpr (PATTERNS) {
         // the two byte patterns alone: a lane takes 16 byte positions from one 24-byte window (position by position, with a
         // 16-byte load each, the pass read every byte 16 times and ran at 0.44 TB/s: 0.22 ms for 96 MB)
@@ -115,12 +123,12 @@ void find_headers_kernel(const uint8_t *__restrict__ src, unsigned long long src
             if (b >= hi_b || b + 8 >= src_len) return;
             if ((uint32_t)w == 0xffff0000u && b + 6 <= src_len) {
                 const uint32_t i = atomicAdd(&nlocal, 1u);
-                if (i < kFindLocal) local[i] = (8ull * (b + 4)) | (1ull << 63);
+                if (i < kFindLocal) local[i] = (8ull * (b + 4)) | (1ull << 63) | tag;
             }
             const uint32_t len16 = (uint32_t)(w >> 8) & 0xffffu, nlen16 = (uint32_t)(w >> 24) & 0xffffu;
             if (((uint32_t)w & 0xfeu) == 0u && len16 != 0u && (len16 ^ nlen16) == 0xffffu && b + 5 + len16 <= src_len) {
                 const uint32_t i = atomicAdd(&nlocal, 1u);
-                if (i < kFindLocal) local[i] = (8ull * b) | (3ull << 62);
+                if (i < kFindLocal) local[i] = (8ull * b) | (3ull << 62) | tag;
             }
         };
         for (unsigned long long base = lo_b; base < hi_b; base += 4096) {
@@ -175,7 +183,7 @@ void find_headers_kernel(const uint8_t *__restrict__ src, unsigned long long src
             }
             if ((uint32_t)lo == 0xffff0000u && b + 6 <= src_len) {       // 00 00 ff ff: the block behind the marker
                 const uint32_t i = atomicAdd(&nlocal, 1u);
-                if (i < kFindLocal) local[i] = (8ull * (b + 4)) | (1ull << 63);
+                if (i < kFindLocal) local[i] = (8ull * (b + 4)) | (1ull << 63) | tag;
             }
             // a stored block that starts on a byte boundary (as every stored block behind another one does: a run of
             // incompressible data is a chain of them, and without these starts it would be ONE part -- 8 MiB of the cfg3 mix
@@ -185,7 +193,7 @@ void find_headers_kernel(const uint8_t *__restrict__ src, unsigned long long src
                 const uint32_t len16 = (uint32_t)(lo >> 8) & 0xffffu, nlen16 = (uint32_t)(lo >> 24) & 0xffffu;
                 if (((uint32_t)lo & 0xfeu) == 0u && len16 != 0u && (len16 ^ nlen16) == 0xffffu && b + 5 + len16 <= src_len) {
                     const uint32_t i = atomicAdd(&nlocal, 1u);
-                    if (i < kFindLocal) local[i] = (8ull * b) | (3ull << 62);          // bit 62: a stored block (light work)
+                    if (i < kFindLocal) local[i] = (8ull * b) | (3ull << 62) | tag;          // bit 62: a stored block (light work)
                 }
             }
             if constexpr (!PATTERNS) {
@@ -208,7 +216,7 @@ void find_headers_kernel(const uint8_t *__restrict__ src, unsigned long long src
                     for (int g = 0; g < 7; ++g) sum += kraft9[(uint32_t)(c >> (9 * g)) & 511u];
                     if (sum != 128u) continue;
                     const uint32_t i = atomicAdd(&nlocal, 1u);
-                    if (i < kFindLocal) local[i] = 8ull * b + k;
+                    if (i < kFindLocal) local[i] = (8ull * b + k) | tag;
                 }
             }
         }
@@ -221,6 +229,36 @@ void find_headers_kernel(const uint8_t *__restrict__ src, unsigned long long src
     flush();
 }
 
+template <bool PATTERNS>
+__global__ __launch_bounds__(256)
+void find_headers_kernel(const uint8_t *__restrict__ src, unsigned long long src_len, unsigned long long *__restrict__ cand,
+                         uint32_t *__restrict__ ncand, uint32_t cap) {
+    const unsigned long long per = (src_len + gridDim.x - 1) / gridDim.x;
+    const unsigned long long lo_b = per * blockIdx.x, hi_b = lo_b + per < src_len ? lo_b + per : src_len;
+    find_headers_range<PATTERNS>(src, src_len, lo_b, hi_b, 0ull, cand, ncand, cap);
+}
+
+// F1 over the streams of a batch (zng_rocm_inflate_large_streams_dev): grid.x = work item, a range of one stream; the
+// survivors of all streams go to ONE list, each tagged with its stream's index in the table (still one global atomic per
+// workgroup and flush)
+struct FindStreamDev {
+    const uint8_t     *src;
+    unsigned long long src_len;
+};
+struct FindItemDev {
+    unsigned long long lo, hi;    // bytes of the stream
+    uint32_t           stream, pad;
+};
+template <bool PATTERNS>
+__global__ __launch_bounds__(256)
+void find_headers_table_kernel(const FindStreamDev *__restrict__ streams, const FindItemDev *__restrict__ items,
+                               unsigned long long *__restrict__ cand, uint32_t *__restrict__ ncand, uint32_t cap) {
+    const FindItemDev it = items[blockIdx.x];
+    const FindStreamDev s = streams[it.stream];
+    find_headers_range<PATTERNS>(s.src, s.src_len, it.lo, it.hi < s.src_len ? it.hi : s.src_len,
+                                 (unsigned long long)it.stream << kFindTagShift, cand, ncand, cap);
+}
+
 // F2.  One lane per survivor of F1: the whole dynamic header (inflate.c:814-917) and inflate_table's validity rules for the
 // literal/length and the distance code (inftrees.c:104-137).  Those rules are statements about Kraft sums, so the code
 // lengths are summed as they are decoded and never stored: a set is over-subscribed when its sum passes 1 (the lane
@@ -229,8 +267,9 @@ void find_headers_kernel(const uint8_t *__restrict__ src, unsigned long long src
 // Per lane in LDS: the code-length code as a 128-entry direct table (length << 5 | symbol).  Survivors are appended to
 // good[] (bit positions; the marker bit removed).
 constexpr int kValLanes = 64;
-__device__ void validate_one(const uint8_t *__restrict__ src, unsigned long long src_len, const unsigned long long c0, uint8_t *T,
-                             unsigned long long *__restrict__ good, uint32_t *__restrict__ ngood, uint32_t cap);
+__device__ __forceinline__ void validate_one(const uint8_t *__restrict__ src, unsigned long long src_len, const unsigned long long c0, uint8_t *T,
+                             unsigned long long *__restrict__ good, uint32_t *__restrict__ ngood, uint32_t cap,
+                             const unsigned long long tag = 0ull);
 __global__ __launch_bounds__(kValLanes)
 void validate_headers_kernel(const uint8_t *__restrict__ src, unsigned long long src_len,
                              const unsigned long long *__restrict__ cand, const uint32_t *__restrict__ ncand, uint32_t cand_cap,
@@ -242,12 +281,34 @@ void validate_headers_kernel(const uint8_t *__restrict__ src, unsigned long long
     for (uint32_t i = blockIdx.x * kValLanes + threadIdx.x; i < n; i += gridDim.x * kValLanes)
         validate_one(src, src_len, cand[i], tab[threadIdx.x], good, ngood, cap);
 }
+// F2 over the tagged list of find_headers_table_kernel: a survivor's stream is looked up by its tag, which it keeps
+__global__ __launch_bounds__(kValLanes)
+void validate_headers_table_kernel(const FindStreamDev *__restrict__ streams, const unsigned long long *__restrict__ cand,
+                                   const uint32_t *__restrict__ ncand, uint32_t cand_cap, unsigned long long *__restrict__ good,
+                                   uint32_t *__restrict__ ngood, uint32_t cap) {
+    __shared__ uint8_t tab[kValLanes][128];
+    const uint32_t n = *ncand < cand_cap ? *ncand : cand_cap;
+    for (uint32_t i = blockIdx.x * kValLanes + threadIdx.x; i < n; i += gridDim.x * kValLanes) {
+        const unsigned long long c = cand[i];
+        const FindStreamDev s = streams[(c & kFindTagMask) >> kFindTagShift];
+        validate_one(s.src, s.src_len, c & ~kFindTagMask, tab[threadIdx.x], good, ngood, cap, c & kFindTagMask);
+    }
+}
+// the first two bytes of every stream of the table (SUBBLOCK wants the first block's type), one lane each
+__global__ __launch_bounds__(256)
+void first_bytes_kernel(const FindStreamDev *__restrict__ streams, uint32_t n, uint16_t *__restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const FindStreamDev s = streams[i];
+    out[i] = (uint16_t)((s.src_len > 0 ? (unsigned)load_u8(s.src) : 0u) | (s.src_len > 1 ? (unsigned)load_u8(s.src + 1) << 8 : 0u));
+}
 
-__device__ void validate_one(const uint8_t *__restrict__ src, unsigned long long src_len, const unsigned long long c0, uint8_t *T,
-                             unsigned long long *__restrict__ good, uint32_t *__restrict__ ngood, uint32_t cap) {
+__device__ __forceinline__ void validate_one(const uint8_t *__restrict__ src, unsigned long long src_len, const unsigned long long c0, uint8_t *T,
+                             unsigned long long *__restrict__ good, uint32_t *__restrict__ ngood, uint32_t cap,
+                             const unsigned long long tag) {
     auto accept = [&]() {
         const uint32_t at = atomicAdd(ngood, 1u);
-        if (at < cap) good[at] = c0 & ~(1ull << 63);      // (bit 62, "a stored block", stays)
+        if (at < cap) good[at] = (c0 & ~(1ull << 63)) | tag;      // (bit 62, "a stored block", stays; a batch: the stream's tag)
     };
     if (c0 >> 63) {                                       // behind a marker: taken as it is
         accept();
@@ -1229,6 +1290,626 @@ int zng_rocm_inflate_large_ex_dev(const uint8_t *d_src, size_t src_len, const ui
         return ZNG_ROCM_EINVAL;
     }
     return inflate_large_call(d_src, src_len, d_window, window_len, d_dst, dst_cap, out_len, in_used, stream, flags != 0);
+}
+
+}  // extern "C"
+
+// ---- many large streams: zng_rocm_inflate_large_streams_dev ---------------------------------------------------------------
+// The device path of inflate_large_try (stream mode; no pieces, no blocks) for a ROUND of streams at once: ONE finder pass
+// over a table of (stream, range) items whose survivors carry their stream, ONE part launch over the parts of all streams
+// (each stream's starts together; a part looks for its end among its own stream's only: InflateJobDev::flags), one chain per
+// stream on the host, ONE compaction and ONE resolve over a symbol array that holds the streams one behind the other, each
+// behind its own 32768-symbol window gap (the layout of inflate_resolve_batch).  So the long parts of one stream run under
+// the short parts of the others, and the host round trips between the kernels are paid per round.  A stream the device
+// path cannot do leaves the round and is decoded as zng_rocm_inflate_large_ex_dev does it (a host copy, the sequential
+// decoder) behind the round's device work; the others do not notice.
+namespace zr {
+int inflate_resolve_symbols_batch(const uint64_t *d_segs, size_t nsegs, uint16_t *sym, const uint64_t *d_seg_dst,
+                                  const uint64_t *d_seg_end, const void *d_streams, size_t nstreams, hipStream_t st);
+int inflate_raw_window_sequential_msg(const uint8_t *src, size_t src_len, const uint8_t *d_window, uint32_t window_len,
+                                      uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, size_t *in_used, const char **msg,
+                                      hipStream_t st);
+}  // namespace zr
+
+constexpr size_t kRoundMin = 4u << 20;
+constexpr size_t kRoundDefault = 256u << 20;
+static thread_local int t_batch_rounds = 0;
+static thread_local int t_batch_part_launches = 0;
+
+namespace {
+
+struct RoundStream {
+    size_t job = 0;                                       // index in the caller's array
+    bool dev = true;                                      // still on the device path
+    bool patterns_do = false;
+    uint16_t b0 = 0;                                      // the stream's first two bytes (SUBBLOCK, when F1 + F2 ran)
+    std::vector<unsigned long long> good, starts, keys;
+    size_t heavy = 1;
+    uint32_t pbase = 0;                                   // its first part in the round's tables
+    std::vector<PartCopy> copies;
+    std::vector<size_t> seg_first;
+    uint64_t produced = 0;
+    unsigned long long end_bit = 0;
+    size_t subparts = 0;
+    bool placed = false;                                  // has symbols in the round's array
+};
+
+struct BatchWindowDev {                                   // BatchStream of inflate_resolve.hip
+    uint64_t       v_start;
+    const uint8_t *d_window;
+    uint64_t       window_len;
+};
+
+bool by_bit(unsigned long long x, unsigned long long y) { return (x & ~(1ull << 62)) < (y & ~(1ull << 62)); }
+
+}  // namespace
+
+// One finder pass over the streams `which` (indices into rs): the patterns alone, or F1 + F2 (and, `bytes`, every stream's
+// first two bytes).  Fills rs[..].good with each stream's survivors, sorted; a stream whose list cannot be had leaves
+// the device path.  One synchronisation (a second one when the list is longer than what comes back with the counts).
+static int round_find(Workspace *ws, zng_rocm_inflate_large_job *jobs, std::vector<RoundStream> &rs, const std::vector<size_t> &which,
+                      bool patterns, bool bytes, hipStream_t st) {
+    const size_t ns = which.size();
+    if (!ns) return ZNG_ROCM_OK;
+    uint64_t total = 0;
+    for (size_t w : which) total += jobs[rs[w].job].src_len;
+    const uint64_t item_bytes = std::max<uint64_t>(4096, std::min<uint64_t>(65536, (total / 4096 + 4095) & ~4095ull));
+    std::vector<FindItemDev> items;
+    for (size_t k = 0; k < ns; ++k) {
+        const uint64_t len = jobs[rs[which[k]].job].src_len;
+        for (uint64_t lo = 0; lo < len; lo += item_bytes) items.push_back(FindItemDev{lo, std::min(lo + item_bytes, len), (uint32_t)k, 0u});
+    }
+    const uint32_t cap1 = (uint32_t)(total / 64 + 4096 * ns), cap2 = (uint32_t)(total / 512 + 4096 * ns);
+    const uint32_t first = (uint32_t)std::min<size_t>(cap2, 16384 + 64 * ns);
+    const size_t tab_b = (ns * sizeof(FindStreamDev) + 255) & ~(size_t)255, items_b = (items.size() * sizeof(FindItemDev) + 255) & ~(size_t)255,
+                 b0_b = (ns * 2 + 255) & ~(size_t)255;
+    uint8_t *fp = nullptr, *hp = nullptr;
+    auto out = [&](const char *reason) {
+        for (size_t w : which) rs[w].dev = false;
+        return why(reason);
+    };
+    if (scratch_reserve(ws, kScrLargeCand, tab_b + items_b + 64 + b0_b + ((size_t)cap1 + cap2) * 8, false, (void **)&fp) != ZNG_ROCM_OK ||
+        scratch_reserve(ws, kScrLargeCandHost, tab_b + items_b + 64 + b0_b + (size_t)first * 8, true, (void **)&hp) != ZNG_ROCM_OK)
+        return out("no room for the round's candidates");
+    FindStreamDev *d_tab = (FindStreamDev *)fp, *h_tab = (FindStreamDev *)hp;
+    FindItemDev *d_items = (FindItemDev *)(fp + tab_b);
+    uint32_t *d_n = (uint32_t *)(fp + tab_b + items_b), *n12 = (uint32_t *)(hp + tab_b + items_b);
+    uint16_t *d_b0 = (uint16_t *)(fp + tab_b + items_b + 64), *h_b0 = (uint16_t *)(hp + tab_b + items_b + 64);
+    unsigned long long *d_cand = (unsigned long long *)(fp + tab_b + items_b + 64 + b0_b), *d_good = d_cand + cap1;
+    unsigned long long *h_good = (unsigned long long *)(hp + tab_b + items_b + 64 + b0_b);
+    for (size_t k = 0; k < ns; ++k) h_tab[k] = FindStreamDev{jobs[rs[which[k]].job].d_src, jobs[rs[which[k]].job].src_len};
+    std::copy(items.begin(), items.end(), (FindItemDev *)(hp + tab_b));
+    n12[0] = n12[1] = 0;
+    ZR_HIP(hipMemcpyAsync(fp, hp, tab_b + items_b, hipMemcpyHostToDevice, st));
+    ZR_HIP(hipMemsetAsync(d_n, 0, 8, st));
+    if (patterns) {
+        hipLaunchKernelGGL(find_headers_table_kernel<true>, dim3((unsigned)items.size()), dim3(256), 0, st, d_tab, d_items, d_good, d_n + 1, cap2);
+        ZR_HIP(hipGetLastError());
+    } else {
+        hipLaunchKernelGGL(find_headers_table_kernel<false>, dim3((unsigned)items.size()), dim3(256), 0, st, d_tab, d_items, d_cand, d_n, cap1);
+        ZR_HIP(hipGetLastError());
+        hipLaunchKernelGGL(validate_headers_table_kernel, dim3(8192), dim3(kValLanes), 0, st, d_tab, d_cand, d_n, cap1, d_good, d_n + 1, cap2);
+        ZR_HIP(hipGetLastError());
+        if (bytes) {
+            hipLaunchKernelGGL(first_bytes_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, st, d_tab, (uint32_t)ns, d_b0);
+            ZR_HIP(hipGetLastError());
+            ZR_HIP(hipMemcpyAsync(h_b0, d_b0, ns * 2, hipMemcpyDeviceToHost, st));
+        }
+    }
+    ZR_HIP(hipMemcpyAsync(n12, d_n, 8, hipMemcpyDeviceToHost, st));
+    ZR_HIP(hipMemcpyAsync(h_good, d_good, (size_t)first * 8, hipMemcpyDeviceToHost, st));
+    ZR_HIP(hipStreamSynchronize(st));
+    if (n12[0] > cap1 || n12[1] > cap2) return out("far more candidates in the round than deflate streams have");
+    const uint32_t n2 = n12[1];
+    std::vector<unsigned long long> rest;
+    if (n2 > first) {
+        rest.resize(n2 - first);
+        ZR_HIP(hipMemcpyAsync(rest.data(), d_good + first, (size_t)(n2 - first) * 8, hipMemcpyDeviceToHost, st));
+        ZR_HIP(hipStreamSynchronize(st));
+    }
+    for (size_t k = 0; k < ns; ++k) {
+        rs[which[k]].good.clear();
+        if (bytes && !patterns) rs[which[k]].b0 = h_b0[k];
+    }
+    for (uint32_t i = 0; i < n2; ++i) {
+        const unsigned long long c = i < first ? h_good[i] : rest[i - first];
+        const size_t k = (size_t)((c & kFindTagMask) >> kFindTagShift);
+        if (k < ns) rs[which[k]].good.push_back(c & ~kFindTagMask & ~(1ull << 63));
+    }
+    for (size_t w : which) std::sort(rs[w].good.begin(), rs[w].good.end(), by_bit);
+    return ZNG_ROCM_OK;
+}
+
+// One round: the jobs idx[0 .. *taken) (all of idx unless their parts together pass one launch's).  Jobs done on the device
+// have their output fields set; the others are appended to `host` (the caller decodes them sequentially).
+static int round_run(Workspace *ws, zng_rocm_inflate_large_job *jobs, const std::vector<size_t> &idx, bool sub, hipStream_t st,
+                     std::vector<size_t> &host, size_t *taken) {
+    *taken = idx.size();
+    const size_t cus = (size_t)ctx()->cus;
+    std::vector<RoundStream> rs(idx.size());
+    std::vector<size_t> scan;
+    for (size_t k = 0; k < idx.size(); ++k) {
+        rs[k].job = idx[k];
+        const size_t len = jobs[idx[k]].src_len;
+        if (len < (128u << 10) || len >= (1ull << 31)) rs[k].dev = false;      // (as inflate_large_try)
+        else scan.push_back(k);
+    }
+    // ---- candidates: the byte patterns for every stream; F1 + F2 for those they do not cut ---------------------------
+    if (int rc = round_find(ws, jobs, rs, scan, true, false, st)) return rc;
+    std::vector<size_t> full;
+    for (size_t k : scan) {
+        RoundStream &s = rs[k];
+        if (!s.dev) continue;
+        const size_t len = jobs[s.job].src_len;
+        const uint32_t first = (uint32_t)std::min<size_t>(len / 512 + 4096, 16384u);
+        s.patterns_do = s.good.size() >= 64u && s.good.size() <= first;
+        if (s.patterns_do) {
+            unsigned long long prev = 0;
+            for (unsigned long long b62 : s.good) {
+                const unsigned long long b = b62 & ~(1ull << 62);
+                if (b - prev > 8ull * (128u << 10)) s.patterns_do = false;
+                prev = b;
+            }
+            if (8ull * len - prev > 8ull * (128u << 10)) s.patterns_do = false;
+        }
+        if (!s.patterns_do) full.push_back(k);
+    }
+    if (int rc = round_find(ws, jobs, rs, full, false, sub, st)) return rc;
+    uint64_t round_bits = 0;
+    size_t round_heavy = 0;
+    for (size_t k : scan) {
+        RoundStream &s = rs[k];
+        if (!s.dev) continue;
+        const size_t len = jobs[s.job].src_len;
+        if (s.good.size() > len / 512 + 4096) {
+            s.dev = false;
+            why("far more valid block headers than a deflate stream has");
+            continue;
+        }
+        s.starts.push_back(0);
+        const unsigned long long spacing = s.good.size() > kPartsUnthinned ? 8ull * kSpacingBytes : 1ull;
+        for (unsigned long long b62 : s.good) {
+            const unsigned long long b = b62 & ~(1ull << 62);
+            if (b >= s.starts.back() + spacing && (b >> 3) + 16 < len) {
+                s.starts.push_back(b);
+                s.heavy += !(b62 >> 62);
+            }
+        }
+        round_bits += 8ull * len;
+        round_heavy += s.heavy;
+    }
+    // ---- SUBBLOCK: guesses in the gaps, as inflate_large_try places them, with a step that fills the chip once per ROUND
+    // (a stream never gets a coarser step than a sixteenth of itself: a small stream among large ones is still cut) ----
+    if (sub) {
+        const unsigned long long round_step = std::max<unsigned long long>(kSubMinStep, round_bits / (kSubPerSlot * 12ull * cus));
+        const uint32_t split_dynamic = round_heavy <= 12u * cus ? 1u : 0u;
+        std::vector<SubRegionDev> regions;
+        std::vector<std::pair<uint32_t, uint32_t>> span(rs.size(), {0u, 0u});      // a stream's guess slots
+        uint32_t nguess = 0;
+        for (size_t k : scan) {
+            RoundStream &s = rs[k];
+            if (!s.dev) continue;
+            const zng_rocm_inflate_large_job &J = jobs[s.job];
+            s.keys.assign(s.starts.size(), 0ull);
+            span[k].first = nguess;
+            const unsigned long long step = std::max<unsigned long long>(kSubMinStep, std::min<unsigned long long>(round_step, 8ull * J.src_len / 16));
+            const bool fixed_first = !s.patterns_do && ((unsigned)s.b0 >> 1 & 3u) == 1u;
+            for (size_t i = 0; i < s.starts.size() && !s.patterns_do && (split_dynamic || fixed_first); ++i) {
+                const unsigned long long s0 = s.starts[i], e0 = i + 1 < s.starts.size() ? s.starts[i + 1] : 8ull * J.src_len;
+                const unsigned long long pieces = (e0 - s0 + step / 2) / step;
+                if (pieces < 2) continue;
+                const unsigned long long spacing = (e0 - s0) / pieces;
+                for (uint32_t k0 = 0; k0 < (uint32_t)(pieces - 1); k0 += 64u) {
+                    const uint32_t n = std::min<uint32_t>(64u, (uint32_t)(pieces - 1) - k0);
+                    regions.push_back(SubRegionDev{s0, spacing, nguess, n, split_dynamic, fixed_first ? 1u : 0u, k0, 0u, J.d_src, J.src_len});
+                    nguess += 2u * n;
+                }
+            }
+            span[k].second = nguess;
+        }
+        if (nguess) {
+            const size_t reg_b = (regions.size() * sizeof(SubRegionDev) + 255) & ~(size_t)255, out_b = (size_t)nguess * 16;
+            uint8_t *dp = nullptr, *hp2 = nullptr;
+            if (scratch_reserve(ws, kScrLargeSub, reg_b + out_b, false, (void **)&dp) != ZNG_ROCM_OK ||
+                scratch_reserve(ws, kScrLargeSubHost, reg_b + out_b, true, (void **)&hp2) != ZNG_ROCM_OK) {
+                nguess = 0;                               // (no sub-starts: the streams go on with the starts found)
+            } else {
+                std::copy(regions.begin(), regions.end(), (SubRegionDev *)hp2);
+                unsigned long long *d_bit = (unsigned long long *)(dp + reg_b), *h_bit = (unsigned long long *)(hp2 + reg_b);
+                ZR_HIP(hipMemcpyAsync(dp, hp2, regions.size() * sizeof(SubRegionDev), hipMemcpyHostToDevice, st));
+                if (int rc = launch_subblock_sync(nullptr, 0, (const SubRegionDev *)dp, regions.size(), d_bit, d_bit + nguess, st)) return rc;
+                ZR_HIP(hipMemcpyAsync(h_bit, d_bit, out_b, hipMemcpyDeviceToHost, st));
+                ZR_HIP(hipStreamSynchronize(st));
+                for (size_t k : scan) {
+                    RoundStream &s = rs[k];
+                    if (!s.dev || span[k].first == span[k].second) continue;
+                    const size_t len = jobs[s.job].src_len;
+                    std::vector<std::pair<unsigned long long, unsigned long long>> all;
+                    all.reserve(s.starts.size() + (span[k].second - span[k].first));
+                    for (size_t i = 0; i < s.starts.size(); ++i) all.emplace_back(s.starts[i], 0ull);
+                    for (uint32_t g = span[k].first; g < span[k].second; ++g) {
+                        const unsigned long long b = h_bit[g];
+                        if (b != ~0ull && b > 0 && (b >> 3) + 16 < len) all.emplace_back(b, h_bit[nguess + g]);
+                    }
+                    std::sort(all.begin(), all.end());
+                    all.erase(std::unique(all.begin(), all.end()), all.end());
+                    s.starts.clear();
+                    s.keys.clear();
+                    for (const auto &a : all) {
+                        s.starts.push_back(a.first);
+                        s.keys.push_back(a.second);
+                        s.heavy += a.second != 0;
+                    }
+                }
+            }
+        }
+    }
+    // ---- the round's parts: each stream's together, the streams one behind the other ------------------------------------
+    size_t np = 0, heavy = 0;
+    std::vector<size_t> on;                               // streams in the part launch
+    for (size_t k : scan) {
+        RoundStream &s = rs[k];
+        if (!s.dev) continue;
+        if (s.starts.size() < 4) {
+            s.dev = false;
+            why("fewer than four block starts found");
+            continue;
+        }
+        if (np + s.starts.size() > kPieceMaxParts) {      // more parts than one launch (and the compaction grid) takes
+            if (on.empty()) {
+                s.dev = false;                            // one stream alone has them: not a stream for this call's device path
+                why("more parts in one stream than one launch takes");
+                continue;
+            }
+            *taken = k;                                   // this job and the ones behind it: the next round
+            break;
+        }
+        s.pbase = (uint32_t)np;
+        np += s.starts.size();
+        heavy += s.heavy;
+        on.push_back(k);
+    }
+    rs.resize(*taken);
+    auto to_host = [&]() {
+        for (const RoundStream &s : rs)
+            if (!s.dev) host.push_back(s.job);
+    };
+    if (on.empty()) {
+        to_host();
+        return ZNG_ROCM_OK;
+    }
+    auto all_out = [&](const char *reason) {
+        for (size_t k : on) rs[k].dev = false;
+        why(reason);
+        to_host();
+        return ZNG_ROCM_OK;
+    };
+    const bool many = heavy > 12u * cus;
+    std::vector<uint64_t> slot_off(np + 1, 0), part_bytes(np, 0);
+    const uint64_t slack = std::max<uint64_t>(64u << 10, std::min<uint64_t>(kSlotSlack, (2ull << 30) / np));
+    for (size_t k : on) {
+        const RoundStream &s = rs[k];
+        const size_t len = jobs[s.job].src_len, n = s.starts.size();
+        for (size_t i = 0; i < n; ++i) {
+            const uint64_t bytes = ((i + 1 < n ? s.starts[i + 1] : 8ull * len) - s.starts[i] + 7) >> 3;
+            part_bytes[s.pbase + i] = bytes;
+            slot_off[s.pbase + i + 1] = slot_off[s.pbase + i] + ((bytes * kSlotRatio + slack + 7) & ~7ull);
+        }
+    }
+    uint8_t *sp = nullptr, *hq = nullptr;
+    const size_t jobs_b = (np * sizeof(InflateJobDev) + 255) & ~(size_t)255, starts_b = (np * (sub ? 16 : 8) + 255) & ~(size_t)255,
+                 res_b = (np * 32 + (sub ? np * 32 : 0) + 255) & ~(size_t)255, slots_b = slot_off[np] * 2;
+    if (scratch_reserve(ws, kScrLargeParts, jobs_b + starts_b + res_b + slots_b, false, (void **)&sp) != ZNG_ROCM_OK)
+        return all_out("no room for the round's part slots");
+    if (scratch_reserve(ws, kScrLargePartsHost, jobs_b + starts_b + res_b, true, (void **)&hq) != ZNG_ROCM_OK)
+        return all_out("no pinned memory for the round's part tables");
+    InflateJobDev *d_jobs = (InflateJobDev *)sp, *pj = (InflateJobDev *)hq;
+    unsigned long long *d_starts = (unsigned long long *)(sp + jobs_b), *h_starts = (unsigned long long *)(hq + jobs_b);
+    uint32_t *d_res = (uint32_t *)(sp + jobs_b + starts_b), *res = (uint32_t *)(hq + jobs_b + starts_b);
+    uint16_t *d_slots = (uint16_t *)(sp + jobs_b + starts_b + res_b);
+    uint32_t *d_side = sub ? d_res + 8 * np : nullptr, *side = res + 8 * np;
+    const size_t res_words = sub ? 16 : 8;
+    for (size_t k : on) {
+        const RoundStream &s = rs[k];
+        const zng_rocm_inflate_large_job &J = jobs[s.job];
+        const size_t n = s.starts.size();
+        std::copy(s.starts.begin(), s.starts.end(), h_starts + s.pbase);
+        if (sub) std::copy(s.keys.begin(), s.keys.end(), h_starts + np + s.pbase);
+        for (size_t i = 0; i < n; ++i)
+            pj[s.pbase + i] = InflateJobDev{J.d_src, (uint8_t *)(d_slots + slot_off[s.pbase + i]), J.src_len,
+                                            slot_off[s.pbase + i + 1] - slot_off[s.pbase + i], i == 0 ? J.window_len : 32768u,
+                                            (uint32_t)(s.pbase + n)};
+    }
+    ZR_HIP(hipMemcpyAsync(sp, hq, jobs_b + np * (sub ? 16 : 8), hipMemcpyHostToDevice, st));      // jobs | starts (| keys)
+    if (int rc = launch_inflate_parts_device(d_jobs, np, d_res, d_starts, many, st, nullptr, d_side)) return rc;
+    ++t_batch_part_launches;
+    ZR_HIP(hipMemcpyAsync(res, d_res, np * 4 * res_words, hipMemcpyDeviceToHost, st));
+    ZR_HIP(hipStreamSynchronize(st));
+    // parts whose slot was too small (more than kSlotRatio : 1), of all streams: ONE launch more, with room for 1032 : 1.  A
+    // stream whose parts want more than is reasonable leaves the round; the others' parts are run again without it.
+    std::vector<uint16_t *> slot_ptr(np);
+    for (size_t i = 0; i < np; ++i) slot_ptr[i] = d_slots + slot_off[i];
+    {
+        std::vector<size_t> again;
+        uint64_t need = 0;
+        for (size_t k : on) {
+            RoundStream &s = rs[k];
+            uint64_t own = 0;
+            for (size_t i = s.pbase; i < s.pbase + s.starts.size(); ++i)
+                if (res[8 * i + 4] == kMsgOutFull) own += (part_bytes[i] * 1032u + kSlotSlack + 7) & ~7ull;
+            if (own * 2 > (24ull << 30)) {
+                s.dev = false;
+                why("parts with a ratio above 64 need more scratch than is reasonable");
+                continue;
+            }
+            for (size_t i = s.pbase; i < s.pbase + s.starts.size() && own; ++i)
+                if (res[8 * i + 4] == kMsgOutFull) again.push_back(i);
+            need += own;
+        }
+        if (!again.empty()) {
+            uint8_t *bigp = nullptr;
+            if (scratch_reserve(ws, kScrLargeRetry, need * 2, false, (void **)&bigp) != ZNG_ROCM_OK) {
+                for (size_t k : on) {                    // (the streams that asked leave; the others are complete)
+                    bool asked = false;
+                    for (size_t i = rs[k].pbase; i < rs[k].pbase + rs[k].starts.size(); ++i) asked |= res[8 * i + 4] == kMsgOutFull;
+                    if (asked) rs[k].dev = false;
+                }
+                why("no room for the parts with a ratio above 64");
+            } else {
+                for (size_t i = 0; i < np; ++i) pj[i].out_cap = 0;
+                uint64_t at = 0;
+                for (size_t i : again) {
+                    const uint64_t capi = (part_bytes[i] * 1032u + kSlotSlack + 7) & ~7ull;
+                    slot_ptr[i] = (uint16_t *)bigp + at;
+                    pj[i].out = (uint8_t *)slot_ptr[i];
+                    pj[i].out_cap = capi;
+                    at += capi;
+                }
+                ZR_HIP(hipMemcpyAsync(d_jobs, pj, np * sizeof(InflateJobDev), hipMemcpyHostToDevice, st));
+                if (int rc = launch_inflate_parts_device(d_jobs, np, d_res, d_starts, many, st, nullptr, d_side)) return rc;
+                ++t_batch_part_launches;
+                ZR_HIP(hipMemcpyAsync(res, d_res, np * 4 * res_words, hipMemcpyDeviceToHost, st));
+                ZR_HIP(hipStreamSynchronize(st));
+            }
+        }
+    }
+    // ---- one chain per stream (the walk of inflate_large_try, stream mode) ----------------------------------------------
+    for (size_t k : on) {
+        RoundStream &s = rs[k];
+        if (!s.dev) continue;
+        zng_rocm_inflate_large_job &J = jobs[s.job];
+        const size_t n = s.starts.size();
+        size_t cur = 0;
+        int fin = -1;
+        bool ok = true;
+        for (;;) {
+            const size_t g = s.pbase + cur;
+            const uint32_t *r = &res[8 * g];
+            const bool ended = r[3] == 1u;
+            if (sub && s.keys[cur] == 1u && fin == 1 && side[8 * g] != 0xffffffffu) {
+                // a fixed-code sub-part inside the FINAL block: the stream ends where its first block ended
+                const uint32_t *e = &side[8 * g];
+                s.end_bit = (unsigned long long)e[1] | ((unsigned long long)e[2] << 32);
+                if (s.end_bit > 8ull * J.src_len) { ok = false; why("the final block runs past the input"); break; }
+                if ((uint64_t)e[3] > s.produced + J.window_len) { ok = false; why("a distance reaches in front of the stream"); break; }
+                if (e[0]) s.copies.push_back(PartCopy{slot_ptr[g], s.produced, 0, e[0], 0u});
+                s.produced += e[0];
+                ++s.subparts;
+                break;
+            }
+            if (r[4] != kMsgNone || !(ended || r[6] != 0xffffffffu)) {                // error / truncation on the chain
+                set_error("inflate_large: sequential decoder (job %zu, part %zu of %zu at bit %llu: message %u \"%s\", %u symbols, "
+                          "ended on %d)", s.job, cur, n, s.starts[cur], r[4], zng_rocm_inflate_message(r[4]), r[0], (int)r[6]);
+                ok = false;
+                break;
+            }
+            if ((uint64_t)r[5] > s.produced + J.window_len) { ok = false; why("a distance reaches in front of the stream"); break; }
+            s.copies.push_back(PartCopy{slot_ptr[g], s.produced, 0, r[0], 0u});
+            s.produced += r[0];
+            s.end_bit = (unsigned long long)r[1] | ((unsigned long long)r[2] << 32);
+            if (ended) break;
+            if (sub) {
+                s.subparts += s.keys[cur] != 0;
+                if (side[8 * g + 4]) fin = side[8 * g + 5] == 2u ? fin : (int)side[8 * g + 5];
+                else fin = -1;
+            }
+            if (r[6] <= g || r[6] >= s.pbase + n) { ok = false; why("bad chain link"); break; }
+            cur = r[6] - s.pbase;
+        }
+        if (!ok) {
+            s.dev = false;
+            continue;
+        }
+        J.out_len = s.produced;
+        J.in_used = (size_t)((s.end_bit + 7) >> 3);
+        J.msg = nullptr;
+        J.parts = (uint32_t)s.copies.size();
+        J.subparts = (uint32_t)s.subparts;
+        if (s.produced > J.dst_cap) {                     // this job's trouble alone: nothing of it is written
+            J.status = -5;
+            continue;
+        }
+        J.status = 1;
+        if (!s.produced) continue;
+        // segments for the context chain, as for one stream: consecutive parts until kSegmentBytes of output are together
+        size_t first = 0;
+        for (size_t c = 0; c < s.copies.size(); ++c) {
+            if (s.copies[c].dst + s.copies[c].n - s.copies[first].dst >= kSegmentBytes || c + 1 == s.copies.size()) {
+                s.seg_first.push_back(first);
+                first = c + 1;
+            }
+        }
+        if (s.seg_first.size() > 1 && s.produced - s.copies[s.seg_first.back()].dst < 32768u) s.seg_first.pop_back();
+        s.seg_first.push_back(s.copies.size());
+        s.placed = true;
+    }
+    // ---- the streams one behind the other in ONE symbol array; compaction, resolve, translate ----------------------------
+    std::vector<uint64_t> segs, seg_dst, seg_end;
+    std::vector<BatchWindowDev> wins;
+    std::vector<PartCopy> copies;
+    uint64_t v = 32768, v_end = 0;
+    for (size_t k : on) {
+        RoundStream &s = rs[k];
+        if (!s.placed) continue;
+        const zng_rocm_inflate_large_job &J = jobs[s.job];
+        wins.push_back(BatchWindowDev{v, J.window_len ? J.d_window : nullptr, J.window_len});
+        const uint32_t c0 = (uint32_t)copies.size();
+        for (size_t g = 0; g + 1 < s.seg_first.size(); ++g) {
+            const uint64_t o0 = s.copies[s.seg_first[g]].dst;
+            const uint64_t o1 = g + 2 < s.seg_first.size() ? s.copies[s.seg_first[g + 1]].dst : s.produced;
+            for (size_t c = s.seg_first[g]; c < s.seg_first[g + 1]; ++c) {
+                PartCopy p = s.copies[c];
+                p.dst += v;
+                p.gstart = v + o0;
+                p.first = c0 + (uint32_t)s.seg_first[g];
+                copies.push_back(p);
+            }
+            segs.push_back(0);
+            segs.push_back(v + o0);
+            segs.push_back(0);
+            seg_dst.push_back((uint64_t)(uintptr_t)(J.d_dst + o0));
+            seg_end.push_back(v + o1);
+        }
+        v_end = v + s.produced;
+        v = v_end + 32768;                                // (a stream's last segment runs on through the gap behind it)
+    }
+    if (!copies.empty()) {
+        if (copies.size() > kPieceMaxParts) return all_out("more parts on the chains than the compaction grid takes");
+        segs.push_back(0);
+        segs.push_back(v_end);
+        segs.push_back(0);
+        const size_t nsegs = seg_dst.size();
+        const size_t segs_b = (segs.size() * 8 + 255) & ~(size_t)255, sd_b = (nsegs * 8 + 255) & ~(size_t)255,
+                     win_b = (wins.size() * sizeof(BatchWindowDev) + 255) & ~(size_t)255,
+                     cp_b = (copies.size() * sizeof(PartCopy) + 255) & ~(size_t)255, sym_b = ((size_t)v_end + 64) * 2;
+        uint8_t *yp = nullptr;
+        if (scratch_reserve(ws, kScrLargeSym, segs_b + 2 * sd_b + win_b + cp_b + sym_b, false, (void **)&yp) != ZNG_ROCM_OK) {
+            for (size_t k : on)
+                if (rs[k].placed) rs[k].dev = false;     // (the -5 jobs keep their status)
+            why("no room for the round's symbols");
+            to_host();
+            return ZNG_ROCM_OK;
+        }
+        uint64_t *d_segs = (uint64_t *)yp, *d_sd = (uint64_t *)(yp + segs_b), *d_se = (uint64_t *)(yp + segs_b + sd_b);
+        BatchWindowDev *d_win = (BatchWindowDev *)(yp + segs_b + 2 * sd_b);
+        PartCopy *d_cp = (PartCopy *)(yp + segs_b + 2 * sd_b + win_b);
+        uint16_t *sym = (uint16_t *)(yp + segs_b + 2 * sd_b + win_b + cp_b);
+        // (the five tables go up in ONE copy: each copy from pageable memory costs the host tens of microseconds)
+        std::vector<uint8_t> up(segs_b + 2 * sd_b + win_b + cp_b);
+        memcpy(up.data(), segs.data(), segs.size() * 8);
+        memcpy(up.data() + segs_b, seg_dst.data(), nsegs * 8);
+        memcpy(up.data() + segs_b + sd_b, seg_end.data(), nsegs * 8);
+        memcpy(up.data() + segs_b + 2 * sd_b, wins.data(), wins.size() * sizeof(BatchWindowDev));
+        memcpy(up.data() + segs_b + 2 * sd_b + win_b, copies.data(), copies.size() * sizeof(PartCopy));
+        ZR_HIP(hipMemcpyAsync(yp, up.data(), up.size(), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(compact_parts_kernel, dim3(16, (unsigned)copies.size()), dim3(256), 0, st, d_cp, sym);
+        ZR_HIP(hipGetLastError());
+        if (int rc = inflate_resolve_symbols_batch(d_segs, nsegs, sym, d_sd, d_se, d_win, wins.size(), st)) return rc;
+        ZR_HIP(hipStreamSynchronize(st));
+    }
+    to_host();
+    return ZNG_ROCM_OK;
+}
+
+extern "C" {
+
+int zng_rocm_inflate_large_last_rounds(void) { return t_batch_rounds; }
+int zng_rocm_inflate_large_last_part_launches(void) { return t_batch_part_launches; }
+
+int zng_rocm_inflate_large_streams_dev(zng_rocm_inflate_large_job *jobs, size_t njobs, size_t round_bytes, uint32_t flags,
+                                       void *stream) {
+    t_batch_rounds = 0;
+    t_batch_part_launches = 0;
+    if (!ctx()) {
+        set_error("zng_rocm_init() has not succeeded");
+        return ZNG_ROCM_ENODEV;
+    }
+    if (flags & ~ZNG_ROCM_INFLATE_SUBBLOCK) {
+        set_error("zng_rocm_inflate_large_streams_dev: unknown flag bits 0x%x", flags & ~ZNG_ROCM_INFLATE_SUBBLOCK);
+        return ZNG_ROCM_EINVAL;
+    }
+    if (round_bytes && (round_bytes < kRoundMin || round_bytes >= (1ull << 31))) {
+        set_error("zng_rocm_inflate_large_streams_dev: round_bytes %zu outside %zu .. 2 GiB", round_bytes, kRoundMin);
+        return ZNG_ROCM_EINVAL;
+    }
+    if (njobs && !jobs) return ZNG_ROCM_EINVAL;
+    for (size_t i = 0; i < njobs; ++i) {
+        const zng_rocm_inflate_large_job &j = jobs[i];
+        if ((!j.d_src && j.src_len) || j.window_len > 32768u || (j.window_len && !j.d_window) || (!j.d_dst && j.dst_cap)) {
+            set_error("zng_rocm_inflate_large_streams_dev: job %zu: a null buffer with a length, or window_len above 32768", i);
+            return ZNG_ROCM_EINVAL;
+        }
+    }
+    if (!njobs) return ZNG_ROCM_OK;
+    if (!round_bytes) round_bytes = kRoundDefault;
+    DeviceGuard dev;
+    hipStream_t st = (hipStream_t)stream;
+    const bool sub = flags != 0;
+    Workspace *ws = workspace_for(st);                   // scratch is keyed by the caller's HIP stream (context.h)
+    if (!ws) return ZNG_ROCM_ENOMEM;
+    int first_err = ZNG_ROCM_OK;
+    size_t next = 0;
+    while (next < njobs) {
+        // a round: jobs in order until their compressed bytes would pass round_bytes (a larger job is a round of its own)
+        std::vector<size_t> idx;
+        size_t bytes = 0;
+        for (size_t i = next; i < njobs; ++i) {
+            if (!idx.empty() && bytes + jobs[i].src_len > round_bytes) break;
+            idx.push_back(i);
+            bytes += jobs[i].src_len;
+        }
+        std::vector<size_t> host;
+        size_t taken = idx.size();
+        int rc;
+        {
+            std::lock_guard<std::mutex> use(ws->mu);
+            rc = round_run(ws, jobs, idx, sub, st, host, &taken);
+        }
+        ++t_batch_rounds;
+        if (rc != ZNG_ROCM_OK) {                         // a device error: the round's jobs have it, and the call ends
+            for (size_t k = 0; k < idx.size(); ++k) {
+                zng_rocm_inflate_large_job &j = jobs[idx[k]];
+                j.status = rc;
+                j.out_len = 0;
+                j.in_used = 0;
+                j.msg = nullptr;
+                j.parts = j.subparts = 0;
+            }
+            for (size_t i = idx.back() + 1; i < njobs; ++i) {
+                jobs[i].status = rc;
+                jobs[i].out_len = 0;
+                jobs[i].in_used = 0;
+                jobs[i].msg = nullptr;
+                jobs[i].parts = jobs[i].subparts = 0;
+            }
+            return rc;
+        }
+        // the jobs that left the round: the sequential decoder on a host copy, exactly as zng_rocm_inflate_large_ex_dev
+        for (size_t i : host) {
+            zng_rocm_inflate_large_job &j = jobs[i];
+            std::vector<uint8_t> copy(j.src_len ? j.src_len : 1);
+            int s = ZNG_ROCM_OK;
+            if (j.src_len && (hipMemcpyAsync(copy.data(), j.d_src, j.src_len, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                              hipStreamSynchronize(st) != hipSuccess)) {
+                set_error("zng_rocm_inflate_large_streams_dev: copying job %zu to the host failed", i);
+                s = ZNG_ROCM_EHIP;
+            }
+            uint64_t n = 0;
+            size_t used = 0;
+            const char *msg = nullptr;
+            if (s == ZNG_ROCM_OK)
+                s = inflate_raw_window_sequential_msg(copy.data(), j.src_len, j.d_window, j.window_len, j.d_dst, j.dst_cap, &n, &used,
+                                                      &msg, st);
+            j.status = s;
+            j.out_len = n;
+            j.in_used = used;
+            j.msg = s == -3 ? msg : nullptr;
+            j.parts = j.subparts = 0;
+            if ((s == ZNG_ROCM_EHIP || s == ZNG_ROCM_ENOMEM) && first_err == ZNG_ROCM_OK) first_err = s;
+        }
+        next = idx[0] + taken;
+    }
+    return first_err;
 }
 
 }  // extern "C"

@@ -26,6 +26,9 @@ int inflate_large_from_host(const uint8_t *src, size_t src_len, const uint8_t *d
 void inflate_large_forget_parts();       // the part counter of the calling thread back to 0 ("the sequential decoder did it")
 int inflate_raw_window_sequential(const uint8_t *src, size_t src_len, const uint8_t *d_window, uint32_t window_len, uint8_t *d_dst,
                                   size_t dst_cap, uint64_t *out_len, size_t *in_used, hipStream_t st);
+int inflate_raw_window_sequential_msg(const uint8_t *src, size_t src_len, const uint8_t *d_window, uint32_t window_len,
+                                      uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, size_t *in_used, const char **msg,
+                                      hipStream_t st);
 
 // K1.  One wavefront per segment, four per workgroup.  Per wave in LDS: a ring with the last 4096 symbols it
 // produced (recent back-references never touch HBM, and a match no longer waits for the wave's own stores to
@@ -388,6 +391,29 @@ int inflate_resolve_symbols(const uint64_t *d_segs, size_t nsegs, uint16_t *sym,
     return ZNG_ROCM_OK;
 }
 
+// the same for the streams of a batch whose symbols are in place (inflate_large.hip, zng_rocm_inflate_large_streams_dev):
+// the layout of inflate_resolve_batch above, without K1
+int inflate_resolve_symbols_batch(const uint64_t *d_segs, size_t nsegs, uint16_t *sym, const uint64_t *d_seg_dst,
+                                  const uint64_t *d_seg_end, const void *d_streams, size_t nstreams, hipStream_t st) {
+    if (!nsegs || !nstreams) return ZNG_ROCM_OK;
+    hipLaunchKernelGGL(inflate_windows_kernel, dim3((unsigned)(kCtx / 256), (unsigned)nstreams), dim3(256), 0, st,
+                       (const BatchStream *)d_streams, sym);
+    ZR_HIP(hipGetLastError());
+    if (nsegs > 1) {
+        const unsigned ngroups = (unsigned)((nsegs - 1 + kGroup - 1) / kGroup);
+        hipLaunchKernelGGL(inflate_context_group_kernel, dim3(ngroups), dim3(1024), 0, st, d_segs, nsegs, sym, 1);
+        ZR_HIP(hipGetLastError());
+        if (ngroups > 1) {
+            hipLaunchKernelGGL(inflate_context_chain_kernel, dim3(1), dim3(1024), 0, st, d_segs, nsegs, sym);
+            ZR_HIP(hipGetLastError());
+        }
+    }
+    ZR_LAUNCH_TRACED(inflate_translate_kernel, dim3((unsigned)nsegs), dim3(1024), st, d_segs, nsegs, sym, (uint8_t *)nullptr,
+                     d_seg_dst, d_seg_end);
+    ZR_HIP(hipGetLastError());
+    return ZNG_ROCM_OK;
+}
+
 }  // namespace zr
 
 using namespace zr;
@@ -543,6 +569,14 @@ namespace zr {
 // the sequential decoder on this thread + the device resolve: what every irregular stream ends up in
 int inflate_raw_window_sequential(const uint8_t *src, size_t src_len, const uint8_t *d_window, uint32_t window_len, uint8_t *d_dst,
                                   size_t dst_cap, uint64_t *out_len, size_t *in_used, hipStream_t st) {
+    return inflate_raw_window_sequential_msg(src, src_len, d_window, window_len, d_dst, dst_cap, out_len, in_used, nullptr, st);
+}
+
+// ... *msg (when given) = the decoder's message of a data error (static storage), else null
+int inflate_raw_window_sequential_msg(const uint8_t *src, size_t src_len, const uint8_t *d_window, uint32_t window_len,
+                                      uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, size_t *in_used, const char **msg,
+                                      hipStream_t st) {
+    if (msg) *msg = nullptr;
     zng_rocm_inflate_tokens tk;
     int status = zng_rocm_inflate_tokens_decode_window(src, src_len, window_len, &tk);
     if (out_len) *out_len = tk.out_len;
@@ -557,6 +591,7 @@ int inflate_raw_window_sequential(const uint8_t *src, size_t src_len, const uint
         return -5;
     }
     if (status < 0) set_error("%s", tk.msg);
+    if (status < 0 && msg) *msg = tk.msg;
     const int rc = inflate_tokens_to_device(&tk, d_window, window_len, d_dst, st);
     zng_rocm_inflate_tokens_free(&tk);
     return rc != ZNG_ROCM_OK ? rc : status;

@@ -311,3 +311,41 @@ def inflate_large_last_subparts():
 def inflate_large_last_substarts():
     """zng_rocm_inflate_large_last_substarts: sub-starts the calling thread's last SUBBLOCK call placed"""
     return int(rocm.lib().zng_rocm_inflate_large_last_substarts())
+
+
+class LargeJob(C.Structure):
+    """zng_rocm_inflate_large_job"""
+    _fields_ = [("d_src", C.c_void_p), ("src_len", C.c_size_t), ("d_window", C.c_void_p), ("window_len", C.c_uint32),
+                ("d_dst", C.c_void_p), ("dst_cap", C.c_size_t), ("status", C.c_int), ("out_len", C.c_uint64),
+                ("in_used", C.c_size_t), ("msg", C.c_char_p), ("parts", C.c_uint32), ("subparts", C.c_uint32)]
+
+
+def large_jobs(srcs_dev, dsts, windows=None):
+    """the job array of inflate_large_streams_dev for CUDA tensors (kept alive by the caller); output fields zeroed"""
+    n = len(srcs_dev)
+    jobs = (LargeJob * max(n, 1))()
+    for i in range(n):
+        w = None if windows is None else windows[i]
+        wl = 0 if w is None else int(w.numel())
+        jobs[i].d_src, jobs[i].src_len = rocm._dev_ptr(srcs_dev[i]), int(srcs_dev[i].numel())
+        jobs[i].d_window, jobs[i].window_len = (rocm._dev_ptr(w) if wl else None), wl
+        jobs[i].d_dst, jobs[i].dst_cap = rocm._dev_ptr(dsts[i]), int(dsts[i].numel())
+    return jobs
+
+
+def inflate_large_streams_dev(srcs_dev, dsts, windows=None, round_bytes=0, subblock=False, stream=None, flags=None, jobs=None):
+    """zng_rocm_inflate_large_streams_dev: a batch of large raw streams that are already in device memory (`srcs_dev`: uint8
+    CUDA tensors), decoded in rounds of one set of launches each; plaintext into the CUDA tensors `dsts`, optional per-job
+    history `windows` (CUDA tensors of <= 32768 bytes, or None).  Returns (return value, rows, rounds, part launches) with
+    rows = [(status, out_len, in_used, msg or None, parts, subparts)] per job.  `flags` overrides subblock (raw flag word);
+    `jobs` (from large_jobs) is used as it is when given."""
+    rocm._need_init()
+    lib = rocm.lib()
+    n = len(srcs_dev)
+    if jobs is None:
+        jobs = large_jobs(srcs_dev, dsts, windows)
+    fl = (SUBBLOCK if subblock else 0) if flags is None else int(flags)
+    rc = lib.zng_rocm_inflate_large_streams_dev(C.cast(jobs, C.c_void_p), n, int(round_bytes), fl, rocm._stream_ptr(stream))
+    rows = [(int(j.status), int(j.out_len), int(j.in_used), j.msg.decode() if j.msg else None, int(j.parts), int(j.subparts))
+            for j in jobs[:n]]
+    return rc, rows, int(lib.zng_rocm_inflate_large_last_rounds()), int(lib.zng_rocm_inflate_large_last_part_launches())

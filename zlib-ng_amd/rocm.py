@@ -132,6 +132,9 @@ _PROTOS = {
                                                     C.c_void_p]),
     "zng_rocm_inflate_large_last_pieces": (C.c_int, []),
     "zng_rocm_inflate_large_last_host_bytes": (C.c_uint64, []),
+    "zng_rocm_inflate_large_streams_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32, C.c_void_p]),
+    "zng_rocm_inflate_large_last_rounds": (C.c_int, []),
+    "zng_rocm_inflate_large_last_part_launches": (C.c_int, []),
     "zng_rocm_workspace_bytes": (C.c_size_t, [C.c_void_p]),
     "zng_rocm_hook_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_size_t]),
     "zng_rocm_hook_destroy": (None, [C.c_void_p]),
