@@ -208,6 +208,13 @@ typedef struct zng_rocm_check_job {
     uint32_t    crc;      /* seed */
 } zng_rocm_check_job;
 int zng_rocm_checksums_dev(int which, const zng_rocm_check_job *jobs, size_t njobs, uint32_t *d_out2, void *stream);
+/* The same for a FEW LARGE messages (the outputs of a round of zng_rocm_uncompress_large_streams_dev: a dozen of 2 .. 32 MiB,
+ * or one of gigabytes), where zng_rocm_checksums_dev -- the same number of workgroups for every message, one per 16 MiB and at
+ * most 16 -- would leave most of the chip idle: every message is cut into 512 KiB sub-messages, ALL sub-messages go through one
+ * many-message pass (one workgroup each), and one workgroup per message folds its sub-checks in order behind the message's
+ * seeds (adler32_combine_ / crc32_combine_, adler32.c:32-54, crc32_braid_comb.c:16-18).  Arguments, results and limits as
+ * zng_rocm_checksums_dev; one more small launch.  Asynchronous on `stream`. */
+int zng_rocm_checksums_cut_dev(int which, const zng_rocm_check_job *jobs, size_t njobs, uint32_t *d_out2, void *stream);
 
 /* ---- inflate-side copy primitive ------------------------------------------
  * slot `chunkmemset_safe` (chunkset_tpl.h:229-261) as a batch of INDEPENDENT copies inside one device
@@ -546,6 +553,53 @@ size_t zng_rocm_compress_streams_bound(size_t source_len, int format);
 int  zng_rocm_compress_streams_dev(int format, const zng_rocm_stream_job *jobs, size_t njobs, uint32_t *d_results, void *stream);
 int  zng_rocm_uncompress_streams_dev(int format, const zng_rocm_inflate_dev_job *jobs, size_t njobs, uint32_t *d_results,
                                      void *stream);
+
+/* zlib (format 1) / gzip (format 2) members around the LARGE device inflaters: zng_rocm_inflate_large_streams_dev (the
+ * batch) and zng_rocm_inflate_large_pieces_dev (one member of any length) for wrapped streams that already sit in device
+ * memory.  format 0 is the raw call itself, field for field and byte for byte; any other format value is ZNG_ROCM_EINVAL
+ * with nothing launched or written.
+ * Per job `d_src / src_len` is the whole member, wrapper included.  `d_window / window_len` is the PRESET DICTIONARY of a
+ * zlib member (inflateSetDictionary, inflate.c:1214-1261) and must be NULL / 0 for gzip (else ZNG_ROCM_EINVAL for the call,
+ * before anything is launched).  round_bytes / piece_bytes, flags (0 or ZNG_ROCM_INFLATE_SUBBLOCK), the refusals, the
+ * thread-local zng_rocm_inflate_large_last_* counters and the scratch bounds are those of the raw calls, which run on the
+ * payload.
+ * What happens: every header is parsed on the device, one wavefront per member (inflate.c:509-555 zlib, :556-700 gzip with
+ * FEXTRA / FNAME / FCOMMENT / FHCRC of any length, :702-715 DICTID; for zlib the Adler-32 of every dictionary given, one pass);
+ * one small readback; the raw engine on the payloads; the check values of all outputs in one many-message pass over 512 KiB
+ * sub-messages folded per member on the device (the single call: the full-grid checksum kernel over its one output); one
+ * small kernel compares the trailers (inflate.c:1105-1147).  Only the FIRST member of a multi-member gzip file is decoded;
+ * in_used is where the next one starts.  The header kernel and the checksum pass fetch aligned 16-byte lines: up to 15 bytes
+ * on either side of a member, a dictionary or an output, inside the same 16-byte line, are read (never used).
+ * Per job (batch) or per call (single; the text of a data error then in zng_rocm_last_error()):
+ *   member complete, check value and length agree   status 1, out_len, in_used = header + payload + trailer (4 / 8 bytes)
+ *   wrapper refused     -3, out_len 0, msg "incorrect header check" (also a gzip magic other than 1f 8b), "unknown
+ *                       compression method", "invalid window size" (inflate.c:527-546), "unknown header flags set"
+ *                       (:565-567), "header crc mismatch" (:686-692)
+ *   input ends inside the header                     -5, out_len 0, in_used = src_len
+ *   zlib FDICT set, no dictionary given              2 (Z_NEED_DICT, inflate.c:713-715), out_len 0, in_used 6
+ *   zlib FDICT set, Adler-32 of the dictionary differs from DICTID    -3, out_len 0, msg NULL (inflate.c:1247-1249)
+ *   zlib FDICT clear                                 the payload is decoded with NO history, dictionary or not
+ *   the payload's own trouble (data error, truncated, dst_cap too small)   as the raw call; in_used counts the header
+ *   payload complete, input ends inside the trailer  -5, out_len (the plaintext is in place), in_used = src_len
+ *   check value differs                              -3, out_len, msg "incorrect data check" (inflate.c:1132)
+ *   gzip ISIZE != out_len mod 2^32                   -3, out_len, msg "incorrect length check" (inflate.c:1146)
+ * Synchronous. */
+int  zng_rocm_uncompress_large_streams_dev(int format, zng_rocm_inflate_large_job *jobs, size_t njobs, size_t round_bytes,
+                                           uint32_t flags, void *stream);
+int  zng_rocm_uncompress_large_dev(int format, const uint8_t *d_src, size_t src_len, const uint8_t *d_dict, uint32_t dict_len,
+                                   uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, size_t *in_used, size_t piece_bytes,
+                                   uint32_t flags, void *stream);
+/* The wrapper alone, on HOST bytes: the same rules as the header kernel of the two calls above (one function for both),
+ * no device needed -- works before zng_rocm_init and without a GPU.  Returns 0 (header complete and accepted; info filled),
+ * 2 (accepted zlib header with FDICT: info->dictid is the Adler-32 the dictionary must have, header_len 6), -3 with the
+ * reference's text in *msg (static storage; msg may be NULL), -5 (src_len ends inside the header), ZNG_ROCM_EINVAL with
+ * *msg = NULL for a format outside 0 .. 2 or a null argument.  format 0: header_len 0. */
+typedef struct zng_rocm_wrapper_info {
+    uint64_t header_len;   /* bytes in front of the raw deflate payload */
+    uint32_t dictid;       /* zlib with FDICT: the Adler-32 the dictionary must have, else 0 */
+    uint32_t fdict;        /* 1 when the zlib header announces a preset dictionary */
+} zng_rocm_wrapper_info;
+int  zng_rocm_wrapper_parse(int format, const uint8_t *src, size_t src_len, zng_rocm_wrapper_info *info, const char **msg);
 
 /* ONE raw stream with its host decode spread over `nthreads` threads (zng_rocm_inflate_tokens_decode_threads) and one
  * device pass; same results and status as zng_rocm_inflate_raw_window, which it falls back to for streams that

@@ -50,4 +50,46 @@ struct FinalArgs {
 int launch_checksum_batch_device(bool do_adler, bool do_crc, const StreamArgs *d_messages, const FinalArgs *d_finals,
                                  Partial *d_part, size_t rows, uint32_t *d_out2, hipStream_t stream);
 
+#if defined(__HIPCC__)
+// The descriptors of one message of the many-message pass (one workgroup per message, seeds 1 / 0), built ON THE DEVICE as
+// checksum.hip's host code builds them: for messages whose address or length only the device knows, or that are cut there.
+__device__ __forceinline__ void fill_check_descriptor(const uint8_t *buf, uint64_t len, const DeviceTables *__restrict__ tabs, int do_adler,
+                                             int do_crc, StreamArgs *sa, FinalArgs *fa) {
+    const uintptr_t p = (uintptr_t)buf;
+    const uintptr_t a0 = p & ~(uintptr_t)15, tail_base = (p + len) & ~(uintptr_t)15;
+    StreamArgs s;
+    s.a0 = (const uint8_t *)a0;
+    s.dst0 = nullptr;
+    s.n = (long long)len;
+    s.body = (long long)(tail_base - a0);
+    s.nunits = (s.body + kUnitBytes - 1) / kUnitBytes;
+    s.head = (int)(p - a0);
+    s.tail = (int)((p + len) - tail_base);
+    s.phase_stamps = nullptr;
+    for (int k = 0; k < 4; ++k)
+        for (int b = 0; b < 8; ++b) {
+            s.bits.stride[k][b] = tabs->stride_tab[k][1u << b];
+            s.bits.x32[k][b] = tabs->x32_tab[k][1u << b];
+        }
+    *sa = s;
+    FinalArgs f;
+    f.tail_base = (const uint8_t *)tail_base;
+    f.tail_dst = nullptr;
+    f.n = s.n;
+    f.nunits = s.nunits;
+    f.tail_lo = s.body == 0 ? s.head : 0;
+    f.tail_hi = s.tail;
+    if (len == 0) f.tail_lo = f.tail_hi = 0;
+    f.groups = 1;
+    f.adler_seed = 1;
+    f.crc_seed = 0;
+    f.crc_len_pow = do_crc ? xpow_bytes(tabs->pow_tab, len) : 0u;
+    f.adler_seed_ptr = nullptr;
+    f.crc_seed_ptr = nullptr;
+    f.do_adler = do_adler;
+    f.do_crc = do_crc;
+    *fa = f;
+}
+#endif
+
 }  // namespace zr

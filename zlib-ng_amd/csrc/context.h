@@ -79,6 +79,10 @@ enum ScratchSlot {
     kScrLargeSub,           // device: regions | guesses' symbol boundaries | their keys (ZNG_ROCM_INFLATE_SUBBLOCK)
     kScrLargeSubHost,       // pinned: the same
     kScrLargeHist,          // device: the 32 KiB history of a piece, spliced from the caller's window and the output
+    kScrFrameLarge,         // device: header / trailer tables and sub-message checks of the wrapped large calls (framing_large.hip)
+    kScrFrameLargeHost,     // pinned: the same tables on their way up and down
+    kScrCheckCut,           // device: messages | first rows | descriptors, partials and checks of the sub-messages
+                            //   (zng_rocm_checksums_cut_dev)
     kScrCount
 };
 

@@ -146,40 +146,7 @@ void fill_check_args_kernel(const InflateJobDev *__restrict__ jobs, const uint32
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= njobs) return;
     const uint64_t len = (int32_t)inflated[4 * i + 2] == 1 ? inflated[4 * i] : 0u;
-    const uintptr_t p = (uintptr_t)jobs[i].out;
-    const uintptr_t a0 = p & ~(uintptr_t)15, tail_base = (p + len) & ~(uintptr_t)15;
-    StreamArgs s;
-    s.a0 = (const uint8_t *)a0;
-    s.dst0 = nullptr;
-    s.n = (long long)len;
-    s.body = (long long)(tail_base - a0);
-    s.nunits = (s.body + kUnitBytes - 1) / kUnitBytes;
-    s.head = (int)(p - a0);
-    s.tail = (int)((p + len) - tail_base);
-    s.phase_stamps = nullptr;
-    for (int k = 0; k < 4; ++k)
-        for (int b = 0; b < 8; ++b) {
-            s.bits.stride[k][b] = tabs->stride_tab[k][1u << b];
-            s.bits.x32[k][b] = tabs->x32_tab[k][1u << b];
-        }
-    sa[i] = s;
-    FinalArgs f;
-    f.tail_base = (const uint8_t *)tail_base;
-    f.tail_dst = nullptr;
-    f.n = s.n;
-    f.nunits = s.nunits;
-    f.tail_lo = s.body == 0 ? s.head : 0;
-    f.tail_hi = s.tail;
-    if (len == 0) f.tail_lo = f.tail_hi = 0;
-    f.groups = 1;
-    f.adler_seed = 1;
-    f.crc_seed = 0;
-    f.crc_len_pow = do_crc ? xpow_bytes(tabs->pow_tab, len) : 0u;
-    f.adler_seed_ptr = nullptr;
-    f.crc_seed_ptr = nullptr;
-    f.do_adler = do_adler;
-    f.do_crc = do_crc;
-    fa[i] = f;
+    fill_check_descriptor(jobs[i].out, len, tabs, do_adler, do_crc, sa + i, fa + i);
 }
 
 __global__ __launch_bounds__(256)

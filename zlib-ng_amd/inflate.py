@@ -349,3 +349,54 @@ def inflate_large_streams_dev(srcs_dev, dsts, windows=None, round_bytes=0, subbl
     rows = [(int(j.status), int(j.out_len), int(j.in_used), j.msg.decode() if j.msg else None, int(j.parts), int(j.subparts))
             for j in jobs[:n]]
     return rc, rows, int(lib.zng_rocm_inflate_large_last_rounds()), int(lib.zng_rocm_inflate_large_last_part_launches())
+
+
+class WrapperInfo(C.Structure):
+    """zng_rocm_wrapper_info"""
+    _fields_ = [("header_len", C.c_uint64), ("dictid", C.c_uint32), ("fdict", C.c_uint32)]
+
+
+def wrapper_parse(fmt, data):
+    """zng_rocm_wrapper_parse: the zlib (fmt 1) / gzip (fmt 2) wrapper of host bytes alone, by the rules the header kernel of
+    the wrapped large calls runs; needs no device.  Returns (status, header_len, dictid, fdict, msg or None): status 0
+    accepted, 2 accepted with a preset dictionary announced (dictid), -3 refused with the reference's text, -5 the bytes end
+    inside the header."""
+    keep, ptr, n = rocm._host_ptr(data)
+    info, msg = WrapperInfo(), C.c_char_p()
+    st = rocm.lib().zng_rocm_wrapper_parse(int(fmt), ptr, n, C.byref(info), C.byref(msg))
+    return st, int(info.header_len), int(info.dictid), int(info.fdict), msg.value.decode() if msg.value else None
+
+
+def uncompress_large_streams_dev(fmt, srcs_dev, dsts, dicts=None, round_bytes=0, subblock=False, stream=None, flags=None,
+                                 jobs=None):
+    """zng_rocm_uncompress_large_streams_dev: inflate_large_streams_dev for zlib (fmt 1) / gzip (fmt 2) members (fmt 0: the
+    raw call).  `srcs_dev`: the whole members, wrapper included; `dicts`: per job the preset dictionary of a zlib member or
+    None.  Returns (return value, rows, rounds, part launches), rows = [(status, out_len, in_used, msg or None, parts,
+    subparts)] as the raw call; status 2 = the member needs a dictionary."""
+    rocm._need_init()
+    lib = rocm.lib()
+    n = len(srcs_dev)
+    if jobs is None:
+        jobs = large_jobs(srcs_dev, dsts, dicts)
+    fl = (SUBBLOCK if subblock else 0) if flags is None else int(flags)
+    rc = lib.zng_rocm_uncompress_large_streams_dev(int(fmt), C.cast(jobs, C.c_void_p), n, int(round_bytes), fl,
+                                                   rocm._stream_ptr(stream))
+    rows = [(int(j.status), int(j.out_len), int(j.in_used), j.msg.decode() if j.msg else None, int(j.parts), int(j.subparts))
+            for j in jobs[:n]]
+    return rc, rows, int(lib.zng_rocm_inflate_large_last_rounds()), int(lib.zng_rocm_inflate_large_last_part_launches())
+
+
+def uncompress_large_dev(fmt, src_dev, dst, dict=None, piece_bytes=0, stream=None, subblock=False, flags=None):
+    """zng_rocm_uncompress_large_dev: inflate_large_pieces_dev for ONE zlib (fmt 1) / gzip (fmt 2) member of any length
+    (fmt 0: the raw call).  Returns (status, bytes produced, member bytes used, parts on the chains, device passes,
+    compressed bytes the sequential decoder took) as the raw call."""
+    rocm._need_init()
+    lib = rocm.lib()
+    out_len, in_used = C.c_uint64(0), C.c_size_t(0)
+    dl = 0 if dict is None else int(dict.numel())
+    fl = (SUBBLOCK if subblock else 0) if flags is None else int(flags)
+    st = lib.zng_rocm_uncompress_large_dev(int(fmt), rocm._dev_ptr(src_dev), int(src_dev.numel()), rocm._dev_ptr(dict) if dl else None,
+                                           dl, rocm._dev_ptr(dst), int(dst.numel()), C.byref(out_len), C.byref(in_used),
+                                           int(piece_bytes), fl, rocm._stream_ptr(stream))
+    return (st, int(out_len.value), int(in_used.value), int(lib.zng_rocm_inflate_large_last_parts()),
+            int(lib.zng_rocm_inflate_large_last_pieces()), int(lib.zng_rocm_inflate_large_last_host_bytes()))

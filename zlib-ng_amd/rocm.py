@@ -57,6 +57,7 @@ _PROTOS = {
     "zng_rocm_fold_copy_dev": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t,
                                          C.c_void_p, C.c_void_p]),
     "zng_rocm_checksums_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "zng_rocm_checksums_cut_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "zng_rocm_adler32_combine_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "zng_rocm_crc32_combine_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "zng_rocm_reserve_cus": (C.c_int, [C.c_int]),
@@ -135,6 +136,11 @@ _PROTOS = {
     "zng_rocm_inflate_large_streams_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32, C.c_void_p]),
     "zng_rocm_inflate_large_last_rounds": (C.c_int, []),
     "zng_rocm_inflate_large_last_part_launches": (C.c_int, []),
+    "zng_rocm_uncompress_large_streams_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32, C.c_void_p]),
+    "zng_rocm_uncompress_large_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t,
+                                                C.POINTER(C.c_uint64), C.POINTER(C.c_size_t), C.c_size_t, C.c_uint32,
+                                                C.c_void_p]),
+    "zng_rocm_wrapper_parse": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_char_p)]),
     "zng_rocm_workspace_bytes": (C.c_size_t, [C.c_void_p]),
     "zng_rocm_hook_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_size_t]),
     "zng_rocm_hook_destroy": (None, [C.c_void_p]),
@@ -357,6 +363,22 @@ def checksums_dev(which, buf, offsets, lengths, out2, adlers=None, crcs=None, st
         jobs[i].crc = 0 if crcs is None else int(crcs[i]) & 0xffffffff
     _check(lib().zng_rocm_checksums_dev(which, C.byref(jobs), n, _dev_ptr(out2), _stream_ptr(stream)),
            "zng_rocm_checksums_dev")
+
+
+def checksums_cut_dev(which, buf, offsets, lengths, out2, adlers=None, crcs=None, stream=None):
+    """checksums_dev for a few LARGE messages (zng_rocm_checksums_cut_dev): every message cut into 512 KiB sub-messages that all
+    go through one many-message pass, folded per message on the device.  Arguments as checksums_dev.  Async on `stream`."""
+    _need_init()
+    n = len(lengths)
+    jobs = (CheckJob * max(n, 1))()
+    base = buf.data_ptr()
+    for i in range(n):
+        jobs[i].buf = base + int(offsets[i])
+        jobs[i].len = int(lengths[i])
+        jobs[i].adler = 1 if adlers is None else int(adlers[i]) & 0xffffffff
+        jobs[i].crc = 0 if crcs is None else int(crcs[i]) & 0xffffffff
+    _check(lib().zng_rocm_checksums_cut_dev(which, C.byref(jobs), n, _dev_ptr(out2), _stream_ptr(stream)),
+           "zng_rocm_checksums_cut_dev")
 
 
 def adler32_combine_dev(checks, lens, out, stream=None):
