@@ -1,0 +1,165 @@
+"""CPU checks of the host plan of the large inflater (zlib-ng_amd/csrc/inflate_large_plan.h): the chain walk over the parts'
+result words and the grouping of parts into segments, which the one-stream call and the batch share.  A small C++ driver
+(tests/c/large_plan_driver.cpp) is built here with g++ and fed hand-written tables; every expected value below is worked out
+by hand from the rules in the header's and the part kernel's comments:
+
+  result words of a part  r = [symbols, end bit lo, end bit hi, 1 = ended the BFINAL block, message, reach, link, -]
+  side words (SUBBLOCK)   s = [symbols of the first block or NONE, its end bit lo, hi, its reach, handed off inside a block,
+                               that block's BFINAL (2 = unknown), -, -]
+  marks (blocks mode)     m = [symbols of the complete blocks, their end bit lo, hi, their reach]
+
+  part 0 is genuine; the part a genuine part links to is genuine; nothing else is.  A link points forward and into its own
+  stream.  A reach may not pass the bytes in front of the part (produced + window_len).  A key-1 part that begins inside the
+  BFINAL block ends the stream where its first block ended.  Segments are closed at >= 40960 symbols; a last one below 32768
+  joins the one in front of it unless it is the only one."""
+import os
+import subprocess
+import tempfile
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NONE = 0xFFFFFFFF
+STARVED, LITLEN_CODE = 12, 9                     # InflateMsg: kMsgStarved, kMsgLitLenCode
+NO_SIDE = [NONE, 0, 0, 0, 0, 0, 0, 0]
+
+
+@pytest.fixture(scope="module")
+def driver():
+    with tempfile.TemporaryDirectory() as tmp:
+        exe = os.path.join(tmp, "large_plan_driver")
+        subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-O1",
+                               "-I" + os.path.join(ROOT, "zlib-ng_amd", "csrc"),
+                               os.path.join(ROOT, "tests", "c", "large_plan_driver.cpp"), "-o", exe])
+        yield exe
+
+
+def part(n, end, ended=0, msg=0, reach=0, link=NONE):
+    return [n, end & 0xFFFFFFFF, end >> 32, ended, msg, reach, link, 0]
+
+
+def walk(exe, starts, res, keys=None, side=None, marks=None, pbase=0, window_len=0, src_len=1000, sub=0, blocks=0):
+    """-> (status line, produced, end_bit, final, subparts, [(table row, dst, n)], seg_first)"""
+    rows, np_ = len(res), len(starts)
+    keys = keys or [0] * np_
+    side = side or [NO_SIDE] * rows
+    marks = marks or [[0, 0, 0, 0]] * rows
+    assert len(keys) == np_ and len(side) == rows and len(marks) == rows and pbase + np_ <= rows
+    words = [rows, pbase, np_, window_len, src_len, sub, blocks] + list(starts) + list(keys)
+    for table in (res, side, marks):
+        for row in table:
+            words += row
+    out = subprocess.run([exe], input=" ".join(str(w) for w in words), capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stderr
+    status, numbers, copies, segs = out.stdout.strip("\n").split("\n")
+    produced, end_bit, final, subparts = (int(x) for x in numbers.split())
+    c = [int(x) for x in copies.split()[1:]]
+    return (status, produced, end_bit, final, subparts, [tuple(c[i:i + 3]) for i in range(0, len(c), 3)],
+            [int(x) for x in segs.split()[1:]])
+
+
+def test_clean_chain_of_four_parts(driver):
+    # each part ends on the next start; the last one ends the BFINAL block at bit 7990 of 8000
+    res = [part(50000, 1000, link=1), part(60000, 2000, link=2, reach=32768), part(100, 3000, link=3), part(20000, 7990, ended=1)]
+    got = walk(driver, [0, 1000, 2000, 3000], res)
+    # segments: [0] closes at 50000 >= 40960, [1] at 60000, parts 2 + 3 are 20100 < 32768 symbols and join the second
+    assert got == ("ok", 130100, 7990, 1, 0, [(0, 0, 50000), (1, 50000, 60000), (2, 110000, 100), (3, 110100, 20000)], [0, 1, 4])
+
+
+def test_a_candidate_never_landed_on_is_skipped(driver):
+    # start 1 was noise: part 0 ran across it and ended on start 2; what part 1 reports (a data error) is never looked at
+    res = [part(50000, 2000, link=2), part(7, 1100, msg=LITLEN_CODE), part(41000, 3000, link=3), part(40000, 7000, ended=1),
+           part(9, 7500, msg=LITLEN_CODE)]
+    got = walk(driver, [0, 1000, 2000, 3000, 7100], res)
+    assert got == ("ok", 131000, 7000, 1, 0, [(0, 0, 50000), (2, 50000, 41000), (3, 91000, 40000)], [0, 1, 2, 3])
+
+
+def test_a_message_or_a_missing_end_on_the_chain_fails_at_that_part(driver):
+    res = [part(50000, 1000, link=1), part(10, 1500, msg=LITLEN_CODE, link=2), part(5, 3000, ended=1)]
+    assert walk(driver, [0, 1000, 2000], res)[0] == "fail 1 a part's message, or no end"
+    res = [part(50000, 1000, link=1), part(10, 1500), part(5, 3000, ended=1)]        # not the end and no start landed on
+    assert walk(driver, [0, 1000, 2000], res)[0] == "fail 1 a part's message, or no end"
+
+
+@pytest.mark.parametrize("link", [1, 0, 4])       # itself, backwards, behind the stream's last part
+def test_a_link_that_does_not_point_forward_inside_the_stream_fails(driver, link):
+    res = [part(50000, 1000, link=1), part(100, 2000, link=link), part(100, 3000, link=3), part(100, 4000, ended=1)]
+    got = walk(driver, [0, 1000, 2000, 3000], res)
+    assert got[0] == "fail -1 bad chain link"
+    assert got[5] == [(0, 0, 50000), (1, 50000, 100)]          # (it stopped there: no second visit)
+
+
+def test_links_of_a_stream_inside_a_batch_table(driver):
+    # the stream's parts are rows 3 .. 6 of a launch of 8: links are rows of the table; rows 2 and 7 belong to other streams
+    other = part(1, 1, ended=1)
+    mine = [part(50000, 1000, link=4), part(45000, 2000, link=5), part(100, 3000, link=6), part(100, 4000, ended=1)]
+    res = [other] * 3 + mine + [other]
+    got = walk(driver, [0, 1000, 2000, 3000], res, pbase=3)
+    assert got == ("ok", 95200, 4000, 1, 0, [(3, 0, 50000), (4, 50000, 45000), (5, 95000, 100), (6, 95100, 100)], [0, 1, 4])
+    for bad in (2, 7):
+        res[4] = part(45000, 2000, link=bad)
+        assert walk(driver, [0, 1000, 2000, 3000], res, pbase=3)[0] == "fail -1 bad chain link"
+
+
+def test_a_distance_in_front_of_the_stream_fails(driver):
+    # part 0 may reach window_len bytes back, part 1 those and part 0's 1000
+    ok = [part(1000, 1000, link=1, reach=100), part(500, 2000, ended=1, reach=1100)]
+    assert walk(driver, [0, 1000], ok, window_len=100)[:3] == ("ok", 1500, 2000)
+    assert walk(driver, [0, 1000], ok, window_len=99)[0] == "fail -1 a distance reaches in front of the stream"
+    far = [part(1000, 1000, link=1, reach=100), part(500, 2000, ended=1, reach=1101)]
+    got = walk(driver, [0, 1000], far, window_len=100)
+    assert got[0] == "fail -1 a distance reaches in front of the stream" and got[5] == [(0, 0, 1000)]
+
+
+def test_a_fixed_code_sub_part_inside_the_final_block_ends_the_stream(driver):
+    starts, keys = [0, 1000, 2000, 3000], [0, 1, 1, 0]
+    # part 0 read a BFINAL header and handed off inside that block to part 1, whose first block -- the rest of it -- ended at
+    # bit 1900 after 700 symbols; what part 1 decoded behind that (its result words) is not part of the stream
+    res = [part(5000, 1000, link=1), part(9999, 3000, link=3), part(1, 2500, msg=LITLEN_CODE), part(1, 7000, ended=1)]
+    side = [[NONE, 0, 0, 0, 1, 1, 0, 0], [700, 1900, 0, 30, 0, 0, 0, 0], NO_SIDE, NO_SIDE]
+    got = walk(driver, starts, res, keys=keys, side=side, sub=1)
+    assert got == ("ok", 5700, 1900, 1, 1, [(0, 0, 5000), (1, 5000, 700)], [0, 2])
+    # its reach is checked like any part's, and its end has to lie inside the input (1000 bytes)
+    side[1] = [700, 1900, 0, 5001, 0, 0, 0, 0]
+    assert walk(driver, starts, res, keys=keys, side=side, sub=1)[0] == "fail -1 a distance reaches in front of the stream"
+    side[1] = [700, 8001, 0, 30, 0, 0, 0, 0]
+    assert walk(driver, starts, res, keys=keys, side=side, sub=1)[0] == "fail -1 the final block runs past the input"
+    # the block part 0 handed off in was NOT final: part 1 is an ordinary link of the chain, and counts as a sub-part
+    side[0], side[1] = [NONE, 0, 0, 0, 1, 0, 0, 0], [700, 1900, 0, 30, 0, 0, 0, 0]
+    got = walk(driver, starts, res, keys=keys, side=side, sub=1)
+    assert got == ("ok", 15000, 7000, 1, 1, [(0, 0, 5000), (1, 5000, 9999), (3, 14999, 1)], [0, 3])
+
+
+def test_the_final_flag_is_carried_across_a_sub_part_still_in_its_first_block(driver):
+    # part 1 began inside the BFINAL block and handed off to part 2 before that block ended (BFINAL word 2 = "unknown to
+    # me"): part 2 still knows the block is final, and ends the stream at its first block's end
+    starts, keys = [0, 1000, 2000], [0, 1, 1]
+    res = [part(5000, 1000, link=1), part(800, 2000, link=2), part(4000, 6000, ended=1)]
+    side = [[NONE, 0, 0, 0, 1, 1, 0, 0], [NONE, 0, 0, 0, 1, 2, 0, 0], [300, 2500, 0, 0, 0, 0, 0, 0]]
+    got = walk(driver, starts, res, keys=keys, side=side, sub=1)
+    assert got == ("ok", 6100, 2500, 1, 2, [(0, 0, 5000), (1, 5000, 800), (2, 5800, 300)], [0, 3])
+    # a part that ended on a block boundary (no hand-off) clears it: part 2's own result counts
+    side[1] = [NONE, 0, 0, 0, 0, 0, 0, 0]
+    got = walk(driver, starts, res, keys=keys, side=side, sub=1)
+    assert got == ("ok", 9800, 6000, 1, 1, [(0, 0, 5000), (1, 5000, 800), (2, 5800, 4000)], [0, 3])
+
+
+def test_blocks_mode_keeps_the_complete_blocks_of_the_part_that_ran_out_of_input(driver):
+    res = [part(50000, 1000, link=1), part(900, 8000, msg=STARVED)]
+    marks = [[0, 0, 0, 0], [300, 1500, 0, 10]]
+    got = walk(driver, [0, 1000], res, marks=marks, blocks=1)
+    assert got == ("ok", 50300, 1500, 0, 0, [(0, 0, 50000), (1, 50000, 300)], [0, 2])
+    assert walk(driver, [0, 1000], res, marks=marks)[0] == "fail 1 a part's message, or no end"       # stream mode: truncated
+
+
+@pytest.mark.parametrize("sizes, segs", [
+    ([100], [0, 1]),                              # a single short segment stands
+    ([50000, 32767], [0, 2]),                     # a tail below 32768 joins the segment in front
+    ([50000, 32768], [0, 1, 2]),                  # a segment's worth of tail stands
+    ([20000, 20000, 960, 40959, 1, 70000], [0, 3, 5, 6]),      # closed at exactly 40960; 40959 + 1 likewise
+])
+def test_segments(driver, sizes, segs):
+    starts = [1000 * i for i in range(len(sizes))]
+    res = [part(n, 1000 * (i + 1), link=i + 1) for i, n in enumerate(sizes[:-1])] + [part(sizes[-1], 1000 * len(sizes), ended=1)]
+    got = walk(driver, starts, res)
+    assert got[0] == "ok" and got[1] == sum(sizes) and got[6] == segs

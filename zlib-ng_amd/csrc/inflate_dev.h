@@ -2,6 +2,7 @@
 // d_results (texts: zng_rocm_inflate_message) and the launcher for a job table that already sits in device memory.
 #pragma once
 #include "context.h"
+#include "inflate_dev_types.h"
 
 namespace zr {
 
@@ -13,14 +14,6 @@ struct InflateJobDev {
     uint32_t       dict_len;
     uint32_t       flags;
 };
-
-enum InflateMsg : uint32_t {
-    kMsgNone = 0, kMsgBlockType, kMsgStoredLen, kMsgTooMany, kMsgCodeLengthsSet, kMsgBitRepeat, kMsgNoEob,
-    kMsgLitLenSet, kMsgDistSet, kMsgLitLenCode, kMsgDistCode, kMsgTooFar, kMsgStarved, kMsgOutFull,
-    // wrappers (framing_dev.hip; inflate.c:509-555 header checks, :686-692 FHCRC, :1105-1147 trailer checks)
-    kMsgHeaderCheck, kMsgMethod, kMsgWindow, kMsgHeaderCrc, kMsgNeedDict, kMsgDataCheck, kMsgLengthCheck, kMsgCount
-};
-
 
 // one wavefront per job; d_jobs and d_results are device memory (results: 4 words per job)
 int launch_inflate_streams_device(const InflateJobDev *d_jobs, size_t njobs, uint32_t *d_results, hipStream_t stream);
@@ -34,18 +27,7 @@ int launch_inflate_streams_device(const InflateJobDev *d_jobs, size_t njobs, uin
 int launch_inflate_parts_device(const InflateJobDev *d_jobs, size_t njobs, uint32_t *d_results, const unsigned long long *d_starts,
                                 bool many, hipStream_t stream, uint32_t *d_marks = nullptr, uint32_t *d_side = nullptr);
 
-// a region of the stream that starts at a block start the finder gave (one work item: at most 64 guesses, so a long region
-// is several items): `n` guesses at start + (k0 + k) * spacing, k = 1 .. n, written to out_bit / out_key [first + 2 (k - 1)] (a symbol boundary B and its key, or ~0 = none) and, when the region's
-// block does not have fixed codes and `fixed_too` is set, [first + 2 (k - 1) + 1] with fixed codes (a noise start inside a
-// fixed-code block reads as a dynamic header or a stored block's pattern); `dynamic` = 0: no guesses with a dynamic block's
-// tables
-struct SubRegionDev {
-    unsigned long long start, spacing;
-    uint32_t           first, n, dynamic, fixed_too, k0;
-    uint32_t           pad = 0;
-    const uint8_t     *src = nullptr;      // a batch of streams in one launch: the region's own stream (null: the launch's)
-    unsigned long long src_len = 0;
-};
+// the sync kernel over a table of regions (SubRegionDev: inflate_dev_types.h)
 int launch_subblock_sync(const uint8_t *d_src, size_t src_len, const SubRegionDev *d_regions, size_t nregions,
                          unsigned long long *d_bit, unsigned long long *d_key, hipStream_t stream);
 

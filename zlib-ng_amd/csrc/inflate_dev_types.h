@@ -1,0 +1,28 @@
+// inflate_dev_types.h -- the part of inflate_dev.h that needs no HIP: the message ids of d_results and the sync kernel's work
+// item.  inflate_large_plan.h (plain host code, compiled by a CPU test as well) is built on these.
+#pragma once
+#include <stdint.h>
+
+namespace zr {
+
+enum InflateMsg : uint32_t {
+    kMsgNone = 0, kMsgBlockType, kMsgStoredLen, kMsgTooMany, kMsgCodeLengthsSet, kMsgBitRepeat, kMsgNoEob,
+    kMsgLitLenSet, kMsgDistSet, kMsgLitLenCode, kMsgDistCode, kMsgTooFar, kMsgStarved, kMsgOutFull,
+    // wrappers (framing_dev.hip; inflate.c:509-555 header checks, :686-692 FHCRC, :1105-1147 trailer checks)
+    kMsgHeaderCheck, kMsgMethod, kMsgWindow, kMsgHeaderCrc, kMsgNeedDict, kMsgDataCheck, kMsgLengthCheck, kMsgCount
+};
+
+// a region of the stream that starts at a block start the finder gave (one work item: at most 64 guesses, so a long region
+// is several items): `n` guesses at start + (k0 + k) * spacing, k = 1 .. n, written to out_bit / out_key [first + 2 (k - 1)] (a symbol boundary B and its key, or ~0 = none) and, when the region's
+// block does not have fixed codes and `fixed_too` is set, [first + 2 (k - 1) + 1] with fixed codes (a noise start inside a
+// fixed-code block reads as a dynamic header or a stored block's pattern); `dynamic` = 0: no guesses with a dynamic block's
+// tables
+struct SubRegionDev {
+    unsigned long long start, spacing;
+    uint32_t           first, n, dynamic, fixed_too, k0;
+    uint32_t           pad = 0;
+    const uint8_t     *src = nullptr;      // a batch of streams in one launch: the region's own stream (null: the launch's)
+    unsigned long long src_len = 0;
+};
+
+}  // namespace zr

@@ -14,13 +14,13 @@
 //        validity rules of inflate_table to the two code sets (inftrees.c:104-137): about 1 random position in 10^6
 //        survives both kernels, real block starts all do.
 //   host                        sorts the few thousand candidates (at least 2 KiB of compressed bytes apart); bit 0 is
-//        always a start.
+//        always a start (thin_starts).
 //   P  inflate_streams_kernel<PART>  one wavefront per part, from its start until a block ends EXACTLY on a later start
 //        (or BFINAL), 16-bit symbols into the part's own slot (a symbol >= 256 names a byte of the 32 KiB in front of
 //        the part: nobody knows yet what is there).
 //   host                        chains the parts from bit 0: part 0 is genuine, the part that starts where it ended is
 //        therefore genuine too, ...; a candidate that was noise is simply never reached (and the part in front of it has
-//        run across it).  Then every part's place in the output is known.
+//        run across it).  Then every part's place in the output is known (walk_chain, group_segments).
 //   C  compact_parts_kernel     slots -> one symbol array, consecutive parts grouped into segments of >= 40 KiB (the
 //        context chain of inflate_resolve.hip looks one segment back) with their references re-based to the segment;
 //        K2 / K3 of inflate_resolve.hip resolve and translate.
@@ -29,12 +29,18 @@
 // A BATCH of such streams (zng_rocm_inflate_large_streams_dev, at the end of this file) runs the same steps once per round
 // over the parts of all its streams: the finder over a table of (stream, range) items, one part launch, one compaction,
 // one resolve.
+// What the host does between the launches -- the steps named above, the SUBBLOCK regions and their merge, the slot sizes --
+// is in inflate_large_plan.h, one copy for the one-stream path (inflate_large_try) and the batch (round_run).  This file
+// keeps the kernels, scratch and table uploads, the launches and synchronisations, and each entry point's policy for a
+// stream the device path cannot do.
 #include <algorithm>
+#include <cstdio>
 #include <cstring>
 #include <mutex>
 #include <vector>
 
 #include "inflate_large_limits.h"
+#include "inflate_large_plan.h"
 #include "context.h"
 #include "deflate_dev.h"
 #include "inflate_dev.h"
@@ -42,15 +48,6 @@
 
 namespace zr {
 
-constexpr uint32_t kSpacingBytes = 2u << 10;      // least compressed bytes between two starts -- applied only when there are
-constexpr uint32_t kPartsUnthinned = 12288;       // more candidates than this.  (Thinning a short list loses real starts:
-                                                  // about one random bit position in 10^6 passes F1 + F2, and a false start
-                                                  // within the spacing in front of a real one would take its place; a false
-                                                  // start that is kept costs one wasted part and nothing else.)
-constexpr uint32_t kSegmentBytes = 40u << 10;     // parts are grouped into segments of at least this much OUTPUT for the
-                                                  // context chain (which looks one segment back: >= 32 KiB each)
-constexpr uint32_t kSlotRatio = 64;               // symbols of slot per compressed byte of the part ...
-constexpr uint32_t kSlotSlack = 640u << 10;       // ... plus this (a 512 KiB run of one byte is ~600 bytes of deflate data)
 // SUBBLOCK (zng_rocm_inflate_large_ex_dev): guesses for starts inside blocks, one every `step` compressed bits of a region,
 // step = the stream's bits / (kSubPerSlot x the chip's resident parts), at least kSubMinStep bits -- so that a block of any
 // length is cut into pieces of about the same compressed size, whatever it expands to
@@ -428,14 +425,6 @@ __device__ __forceinline__ void validate_one(const uint8_t *__restrict__ src, un
     accept();
 }
 
-struct PartCopy {
-    const uint16_t *src;      // the part's slot
-    uint64_t        dst;      // its first symbol's index in the stream's symbol array
-    uint64_t        gstart;   // first symbol of the SEGMENT (group of consecutive parts) it belongs to
-    uint32_t        n;
-    uint32_t        first;    // chain index of the segment's first part
-};
-
 // C.  grid.y = part on the chain: its symbols go to their place in the stream's symbol array.  A part's references count
 // back from the PART's first byte; the context chain wants them counted from the SEGMENT's: a reference that lands inside
 // an earlier part of the same segment is replaced by the symbol that part has there (itself possibly a reference: the
@@ -511,29 +500,28 @@ static int why(const char *reason) {
     set_error("inflate_large: sequential decoder (%s)", reason);
     return 0;
 }
+// the same for a chain walk that failed: its reason, or -- a part's own result -- which part (of `np`; starts, keys or null,
+// result words and job entries are the stream's own) and what it said; `job` < 0: not a batch
+static int why_chain(const Chain &c, size_t np, const unsigned long long *starts, const unsigned long long *keys, const uint32_t *res,
+                     const InflateJobDev *jobs, long job) {
+    if (c.bad_part >= np) return why(c.reason);
+    char of[32] = "";
+    if (job >= 0) snprintf(of, sizeof of, "job %ld, ", job);
+    const size_t cur = c.bad_part;
+    const uint32_t *r = &res[8 * cur];                    // (key, where the part began: 0 a block start, 1 fixed, H + 2 dynamic)
+    set_error("inflate_large: sequential decoder (%spart %zu of %zu at bit %llu, key %llu: message %u \"%s\", %u symbols of %llu, "
+              "ended on %d)", of, cur, np, starts[cur], keys ? keys[cur] : 0ull, r[4], zng_rocm_inflate_message(r[4]), r[0],
+              (unsigned long long)jobs[cur].out_cap, (int)r[6]);
+    return 0;
+}
 
-// One device pass of zng_rocm_inflate_large_pieces_dev over a piece of the stream.  The pass's buffer (d_src, src_len of
-// inflate_large_try) begins at or in front of the piece -- at the header of the dynamic block a sub-start lies in, when it
-// does -- and ends at the piece's end; the finder scans from `scan_lo` on.  Scratch is checked against caps that depend on
-// the piece size alone (`q` = the largest piece, in compressed bytes); a pass that would need more asks to be run again
-// with half the piece.
-struct PiecePass {
-    uint64_t scan_lo = 0;         // byte of the buffer where the piece (and the finder's scan) begins
-    uint64_t key0 = 0;            // key of the first start: 0 a block start, 1 inside a fixed-code block, H + 2 (buffer bits)
-    int      fin0 = -1;           // BFINAL of the fixed-code block a key-1 first start lies in (-1 unknown)
-    bool     last = false;        // the piece reaches the end of the stream: stream mode (truncation, in_used, errors)
-    uint64_t q = 0;
-    // out
-    bool     stopped = false;     // the chain stopped at a part that ran out of the piece: the next piece starts there
-    uint64_t next_bit = 0, next_key = 0;
-    int      next_fin = -1;
-    bool     halve = false;       // the scratch caps were exceeded
-};
-// caps of one pass in bytes, q = piece bytes (the device scratch of a pieces call is their sum: DESIGN 3.10, zng_rocm.h)
-constexpr uint32_t kPieceMaxParts = 65535;                      // also the compaction grid's y limit
-inline uint64_t piece_cap_sub(uint64_t q) { return q / 8 + (1u << 20); }
-inline uint64_t piece_cap_retry(uint64_t q) { return 32 * q; }
-inline uint64_t piece_cap_sym(uint64_t q) { return 48 * q; }
+// the part counters of the calling thread back to 0 (a call begins; or "the sequential decoder did it": inflate_resolve.hip)
+void inflate_large_forget_parts() {
+    t_large_parts = 0;
+    t_large_subparts = 0;
+    t_large_substarts = 0;
+}
+
 
 // returns 1 with *out_len / *in_used set, or 0 = "irregular: use the sequential decoder", or a negative error.
 // Blocks mode (`blocks`, the streaming hook): the stream starts at bit `start_bit` of d_src, and input that ends inside a
@@ -545,8 +533,7 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
                              uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, size_t *in_used, hipStream_t st,
                              bool blocks = false, uint64_t start_bit = 0, uint64_t *end_bit_out = nullptr, int *final_out = nullptr,
                              bool sub = false, PiecePass *pp = nullptr) {
-    if (src_len < (128u << 10) || src_len >= (1ull << 31)) return why("stream below 128 KiB (or 2 GiB and more)");
-    const bool piece = pp && !pp->last;                   // the input ends at the piece's end, not the stream's
+    if (!large_length_ok(src_len)) return why("stream below 128 KiB (or 2 GiB and more)");
     // ---- candidates ---------------------------------------------------------------------------------------------
     // (pieces: the finder scans the piece alone, from scan_lo; its bit positions are moved to the buffer's by `lo_bits`)
     const size_t scan_lo = pp ? (size_t)pp->scan_lo : 0, scan_len = src_len - scan_lo;
@@ -561,7 +548,7 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
     // bytes without a start, that is all the cutting the stream needs and the search of every bit position (F1's
     // main loop) and F2 are skipped -- 1.3 of 9.4 ms for the 256 MiB cfg3 stream of this library's level-6 class
     std::vector<unsigned long long> good;
-    const uint32_t first = std::min<uint32_t>(cap2, 16384u);
+    const uint32_t first = patterns_first(scan_len);
     // what comes back from and goes up to the device between the launches passes through pinned memory (pageable copies of
     // these few hundred KiB were a good part of the 0.55 ms the host spends between the kernels of a 256 MiB stream)
     uint8_t *hp = nullptr;
@@ -576,20 +563,12 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
     ZR_HIP(hipMemcpyAsync(n12, d_n, 8, hipMemcpyDeviceToHost, st));
     ZR_HIP(hipMemcpyAsync(h_good, d_good, (size_t)first * 8, hipMemcpyDeviceToHost, st));
     ZR_HIP(hipStreamSynchronize(st));
-    // ... "enough" = no stretch of more than 128 KiB without one (a count would not do: the stored blocks of one incompressible
-    // region are thousands of starts and say nothing about the Huffman blocks elsewhere)
-    bool patterns_do = n12[1] >= 64u && n12[1] <= first;
+    bool patterns_do = n12[1] <= first;                   // (what came back is the whole list)
     if (patterns_do) {
         good.assign(h_good, h_good + n12[1]);
         for (unsigned long long &b : good) b = (b & ~(1ull << 63)) + lo_bits;
-        std::sort(good.begin(), good.end(), [](unsigned long long x, unsigned long long y) { return (x & ~(1ull << 62)) < (y & ~(1ull << 62)); });
-        unsigned long long prev = start_bit;
-        for (unsigned long long b62 : good) {
-            const unsigned long long b = b62 & ~(1ull << 62);
-            if (b - prev > 8ull * (128u << 10)) patterns_do = false;
-            prev = b;
-        }
-        if (8ull * src_len - prev > 8ull * (128u << 10)) patterns_do = false;
+        std::sort(good.begin(), good.end(), by_bit);
+        patterns_do = patterns_cut(good, start_bit, 8ull * src_len);
     }
     if (!patterns_do) {
         ZR_HIP(hipMemsetAsync(d_n, 0, 8, st));
@@ -617,34 +596,19 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
     }
     if (!patterns_do) {                                              // (the patterns' list has been sorted above)
         for (unsigned long long &b : good) b = (b & ~(1ull << 63)) + lo_bits;
-        std::sort(good.begin(), good.end(), [](unsigned long long x, unsigned long long y) { return (x & ~(1ull << 62)) < (y & ~(1ull << 62)); });
+        std::sort(good.begin(), good.end(), by_bit);
     }
     std::vector<unsigned long long> starts;
-    starts.push_back(start_bit);                          // (candidates in front of it, or on it, fall to the spacing test)
-    const unsigned long long spacing = good.size() > kPartsUnthinned ? 8ull * kSpacingBytes : 1ull;
-    size_t heavy = 1;                                     // parts that are not a stored block: the ones that take time
-    for (unsigned long long b62 : good) {
-        const unsigned long long b = b62 & ~(1ull << 62);
-        if (b >= starts.back() + spacing && (b >> 3) + 16 < src_len) {
-            starts.push_back(b);
-            heavy += !(b62 >> 62);
-        }
-    }
-    // ---- SUBBLOCK: starts inside blocks ---------------------------------------------------------------------------
-    // Guesses go into every gap between two starts found (and behind the last) -- none when the pattern pass alone cut the
-    // stream: its writer (this library's level-6 class, pigz) already closed a block every few tens of KiB, and that
-    // kernel is bound by throughput, not by a long part.  The sync kernel reads the block at the gap's start (fixed codes,
-    // or a dynamic header and its tables) and turns each guess into a symbol boundary B with that identity.  Dynamic
+    size_t heavy = 0;
+    thin_starts(good, start_bit, src_len, starts, heavy);
+    // ---- SUBBLOCK: starts inside blocks (plan_sub_regions) --------------------------------------------------------
+    // No guesses when the pattern pass alone cut the stream: its writer (this library's level-6 class, pigz) already closed
+    // a block every few tens of KiB, and that kernel is bound by throughput, not by a long part.  Dynamic
     // blocks are split while the Huffman starts found are no more than the chip's resident parts (12 per CU): the 256 MiB
     // CPython level-6 stream (about 2700 of them) takes 10.3 ms split against 10.6 ms whole; with more
-    // starts than slots the chip is full without splitting.  When the stream's first block has
-    // fixed codes, every gap that does not begin with fixed codes gets fixed-code guesses as well: about one bit position in
-    // 10^6 of fixed-code data passes F1 + F2 and one byte in 2^23 looks like a stored block's header, and the gap behind
-    // such a noise start would otherwise be one long part.
+    // starts than slots the chip is full without splitting.
     std::vector<unsigned long long> keys;                 // per start: 0 a block start, 1 inside a fixed-code block, H + 2 inside the dynamic block at H
-    // (pieces: the first start may lie inside a block itself -- a key-1 one gets fixed-code guesses, a key-(H + 2) one the
-    // tables of the header at H, with the guesses placed behind it)
-    const unsigned long long key0 = pp ? pp->key0 : 0ull;
+    const unsigned long long key0 = pp ? pp->key0 : 0ull;   // (pieces: the first start may lie inside a block itself)
     if (sub) {
         keys.assign(starts.size(), 0ull);
         keys[0] = key0;
@@ -656,27 +620,8 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
         const bool fixed_first = !patterns_do && (key0 == 1u || (key0 == 0u &&
                                  ((((unsigned)b0[0] | ((unsigned)b0[1] << 8)) >> ((start_bit & 7u) + 1u)) & 3u) == 1u));
         const uint32_t split_dynamic = heavy <= 12u * (size_t)ctx()->cus ? 1u : 0u;
-        for (size_t i = 0; i < starts.size() && !patterns_do && (split_dynamic || fixed_first); ++i) {
-            const unsigned long long s0 = starts[i], e0 = i + 1 < starts.size() ? starts[i + 1] : 8ull * src_len;
-            const unsigned long long pieces = (e0 - s0 + step / 2) / step;
-            if (pieces < 2) continue;
-            unsigned long long rs = s0;
-            const unsigned long long spacing = (e0 - s0) / pieces;
-            uint32_t j0 = 0, dyn = split_dynamic, ft = fixed_first ? 1u : 0u;
-            if (i == 0 && key0 == 1u) {                   // (what the sync kernel reads at s0 is no header: fixed guesses)
-                dyn = 0u;
-                ft = 1u;
-            } else if (i == 0 && key0 >= 2u) {            // the region reads the header at H; its guesses begin behind s0
-                rs = key0 - 2u;
-                j0 = (uint32_t)((s0 - rs) / spacing);
-            }
-            // one work item (wavefront) per 64 guesses: a long gap is not one wavefront's serial work
-            for (uint32_t k0 = 0; k0 < (uint32_t)(pieces - 1); k0 += 64u) {
-                const uint32_t n = std::min<uint32_t>(64u, (uint32_t)(pieces - 1) - k0);
-                regions.push_back(SubRegionDev{rs, spacing, nguess, n, dyn, ft, j0 + k0});
-                nguess += 2u * n;
-            }
-        }
+        // (the regions' own stream stays null: the sync kernel's launch names it)
+        if (!patterns_do) plan_sub_regions(starts, 8ull * src_len, step, split_dynamic, fixed_first, key0, nullptr, 0, regions, nguess);
         if (nguess) {
             const size_t reg_b = (regions.size() * sizeof(SubRegionDev) + 255) & ~(size_t)255, out_b = (size_t)nguess * 16;
             if (pp && reg_b + out_b > piece_cap_sub(pp->q)) {
@@ -692,23 +637,7 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
             if (int rc = launch_subblock_sync(d_src, src_len, (const SubRegionDev *)dp, regions.size(), d_bit, d_bit + nguess, st)) return rc;
             ZR_HIP(hipMemcpyAsync(h_bit, d_bit, out_b, hipMemcpyDeviceToHost, st));
             ZR_HIP(hipStreamSynchronize(st));
-            std::vector<std::pair<unsigned long long, unsigned long long>> all;
-            all.reserve(starts.size() + nguess);
-            for (size_t i = 0; i < starts.size(); ++i) all.emplace_back(starts[i], keys[i]);       // (keys[0]: a piece's key0)
-            for (uint32_t g = 0; g < nguess; ++g) {
-                const unsigned long long b = h_bit[g];
-                if (b != ~0ull && b > start_bit && (b >> 3) + 16 < src_len) all.emplace_back(b, h_bit[nguess + g]);
-            }
-            std::sort(all.begin(), all.end());
-            all.erase(std::unique(all.begin(), all.end()), all.end());
-            starts.clear();
-            keys.clear();
-            for (const auto &a : all) {
-                starts.push_back(a.first);
-                keys.push_back(a.second);
-                heavy += a.second != 0;
-                t_large_substarts += a.second != 0;
-            }
+            t_large_substarts += (int)merge_sub_starts(starts, keys, h_bit, h_bit + nguess, 0, nguess, start_bit, src_len, heavy);
         }
     }
     const size_t np = starts.size();
@@ -720,16 +649,8 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
     }
 
     // ---- parts ----------------------------------------------------------------------------------------------------
-    // (pieces: the parts' slack together stays within 8 symbols per compressed byte of the largest piece, 4 Ki at least)
-    std::vector<uint64_t> slot_off(np + 1, 0);
-    const uint64_t slack = pp ? std::max<uint64_t>(4u << 10, std::min<uint64_t>(kSlotSlack, 8 * pp->q / np))
-                              : std::max<uint64_t>(64u << 10, std::min<uint64_t>(kSlotSlack, (2ull << 30) / np));
-    for (size_t i = 0; i < np; ++i) {
-        const uint64_t bytes = ((i + 1 < np ? starts[i + 1] : 8ull * src_len) - starts[i] + 7) >> 3;
-        uint64_t capi = bytes * kSlotRatio + slack;
-        capi = (capi + 7) & ~7ull;
-        slot_off[i + 1] = slot_off[i] + capi;
-    }
+    std::vector<uint64_t> slot_off(np + 1, 0), part_bytes(np, 0);
+    slot_caps(starts.data(), np, 8ull * src_len, slot_slack(np, pp), slot_off.data(), part_bytes.data());
     uint8_t *sp = nullptr;
     // (SUBBLOCK: the keys follow the start bits, and 8 words per part follow the results)
     const size_t jobs_b = (np * sizeof(InflateJobDev) + 255) & ~(size_t)255, starts_b = (np * (sub ? 16 : 8) + 255) & ~(size_t)255,
@@ -759,7 +680,7 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
     if (int rc = launch_inflate_parts_device(d_jobs, np, d_res, d_starts, many, st, d_marks, d_side)) return rc;
     ZR_HIP(hipMemcpyAsync(res, d_res, np * 4 * res_words, hipMemcpyDeviceToHost, st));
     ZR_HIP(hipStreamSynchronize(st));
-    // parts whose slot was too small (more than kSlotRatio : 1): once more, with room for deflate's worst case (1032 : 1)
+    // parts whose slot was too small: once more, with retry_cap's room
     uint8_t *bigp = nullptr;
     std::vector<uint16_t *> slot_ptr(np);
     for (size_t i = 0; i < np; ++i) slot_ptr[i] = d_slots + slot_off[i];
@@ -769,8 +690,7 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
         for (size_t i = 0; i < np; ++i)
             if (res[8 * i + 4] == kMsgOutFull) {
                 again.push_back(i);
-                const uint64_t bytes = ((i + 1 < np ? starts[i + 1] : 8ull * src_len) - starts[i] + 7) >> 3;
-                need += (bytes * 1032u + kSlotSlack + 7) & ~7ull;
+                need += retry_cap(part_bytes[i]);
             }
         if (!again.empty()) {
             if (pp && need * 2 > piece_cap_retry(pp->q)) {
@@ -782,8 +702,7 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
             for (size_t i = 0; i < np; ++i) jobs[i].out_cap = 0;
             uint64_t at = 0;
             for (size_t i : again) {
-                const uint64_t bytes = ((i + 1 < np ? starts[i + 1] : 8ull * src_len) - starts[i] + 7) >> 3;
-                const uint64_t capi = (bytes * 1032u + kSlotSlack + 7) & ~7ull;
+                const uint64_t capi = retry_cap(part_bytes[i]);
                 slot_ptr[i] = (uint16_t *)bigp + at;
                 jobs[i].out = (uint8_t *)slot_ptr[i];
                 jobs[i].out_cap = capi;
@@ -801,102 +720,18 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
     g_dbg_res.assign(res, res + np * 8);
 #endif
     // ---- the chain from bit 0 -------------------------------------------------------------------------------------
-    std::vector<PartCopy> copies;
-    uint64_t produced = 0;
-    size_t cur = 0;
-    unsigned long long end_bit = start_bit;
-    bool final = false;
-    int fin = pp ? pp->fin0 : -1;                         // SUBBLOCK: BFINAL of the block the current part began inside
-    size_t subparts = 0;
-    for (;;) {
-        const uint32_t *r = &res[8 * cur];
-        const bool ended = r[3] == 1u;
-        // (pieces: an end behind the piece's input is no end yet -- the next piece decodes that part again)
-        const bool past = piece && sub && side[8 * cur] != 0xffffffffu &&
-                          ((unsigned long long)side[8 * cur + 1] | ((unsigned long long)side[8 * cur + 2] << 32)) > 8ull * src_len;
-        if (sub && keys[cur] == 1u && fin == 1 && side[8 * cur] != 0xffffffffu && !past) {
-            // a fixed-code sub-part inside the FINAL block (its header, read by a part in front, said so): the stream ends
-            // where its first block ended, whatever it decoded behind that
-            const uint32_t *s = &side[8 * cur];
-            end_bit = (unsigned long long)s[1] | ((unsigned long long)s[2] << 32);
-            if (end_bit > 8ull * src_len) return why("the final block runs past the input");
-            if ((uint64_t)s[3] > produced + window_len) return why("a distance reaches in front of the stream");
-            if (s[0]) copies.push_back(PartCopy{slot_ptr[cur], produced, 0, s[0], 0u});
-            produced += s[0];
-            ++subparts;
-            final = true;
-            break;
-        }
-        if (pp) {
-            // pieces: the first part on the chain that ran out of the piece's input is where the next piece begins; so is a
-            // part whose symbols would take the symbol array past its cap (in the last piece too)
-            const bool full = r[4] == kMsgNone && ((produced + r[0] + 32768 + 64) * 2 + 64 * (copies.size() + 1) + 512 >
-                                                   piece_cap_sym(pp->q));
-            if ((piece && r[4] == kMsgStarved) || full || (past && keys[cur] == 1u && fin == 1)) {
-                if (cur == 0) {
-                    pp->halve = full;
-                    return why(full ? "the piece's first part needs more scratch than its cap"
-                                    : "no start behind the piece's first is landed on");
-                }
-                pp->stopped = true;
-                pp->next_bit = starts[cur];
-                pp->next_key = sub ? keys[cur] : 0ull;
-                pp->next_fin = fin;
-                end_bit = starts[cur];
-                break;
-            }
-        }
-        if (blocks && r[4] == kMsgStarved) {            // the input ends in this part: its complete blocks, and no more
-            const uint32_t *m = &marks[4 * cur];
-            if ((uint64_t)m[3] > produced + window_len) return why("a distance reaches in front of the stream");
-            if (m[0]) copies.push_back(PartCopy{slot_ptr[cur], produced, 0, m[0], 0u});
-            produced += m[0];
-            end_bit = (unsigned long long)m[1] | ((unsigned long long)m[2] << 32);
-            break;
-        }
-        if (r[4] != kMsgNone || !(ended || r[6] != 0xffffffffu)) {                // error / truncation on the chain
-            if (!sub)
-                set_error("inflate_large: sequential decoder (part %zu of %zu at bit %llu: message %u \"%s\", %u symbols of %llu, "
-                          "ended on %d)", cur, np, starts[cur], r[4], zng_rocm_inflate_message(r[4]), r[0],
-                          (unsigned long long)jobs[cur].out_cap, (int)r[6]);
-            else                                          // (and where the part began: 0 a block start, 1 fixed, H + 2 dynamic)
-                set_error("inflate_large: sequential decoder (part %zu of %zu at bit %llu, key %llu: message %u \"%s\", %u symbols "
-                          "of %llu, ended on %d)", cur, np, starts[cur], keys[cur], r[4], zng_rocm_inflate_message(r[4]), r[0],
-                          (unsigned long long)jobs[cur].out_cap, (int)r[6]);
-            return 0;
-        }
-        if ((uint64_t)r[5] > produced + window_len) return why("a distance reaches in front of the stream");
-        copies.push_back(PartCopy{slot_ptr[cur], produced, 0, r[0], 0u});
-        produced += r[0];
-        end_bit = (unsigned long long)r[1] | ((unsigned long long)r[2] << 32);
-        if (ended) {
-            final = true;
-            break;
-        }
-        if (sub) {
-            subparts += keys[cur] != 0;
-            // handed off inside a block: the next part starts there and learns that block's BFINAL from here (2: this part
-            // did not know it either -- a fixed-code sub-part still in its first block -- so it stays what it was)
-            if (side[8 * cur + 4]) fin = side[8 * cur + 5] == 2u ? fin : (int)side[8 * cur + 5];
-            else fin = -1;
-        }
-        cur = r[6];
-        if (cur >= np) return why("bad chain link");
-    }
-    // segments for the context chain: consecutive parts until kSegmentBytes of output are together; what is left at the end
-    // joins the last segment unless it is a segment's worth itself (only the stream's LAST segment may be short)
+    Chain chain;
+    if (!walk_chain(res, side, marks, slot_ptr.data(), 0, np, starts.data(), sub ? keys.data() : nullptr, window_len, src_len, sub,
+                    blocks, pp, chain))
+        return why_chain(chain, np, starts.data(), sub ? keys.data() : nullptr, res, jobs, -1);
+    std::vector<PartCopy> &copies = chain.copies;
+    const uint64_t produced = chain.produced;
+    const unsigned long long end_bit = chain.end_bit;
+    const bool final = chain.final;
+    const size_t subparts = chain.subparts;
     std::vector<uint64_t> segs;                           // triples as inflate_resolve.hip wants them; only [3 s + 1] is used
     {
-        size_t first = 0;
-        std::vector<size_t> seg_first;
-        for (size_t c = 0; c < copies.size(); ++c) {
-            if (copies[c].dst + copies[c].n - copies[first].dst >= kSegmentBytes || c + 1 == copies.size()) {
-                seg_first.push_back(first);
-                first = c + 1;
-            }
-        }
-        if (seg_first.size() > 1 && produced - copies[seg_first.back()].dst < 32768u) seg_first.pop_back();
-        seg_first.push_back(copies.size());
+        const std::vector<size_t> seg_first = group_segments(copies, produced);
         for (size_t g = 0; g + 1 < seg_first.size(); ++g) {
             for (size_t c = seg_first[g]; c < seg_first[g + 1]; ++c) {
                 copies[c].gstart = copies[seg_first[g]].dst;
@@ -944,12 +779,6 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
     return 1;
 }
 
-void inflate_large_forget_parts() {
-    t_large_parts = 0;
-    t_large_subparts = 0;
-    t_large_substarts = 0;
-}
-
 // A large stream that is in HOST memory (zng_rocm_inflate_raw*, and with them uncompress2 and the gzip / zlib one-shots):
 // up over PCIe once and through the device path; 0 = not done here (the caller's sequential decoder takes it).
 int inflate_large_from_host(const uint8_t *src, size_t src_len, const uint8_t *d_window, uint32_t window_len, uint8_t *d_dst,
@@ -976,9 +805,7 @@ int inflate_large_from_host(const uint8_t *src, size_t src_len, const uint8_t *d
 // negatives = errors.
 int inflate_large_device_only(const uint8_t *d_src, size_t src_len, const uint8_t *d_window, uint32_t window_len, uint8_t *d_dst,
                               size_t dst_cap, uint64_t *out_len, size_t *in_used, hipStream_t st) {
-    t_large_parts = 0;
-    t_large_subparts = 0;
-    t_large_substarts = 0;
+    inflate_large_forget_parts();
     Workspace *ws = workspace_for(st);
     if (!ws) return ZNG_ROCM_ENOMEM;
     std::lock_guard<std::mutex> use(ws->mu);
@@ -991,9 +818,7 @@ int inflate_large_device_only(const uint8_t *d_src, size_t src_len, const uint8_
 int inflate_large_blocks_device_only(const uint8_t *d_src, size_t src_len, unsigned start_bit, const uint8_t *d_window,
                                      uint32_t window_len, uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, uint64_t *end_bit,
                                      int *final, hipStream_t st) {
-    t_large_parts = 0;
-    t_large_subparts = 0;
-    t_large_substarts = 0;
+    inflate_large_forget_parts();
     Workspace *ws = workspace_for(st);
     if (!ws) return ZNG_ROCM_ENOMEM;
     std::lock_guard<std::mutex> use(ws->mu);
@@ -1036,9 +861,7 @@ static int inflate_large_call(const uint8_t *d_src, size_t src_len, const uint8_
     if ((!d_src && src_len) || window_len > 32768u || (window_len && !d_window)) return ZNG_ROCM_EINVAL;
     DeviceGuard dev;
     hipStream_t st = (hipStream_t)stream;
-    t_large_parts = 0;
-    t_large_subparts = 0;
-    t_large_substarts = 0;
+    inflate_large_forget_parts();
     {
         Workspace *ws = workspace_for(st);               // scratch is keyed by the caller's HIP stream (context.h)
         if (!ws) return ZNG_ROCM_ENOMEM;
@@ -1250,9 +1073,7 @@ extern "C" {
 int zng_rocm_inflate_large_pieces_dev(const uint8_t *d_src, size_t src_len, const uint8_t *d_window, uint32_t window_len,
                                       uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, size_t *in_used, size_t piece_bytes,
                                       uint32_t flags, void *stream) {
-    t_large_parts = 0;
-    t_large_subparts = 0;
-    t_large_substarts = 0;
+    inflate_large_forget_parts();
     t_large_pieces = 0;
     t_large_host_bytes = 0;
     if (out_len) *out_len = 0;
@@ -1318,7 +1139,8 @@ namespace zr {
 // framing_large.hip answers a wrapped member whose header it refuses without reaching the calls above: the calling
 // thread's last_* counters then say that nothing ran
 void inflate_large_reset_counters() {
-    t_large_parts = t_large_subparts = t_large_substarts = t_large_pieces = 0;
+    inflate_large_forget_parts();
+    t_large_pieces = 0;
     t_large_host_bytes = 0;
     t_batch_rounds = t_batch_part_launches = 0;
 }
@@ -1334,11 +1156,8 @@ struct RoundStream {
     std::vector<unsigned long long> good, starts, keys;
     size_t heavy = 1;
     uint32_t pbase = 0;                                   // its first part in the round's tables
-    std::vector<PartCopy> copies;
+    Chain chain;                                          // its walk (walk_chain)
     std::vector<size_t> seg_first;
-    uint64_t produced = 0;
-    unsigned long long end_bit = 0;
-    size_t subparts = 0;
     bool placed = false;                                  // has symbols in the round's array
 };
 
@@ -1347,8 +1166,6 @@ struct BatchWindowDev {                                   // BatchStream of infl
     const uint8_t *d_window;
     uint64_t       window_len;
 };
-
-bool by_bit(unsigned long long x, unsigned long long y) { return (x & ~(1ull << 62)) < (y & ~(1ull << 62)); }
 
 }  // namespace
 
@@ -1438,8 +1255,7 @@ static int round_run(Workspace *ws, zng_rocm_inflate_large_job *jobs, const std:
     std::vector<size_t> scan;
     for (size_t k = 0; k < idx.size(); ++k) {
         rs[k].job = idx[k];
-        const size_t len = jobs[idx[k]].src_len;
-        if (len < (128u << 10) || len >= (1ull << 31)) rs[k].dev = false;      // (as inflate_large_try)
+        if (!large_length_ok(jobs[idx[k]].src_len)) rs[k].dev = false;
         else scan.push_back(k);
     }
     // ---- candidates: the byte patterns for every stream; F1 + F2 for those they do not cut ---------------------------
@@ -1449,17 +1265,7 @@ static int round_run(Workspace *ws, zng_rocm_inflate_large_job *jobs, const std:
         RoundStream &s = rs[k];
         if (!s.dev) continue;
         const size_t len = jobs[s.job].src_len;
-        const uint32_t first = (uint32_t)std::min<size_t>(len / 512 + 4096, 16384u);
-        s.patterns_do = s.good.size() >= 64u && s.good.size() <= first;
-        if (s.patterns_do) {
-            unsigned long long prev = 0;
-            for (unsigned long long b62 : s.good) {
-                const unsigned long long b = b62 & ~(1ull << 62);
-                if (b - prev > 8ull * (128u << 10)) s.patterns_do = false;
-                prev = b;
-            }
-            if (8ull * len - prev > 8ull * (128u << 10)) s.patterns_do = false;
-        }
+        s.patterns_do = s.good.size() <= patterns_first(len) && patterns_cut(s.good, 0, 8ull * len);
         if (!s.patterns_do) full.push_back(k);
     }
     if (int rc = round_find(ws, jobs, rs, full, false, sub, st)) return rc;
@@ -1474,20 +1280,12 @@ static int round_run(Workspace *ws, zng_rocm_inflate_large_job *jobs, const std:
             why("far more valid block headers than a deflate stream has");
             continue;
         }
-        s.starts.push_back(0);
-        const unsigned long long spacing = s.good.size() > kPartsUnthinned ? 8ull * kSpacingBytes : 1ull;
-        for (unsigned long long b62 : s.good) {
-            const unsigned long long b = b62 & ~(1ull << 62);
-            if (b >= s.starts.back() + spacing && (b >> 3) + 16 < len) {
-                s.starts.push_back(b);
-                s.heavy += !(b62 >> 62);
-            }
-        }
+        thin_starts(s.good, 0, len, s.starts, s.heavy);
         round_bits += 8ull * len;
         round_heavy += s.heavy;
     }
-    // ---- SUBBLOCK: guesses in the gaps, as inflate_large_try places them, with a step that fills the chip once per ROUND
-    // (a stream never gets a coarser step than a sixteenth of itself: a small stream among large ones is still cut) ----
+    // ---- SUBBLOCK: guesses in the gaps (plan_sub_regions), with a step that fills the chip once per ROUND (a stream never
+    // gets a coarser step than a sixteenth of itself: a small stream among large ones is still cut) ----
     if (sub) {
         const unsigned long long round_step = std::max<unsigned long long>(kSubMinStep, round_bits / (kSubPerSlot * 12ull * cus));
         const uint32_t split_dynamic = round_heavy <= 12u * cus ? 1u : 0u;
@@ -1502,17 +1300,8 @@ static int round_run(Workspace *ws, zng_rocm_inflate_large_job *jobs, const std:
             span[k].first = nguess;
             const unsigned long long step = std::max<unsigned long long>(kSubMinStep, std::min<unsigned long long>(round_step, 8ull * J.src_len / 16));
             const bool fixed_first = !s.patterns_do && ((unsigned)s.b0 >> 1 & 3u) == 1u;
-            for (size_t i = 0; i < s.starts.size() && !s.patterns_do && (split_dynamic || fixed_first); ++i) {
-                const unsigned long long s0 = s.starts[i], e0 = i + 1 < s.starts.size() ? s.starts[i + 1] : 8ull * J.src_len;
-                const unsigned long long pieces = (e0 - s0 + step / 2) / step;
-                if (pieces < 2) continue;
-                const unsigned long long spacing = (e0 - s0) / pieces;
-                for (uint32_t k0 = 0; k0 < (uint32_t)(pieces - 1); k0 += 64u) {
-                    const uint32_t n = std::min<uint32_t>(64u, (uint32_t)(pieces - 1) - k0);
-                    regions.push_back(SubRegionDev{s0, spacing, nguess, n, split_dynamic, fixed_first ? 1u : 0u, k0, 0u, J.d_src, J.src_len});
-                    nguess += 2u * n;
-                }
-            }
+            if (!s.patterns_do)
+                plan_sub_regions(s.starts, 8ull * J.src_len, step, split_dynamic, fixed_first, 0, J.d_src, J.src_len, regions, nguess);
             span[k].second = nguess;
         }
         if (nguess) {
@@ -1531,23 +1320,7 @@ static int round_run(Workspace *ws, zng_rocm_inflate_large_job *jobs, const std:
                 for (size_t k : scan) {
                     RoundStream &s = rs[k];
                     if (!s.dev || span[k].first == span[k].second) continue;
-                    const size_t len = jobs[s.job].src_len;
-                    std::vector<std::pair<unsigned long long, unsigned long long>> all;
-                    all.reserve(s.starts.size() + (span[k].second - span[k].first));
-                    for (size_t i = 0; i < s.starts.size(); ++i) all.emplace_back(s.starts[i], 0ull);
-                    for (uint32_t g = span[k].first; g < span[k].second; ++g) {
-                        const unsigned long long b = h_bit[g];
-                        if (b != ~0ull && b > 0 && (b >> 3) + 16 < len) all.emplace_back(b, h_bit[nguess + g]);
-                    }
-                    std::sort(all.begin(), all.end());
-                    all.erase(std::unique(all.begin(), all.end()), all.end());
-                    s.starts.clear();
-                    s.keys.clear();
-                    for (const auto &a : all) {
-                        s.starts.push_back(a.first);
-                        s.keys.push_back(a.second);
-                        s.heavy += a.second != 0;
-                    }
+                    merge_sub_starts(s.starts, s.keys, h_bit, h_bit + nguess, span[k].first, span[k].second, 0, jobs[s.job].src_len, s.heavy);
                 }
             }
         }
@@ -1594,15 +1367,10 @@ static int round_run(Workspace *ws, zng_rocm_inflate_large_job *jobs, const std:
     };
     const bool many = heavy > 12u * cus;
     std::vector<uint64_t> slot_off(np + 1, 0), part_bytes(np, 0);
-    const uint64_t slack = std::max<uint64_t>(64u << 10, std::min<uint64_t>(kSlotSlack, (2ull << 30) / np));
     for (size_t k : on) {
         const RoundStream &s = rs[k];
-        const size_t len = jobs[s.job].src_len, n = s.starts.size();
-        for (size_t i = 0; i < n; ++i) {
-            const uint64_t bytes = ((i + 1 < n ? s.starts[i + 1] : 8ull * len) - s.starts[i] + 7) >> 3;
-            part_bytes[s.pbase + i] = bytes;
-            slot_off[s.pbase + i + 1] = slot_off[s.pbase + i] + ((bytes * kSlotRatio + slack + 7) & ~7ull);
-        }
+        slot_caps(s.starts.data(), s.starts.size(), 8ull * jobs[s.job].src_len, slot_slack(np, nullptr), &slot_off[s.pbase],
+                  &part_bytes[s.pbase]);
     }
     uint8_t *sp = nullptr, *hq = nullptr;
     const size_t jobs_b = (np * sizeof(InflateJobDev) + 255) & ~(size_t)255, starts_b = (np * (sub ? 16 : 8) + 255) & ~(size_t)255,
@@ -1633,7 +1401,7 @@ static int round_run(Workspace *ws, zng_rocm_inflate_large_job *jobs, const std:
     ++t_batch_part_launches;
     ZR_HIP(hipMemcpyAsync(res, d_res, np * 4 * res_words, hipMemcpyDeviceToHost, st));
     ZR_HIP(hipStreamSynchronize(st));
-    // parts whose slot was too small (more than kSlotRatio : 1), of all streams: ONE launch more, with room for 1032 : 1.  A
+    // parts whose slot was too small, of all streams: ONE launch more, with retry_cap's room.  A
     // stream whose parts want more than is reasonable leaves the round; the others' parts are run again without it.
     std::vector<uint16_t *> slot_ptr(np);
     for (size_t i = 0; i < np; ++i) slot_ptr[i] = d_slots + slot_off[i];
@@ -1644,7 +1412,7 @@ static int round_run(Workspace *ws, zng_rocm_inflate_large_job *jobs, const std:
             RoundStream &s = rs[k];
             uint64_t own = 0;
             for (size_t i = s.pbase; i < s.pbase + s.starts.size(); ++i)
-                if (res[8 * i + 4] == kMsgOutFull) own += (part_bytes[i] * 1032u + kSlotSlack + 7) & ~7ull;
+                if (res[8 * i + 4] == kMsgOutFull) own += retry_cap(part_bytes[i]);
             if (own * 2 > (24ull << 30)) {
                 s.dev = false;
                 why("parts with a ratio above 64 need more scratch than is reasonable");
@@ -1667,7 +1435,7 @@ static int round_run(Workspace *ws, zng_rocm_inflate_large_job *jobs, const std:
                 for (size_t i = 0; i < np; ++i) pj[i].out_cap = 0;
                 uint64_t at = 0;
                 for (size_t i : again) {
-                    const uint64_t capi = (part_bytes[i] * 1032u + kSlotSlack + 7) & ~7ull;
+                    const uint64_t capi = retry_cap(part_bytes[i]);
                     slot_ptr[i] = (uint16_t *)bigp + at;
                     pj[i].out = (uint8_t *)slot_ptr[i];
                     pj[i].out_cap = capi;
@@ -1681,74 +1449,30 @@ static int round_run(Workspace *ws, zng_rocm_inflate_large_job *jobs, const std:
             }
         }
     }
-    // ---- one chain per stream (the walk of inflate_large_try, stream mode) ----------------------------------------------
+    // ---- one chain per stream: stream mode, and a stream whose walk fails leaves the round ---------------------------------
     for (size_t k : on) {
         RoundStream &s = rs[k];
         if (!s.dev) continue;
         zng_rocm_inflate_large_job &J = jobs[s.job];
-        const size_t n = s.starts.size();
-        size_t cur = 0;
-        int fin = -1;
-        bool ok = true;
-        for (;;) {
-            const size_t g = s.pbase + cur;
-            const uint32_t *r = &res[8 * g];
-            const bool ended = r[3] == 1u;
-            if (sub && s.keys[cur] == 1u && fin == 1 && side[8 * g] != 0xffffffffu) {
-                // a fixed-code sub-part inside the FINAL block: the stream ends where its first block ended
-                const uint32_t *e = &side[8 * g];
-                s.end_bit = (unsigned long long)e[1] | ((unsigned long long)e[2] << 32);
-                if (s.end_bit > 8ull * J.src_len) { ok = false; why("the final block runs past the input"); break; }
-                if ((uint64_t)e[3] > s.produced + J.window_len) { ok = false; why("a distance reaches in front of the stream"); break; }
-                if (e[0]) s.copies.push_back(PartCopy{slot_ptr[g], s.produced, 0, e[0], 0u});
-                s.produced += e[0];
-                ++s.subparts;
-                break;
-            }
-            if (r[4] != kMsgNone || !(ended || r[6] != 0xffffffffu)) {                // error / truncation on the chain
-                set_error("inflate_large: sequential decoder (job %zu, part %zu of %zu at bit %llu: message %u \"%s\", %u symbols, "
-                          "ended on %d)", s.job, cur, n, s.starts[cur], r[4], zng_rocm_inflate_message(r[4]), r[0], (int)r[6]);
-                ok = false;
-                break;
-            }
-            if ((uint64_t)r[5] > s.produced + J.window_len) { ok = false; why("a distance reaches in front of the stream"); break; }
-            s.copies.push_back(PartCopy{slot_ptr[g], s.produced, 0, r[0], 0u});
-            s.produced += r[0];
-            s.end_bit = (unsigned long long)r[1] | ((unsigned long long)r[2] << 32);
-            if (ended) break;
-            if (sub) {
-                s.subparts += s.keys[cur] != 0;
-                if (side[8 * g + 4]) fin = side[8 * g + 5] == 2u ? fin : (int)side[8 * g + 5];
-                else fin = -1;
-            }
-            if (r[6] <= g || r[6] >= s.pbase + n) { ok = false; why("bad chain link"); break; }
-            cur = r[6] - s.pbase;
-        }
-        if (!ok) {
+        const unsigned long long *keys = sub ? s.keys.data() : nullptr;
+        if (!walk_chain(res, side, nullptr, slot_ptr.data(), s.pbase, s.starts.size(), s.starts.data(), keys, J.window_len, J.src_len,
+                        sub, false, nullptr, s.chain)) {
+            why_chain(s.chain, s.starts.size(), s.starts.data(), keys, res + 8 * s.pbase, pj + s.pbase, (long)s.job);
             s.dev = false;
             continue;
         }
-        J.out_len = s.produced;
-        J.in_used = (size_t)((s.end_bit + 7) >> 3);
+        J.out_len = s.chain.produced;
+        J.in_used = (size_t)((s.chain.end_bit + 7) >> 3);
         J.msg = nullptr;
-        J.parts = (uint32_t)s.copies.size();
-        J.subparts = (uint32_t)s.subparts;
-        if (s.produced > J.dst_cap) {                     // this job's trouble alone: nothing of it is written
+        J.parts = (uint32_t)s.chain.copies.size();
+        J.subparts = (uint32_t)s.chain.subparts;
+        if (s.chain.produced > J.dst_cap) {               // this job's trouble alone: nothing of it is written
             J.status = -5;
             continue;
         }
         J.status = 1;
-        if (!s.produced) continue;
-        // segments for the context chain, as for one stream: consecutive parts until kSegmentBytes of output are together
-        size_t first = 0;
-        for (size_t c = 0; c < s.copies.size(); ++c) {
-            if (s.copies[c].dst + s.copies[c].n - s.copies[first].dst >= kSegmentBytes || c + 1 == s.copies.size()) {
-                s.seg_first.push_back(first);
-                first = c + 1;
-            }
-        }
-        if (s.seg_first.size() > 1 && s.produced - s.copies[s.seg_first.back()].dst < 32768u) s.seg_first.pop_back();
-        s.seg_first.push_back(s.copies.size());
+        if (!s.chain.produced) continue;
+        s.seg_first = group_segments(s.chain.copies, s.chain.produced);
         s.placed = true;
     }
     // ---- the streams one behind the other in ONE symbol array; compaction, resolve, translate ----------------------------
@@ -1763,10 +1487,11 @@ static int round_run(Workspace *ws, zng_rocm_inflate_large_job *jobs, const std:
         wins.push_back(BatchWindowDev{v, J.window_len ? J.d_window : nullptr, J.window_len});
         const uint32_t c0 = (uint32_t)copies.size();
         for (size_t g = 0; g + 1 < s.seg_first.size(); ++g) {
-            const uint64_t o0 = s.copies[s.seg_first[g]].dst;
-            const uint64_t o1 = g + 2 < s.seg_first.size() ? s.copies[s.seg_first[g + 1]].dst : s.produced;
+            const std::vector<PartCopy> &sc = s.chain.copies;
+            const uint64_t o0 = sc[s.seg_first[g]].dst;
+            const uint64_t o1 = g + 2 < s.seg_first.size() ? sc[s.seg_first[g + 1]].dst : s.chain.produced;
             for (size_t c = s.seg_first[g]; c < s.seg_first[g + 1]; ++c) {
-                PartCopy p = s.copies[c];
+                PartCopy p = sc[c];
                 p.dst += v;
                 p.gstart = v + o0;
                 p.first = c0 + (uint32_t)s.seg_first[g];
@@ -1778,7 +1503,7 @@ static int round_run(Workspace *ws, zng_rocm_inflate_large_job *jobs, const std:
             seg_dst.push_back((uint64_t)(uintptr_t)(J.d_dst + o0));
             seg_end.push_back(v + o1);
         }
-        v_end = v + s.produced;
+        v_end = v + s.chain.produced;
         v = v_end + 32768;                                // (a stream's last segment runs on through the gap behind it)
     }
     if (!copies.empty()) {
@@ -1817,6 +1542,15 @@ static int round_run(Workspace *ws, zng_rocm_inflate_large_job *jobs, const std:
     }
     to_host();
     return ZNG_ROCM_OK;
+}
+
+// a job that no device path answered: the status and counts given, no parts
+static void job_answer(zng_rocm_inflate_large_job &j, int status, uint64_t n, size_t used, const char *msg) {
+    j.status = status;
+    j.out_len = n;
+    j.in_used = used;
+    j.msg = msg;
+    j.parts = j.subparts = 0;
 }
 
 extern "C" {
@@ -1875,21 +1609,7 @@ int zng_rocm_inflate_large_streams_dev(zng_rocm_inflate_large_job *jobs, size_t 
         }
         ++t_batch_rounds;
         if (rc != ZNG_ROCM_OK) {                         // a device error: the round's jobs have it, and the call ends
-            for (size_t k = 0; k < idx.size(); ++k) {
-                zng_rocm_inflate_large_job &j = jobs[idx[k]];
-                j.status = rc;
-                j.out_len = 0;
-                j.in_used = 0;
-                j.msg = nullptr;
-                j.parts = j.subparts = 0;
-            }
-            for (size_t i = idx.back() + 1; i < njobs; ++i) {
-                jobs[i].status = rc;
-                jobs[i].out_len = 0;
-                jobs[i].in_used = 0;
-                jobs[i].msg = nullptr;
-                jobs[i].parts = jobs[i].subparts = 0;
-            }
+            for (size_t i = idx[0]; i < njobs; ++i) job_answer(jobs[i], rc, 0, 0, nullptr);
             return rc;
         }
         // the jobs that left the round: the sequential decoder on a host copy, exactly as zng_rocm_inflate_large_ex_dev
@@ -1908,11 +1628,7 @@ int zng_rocm_inflate_large_streams_dev(zng_rocm_inflate_large_job *jobs, size_t 
             if (s == ZNG_ROCM_OK)
                 s = inflate_raw_window_sequential_msg(copy.data(), j.src_len, j.d_window, j.window_len, j.d_dst, j.dst_cap, &n, &used,
                                                       &msg, st);
-            j.status = s;
-            j.out_len = n;
-            j.in_used = used;
-            j.msg = s == -3 ? msg : nullptr;
-            j.parts = j.subparts = 0;
+            job_answer(j, s, n, used, s == -3 ? msg : nullptr);
             if ((s == ZNG_ROCM_EHIP || s == ZNG_ROCM_ENOMEM) && first_err == ZNG_ROCM_OK) first_err = s;
         }
         next = idx[0] + taken;

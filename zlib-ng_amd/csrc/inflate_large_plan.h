@@ -1,0 +1,302 @@
+// inflate_large_plan.h -- the host steps between the kernel launches of inflate_large.hip, once for the one-stream path
+// (inflate_large_try: one pass, pieces, blocks mode) and the batch (round_run).  Plain C++ over integers and the part
+// tables, no HIP: every rule that decides what a valid result is -- which candidates become starts, where guesses go, how
+// large a slot is, which parts are genuine, how parts are grouped for the context chain -- lives here, and a CPU test
+// (tests/test_large_plan_cpu.py) drives the walk and the grouping with hand-written tables.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <utility>
+#include <vector>
+
+#include "inflate_dev_types.h"
+
+namespace zr {
+
+constexpr uint32_t kSpacingBytes = 2u << 10;      // least compressed bytes between two starts -- applied only when there are
+constexpr uint32_t kPartsUnthinned = 12288;       // more candidates than this.  (Thinning a short list loses real starts:
+                                                  // about one random bit position in 10^6 passes F1 + F2, and a false start
+                                                  // within the spacing in front of a real one would take its place; a false
+                                                  // start that is kept costs one wasted part and nothing else.)
+constexpr uint32_t kSegmentBytes = 40u << 10;     // parts are grouped into segments of at least this much OUTPUT for the
+                                                  // context chain (which looks one segment back: >= 32 KiB each)
+constexpr uint32_t kSlotRatio = 64;               // symbols of slot per compressed byte of the part ...
+constexpr uint32_t kSlotSlack = 640u << 10;       // ... plus this (a 512 KiB run of one byte is ~600 bytes of deflate data)
+
+struct PartCopy {
+    const uint16_t *src;      // the part's slot
+    uint64_t        dst;      // its first symbol's index in the stream's symbol array
+    uint64_t        gstart;   // first symbol of the SEGMENT (group of consecutive parts) it belongs to
+    uint32_t        n;
+    uint32_t        first;    // chain index of the segment's first part
+};
+
+// One device pass of zng_rocm_inflate_large_pieces_dev over a piece of the stream.  The pass's buffer (d_src, src_len of
+// inflate_large_try) begins at or in front of the piece -- at the header of the dynamic block a sub-start lies in, when it
+// does -- and ends at the piece's end; the finder scans from `scan_lo` on.  Scratch is checked against caps that depend on
+// the piece size alone (`q` = the largest piece, in compressed bytes); a pass that would need more asks to be run again
+// with half the piece.
+struct PiecePass {
+    uint64_t scan_lo = 0;         // byte of the buffer where the piece (and the finder's scan) begins
+    uint64_t key0 = 0;            // key of the first start: 0 a block start, 1 inside a fixed-code block, H + 2 (buffer bits)
+    int      fin0 = -1;           // BFINAL of the fixed-code block a key-1 first start lies in (-1 unknown)
+    bool     last = false;        // the piece reaches the end of the stream: stream mode (truncation, in_used, errors)
+    uint64_t q = 0;
+    // out
+    bool     stopped = false;     // the chain stopped at a part that ran out of the piece: the next piece starts there
+    uint64_t next_bit = 0, next_key = 0;
+    int      next_fin = -1;
+    bool     halve = false;       // the scratch caps were exceeded
+};
+// caps of one pass in bytes, q = piece bytes (the device scratch of a pieces call is their sum: DESIGN 3.10, zng_rocm.h)
+constexpr uint32_t kPieceMaxParts = 65535;                      // also the compaction grid's y limit
+inline uint64_t piece_cap_sub(uint64_t q) { return q / 8 + (1u << 20); }
+inline uint64_t piece_cap_retry(uint64_t q) { return 32 * q; }
+inline uint64_t piece_cap_sym(uint64_t q) { return 48 * q; }
+
+// what the device path takes: shorter streams are the sequential decoder's, and a bit position has to fit the tables' words
+inline bool large_length_ok(uint64_t src_len) { return src_len >= (128u << 10) && src_len < (1ull << 31); }
+
+// ---- candidates -> starts ---------------------------------------------------------------------------------------------
+// a candidate is its bit position, bit 62 set for "a stored block" (light work)
+inline bool by_bit(unsigned long long x, unsigned long long y) { return (x & ~(1ull << 62)) < (y & ~(1ull << 62)); }
+
+// as many of the pattern pass's survivors as come back with its counts; a longer list is not one the patterns cut
+inline uint32_t patterns_first(size_t scan_len) { return (uint32_t)std::min<size_t>(scan_len / 512 + 4096, 16384u); }
+
+// Do the byte patterns alone (sync markers, byte-aligned stored blocks; `good` sorted by bit) cut the stream [start_bit,
+// end_bit)?  "Enough" = no stretch of more than 128 KiB without one (a count would not do: the stored blocks of one
+// incompressible region are thousands of starts and say nothing about the Huffman blocks elsewhere).
+inline bool patterns_cut(const std::vector<unsigned long long> &good, unsigned long long start_bit, unsigned long long end_bit) {
+    if (good.size() < 64u) return false;
+    const unsigned long long gap = 8ull * (128u << 10);
+    unsigned long long prev = start_bit;
+    for (unsigned long long b62 : good) {
+        const unsigned long long b = b62 & ~(1ull << 62);
+        if (b - prev > gap) return false;
+        prev = b;
+    }
+    return end_bit - prev <= gap;
+}
+
+// the sorted candidates thinned into starts; `heavy` counts the parts that are not a stored block: the ones that take time
+inline void thin_starts(const std::vector<unsigned long long> &good, unsigned long long start_bit, uint64_t src_len,
+                        std::vector<unsigned long long> &starts, size_t &heavy) {
+    starts.assign(1, start_bit);                          // (candidates in front of it, or on it, fall to the spacing test)
+    heavy = 1;
+    const unsigned long long spacing = good.size() > kPartsUnthinned ? 8ull * kSpacingBytes : 1ull;
+    for (unsigned long long b62 : good) {
+        const unsigned long long b = b62 & ~(1ull << 62);
+        if (b >= starts.back() + spacing && (b >> 3) + 16 < src_len) {
+            starts.push_back(b);
+            heavy += !(b62 >> 62);
+        }
+    }
+}
+
+// ---- SUBBLOCK: starts inside blocks -------------------------------------------------------------------------------------
+// Guesses go into every gap between two starts found (and behind the last), one every `step` compressed bits.  The sync
+// kernel reads the block at the gap's start (fixed codes, or a dynamic header and its tables) and turns each guess into a
+// symbol boundary B with that identity.  `split_dynamic`: guesses with a dynamic block's tables; `fixed_first` (the stream's
+// first block has fixed codes): every gap that does not begin with fixed codes gets fixed-code guesses as well -- about one
+// bit position in 10^6 of fixed-code data passes F1 + F2 and one byte in 2^23 looks like a stored block's header, and the
+// gap behind such a noise start would otherwise be one long part.
+// `key0` (pieces) is the key of starts[0], which may lie inside a block itself: a key-1 one gets fixed-code guesses, a
+// key-(H + 2) one the tables of the header at H, with the guesses placed behind it.
+// `src` / `src_len`: the regions' own stream (a batch of streams in one launch), or null / 0 for the launch's.
+// Appends to `regions`; `nguess` counts guess slots, two per guess.
+inline void plan_sub_regions(const std::vector<unsigned long long> &starts, unsigned long long end_bit, unsigned long long step,
+                             uint32_t split_dynamic, bool fixed_first, unsigned long long key0, const uint8_t *src,
+                             unsigned long long src_len, std::vector<SubRegionDev> &regions, uint32_t &nguess) {
+    for (size_t i = 0; i < starts.size() && (split_dynamic || fixed_first); ++i) {
+        const unsigned long long s0 = starts[i], e0 = i + 1 < starts.size() ? starts[i + 1] : end_bit;
+        const unsigned long long pieces = (e0 - s0 + step / 2) / step;
+        if (pieces < 2) continue;
+        unsigned long long rs = s0;
+        const unsigned long long spacing = (e0 - s0) / pieces;
+        uint32_t j0 = 0, dyn = split_dynamic, ft = fixed_first ? 1u : 0u;
+        if (i == 0 && key0 == 1u) {                       // (what the sync kernel reads at s0 is no header: fixed guesses)
+            dyn = 0u;
+            ft = 1u;
+        } else if (i == 0 && key0 >= 2u) {                // the region reads the header at H; its guesses begin behind s0
+            rs = key0 - 2u;
+            j0 = (uint32_t)((s0 - rs) / spacing);
+        }
+        // one work item (wavefront) per 64 guesses: a long gap is not one wavefront's serial work
+        for (uint32_t k0 = 0; k0 < (uint32_t)(pieces - 1); k0 += 64u) {
+            const uint32_t n = std::min<uint32_t>(64u, (uint32_t)(pieces - 1) - k0);
+            regions.push_back(SubRegionDev{rs, spacing, nguess, n, dyn, ft, j0 + k0, 0u, src, src_len});
+            nguess += 2u * n;
+        }
+    }
+}
+
+// The sync kernel's answers h_bit / h_key [first, last) (a boundary and its key, or ~0 = none) merged into the stream's
+// starts and keys, sorted and deduplicated.  Returns the number of starts that now lie inside a block (key != 0); they are
+// heavy parts.
+inline size_t merge_sub_starts(std::vector<unsigned long long> &starts, std::vector<unsigned long long> &keys,
+                               const unsigned long long *h_bit, const unsigned long long *h_key, uint32_t first, uint32_t last,
+                               unsigned long long start_bit, uint64_t src_len, size_t &heavy) {
+    std::vector<std::pair<unsigned long long, unsigned long long>> all;
+    all.reserve(starts.size() + (last - first));
+    for (size_t i = 0; i < starts.size(); ++i) all.emplace_back(starts[i], keys[i]);       // (keys[0]: a piece's key0)
+    for (uint32_t g = first; g < last; ++g) {
+        const unsigned long long b = h_bit[g];
+        if (b != ~0ull && b > start_bit && (b >> 3) + 16 < src_len) all.emplace_back(b, h_key[g]);
+    }
+    std::sort(all.begin(), all.end());
+    all.erase(std::unique(all.begin(), all.end()), all.end());
+    starts.clear();
+    keys.clear();
+    size_t inside = 0;
+    for (const auto &a : all) {
+        starts.push_back(a.first);
+        keys.push_back(a.second);
+        inside += a.second != 0;
+    }
+    heavy += inside;
+    return inside;
+}
+
+// ---- slots --------------------------------------------------------------------------------------------------------------
+// what every part's slot gets on top of kSlotRatio symbols per compressed byte, `np` parts in the launch (pieces: the parts'
+// slack together stays within 8 symbols per compressed byte of the largest piece, 4 Ki at least)
+inline uint64_t slot_slack(size_t np, const PiecePass *pp) {
+    return pp ? std::max<uint64_t>(4u << 10, std::min<uint64_t>(kSlotSlack, 8 * pp->q / np))
+              : std::max<uint64_t>(64u << 10, std::min<uint64_t>(kSlotSlack, (2ull << 30) / np));
+}
+// The `n` parts of one stream: part_bytes[i] = its compressed bytes (to the next start, the last one to end_bit),
+// slot_off[i + 1] = slot_off[i] + its slot in symbols (slot_off[0] is the caller's: the stream's first slot).
+inline void slot_caps(const unsigned long long *starts, size_t n, unsigned long long end_bit, uint64_t slack, uint64_t *slot_off,
+                      uint64_t *part_bytes) {
+    for (size_t i = 0; i < n; ++i) {
+        part_bytes[i] = ((i + 1 < n ? starts[i + 1] : end_bit) - starts[i] + 7) >> 3;
+        slot_off[i + 1] = slot_off[i] + ((part_bytes[i] * kSlotRatio + slack + 7) & ~7ull);
+    }
+}
+// a part whose slot was too small (more than kSlotRatio : 1) is run once more with room for deflate's worst case, 1032 : 1
+inline uint64_t retry_cap(uint64_t part_bytes) { return (part_bytes * 1032u + kSlotSlack + 7) & ~7ull; }
+
+// ---- the chain from the stream's first part ---------------------------------------------------------------------------
+// Part 0 is genuine, the part that starts where it ended is therefore genuine too, ...; a candidate that was noise is never
+// reached.  Result words of a part (inflate_streams_kernel<PART>): r[0] symbols, r[1..2] the bit it ended on, r[3] = 1 when
+// that was the end of the BFINAL block, r[4] message, r[5] the farthest a distance reached in front of the part, r[6] the
+// part (index in the launch's tables) that starts where it ended, or ~0.  SUBBLOCK side words: s[0] symbols of the part's
+// first block (~0: it did not end inside the input), s[1..2] the bit that block ended on, s[3] the reach within it, s[4]
+// != 0 when the part handed off inside a block, whose BFINAL is s[5] (2: unknown).  Blocks mode marks: m[0] symbols of the
+// part's complete blocks, m[1..2] where they end, m[3] the reach within them.
+struct Chain {
+    std::vector<PartCopy> copies;                         // the genuine parts in order; gstart / first: group_segments' caller
+    uint64_t produced = 0;
+    unsigned long long end_bit = 0;
+    bool final = false;                                   // the BFINAL block is among what was delivered
+    size_t subparts = 0;                                  // of the parts, those that began inside a block
+    // a failed walk: why, and when it was a part's own result (message, no end), which part of the stream
+    const char *reason = nullptr;
+    size_t bad_part = ~(size_t)0;
+};
+
+// One stream's walk.  res / side / marks / slot_ptr are the launch's tables, the stream's parts are [pbase, pbase + np)
+// of them; starts / keys (SUBBLOCK) are the stream's own.  Modes: `sub` (side words, keys), `blocks` (the input may end
+// inside a block: the chain stops at the first part that ran out of it and keeps that part's complete blocks), `pp` (a
+// piece: see PiecePass; its out fields are set here).  false = irregular (c.reason): the caller decides what that means.
+inline bool walk_chain(const uint32_t *res, const uint32_t *side, const uint32_t *marks, uint16_t *const *slot_ptr, size_t pbase,
+                       size_t np, const unsigned long long *starts, const unsigned long long *keys, uint32_t window_len,
+                       uint64_t src_len, bool sub, bool blocks, PiecePass *pp, Chain &c) {
+    const bool piece = pp && !pp->last;                   // the input ends at the piece's end, not the stream's
+    auto fail = [&](const char *reason) {
+        c.reason = reason;
+        return false;
+    };
+    c.end_bit = starts[0];
+    int fin = pp ? pp->fin0 : -1;                         // SUBBLOCK: BFINAL of the block the current part began inside
+    for (size_t cur = 0;;) {
+        const size_t g = pbase + cur;
+        const uint32_t *r = &res[8 * g], *s = sub ? &side[8 * g] : nullptr;
+        const bool ended = r[3] == 1u;
+        // (pieces: an end behind the piece's input is no end yet -- the next piece decodes that part again)
+        const bool past = piece && sub && s[0] != 0xffffffffu && ((unsigned long long)s[1] | ((unsigned long long)s[2] << 32)) > 8ull * src_len;
+        if (sub && keys[cur] == 1u && fin == 1 && s[0] != 0xffffffffu && !past) {
+            // a fixed-code sub-part inside the FINAL block (its header, read by a part in front, said so): the stream ends
+            // where its first block ended, whatever it decoded behind that
+            c.end_bit = (unsigned long long)s[1] | ((unsigned long long)s[2] << 32);
+            if (c.end_bit > 8ull * src_len) return fail("the final block runs past the input");
+            if ((uint64_t)s[3] > c.produced + window_len) return fail("a distance reaches in front of the stream");
+            if (s[0]) c.copies.push_back(PartCopy{slot_ptr[g], c.produced, 0, s[0], 0u});
+            c.produced += s[0];
+            ++c.subparts;
+            c.final = true;
+            return true;
+        }
+        if (pp) {
+            // pieces: the first part on the chain that ran out of the piece's input is where the next piece begins; so is a
+            // part whose symbols would take the symbol array past its cap (in the last piece too)
+            const bool full = r[4] == kMsgNone && ((c.produced + r[0] + 32768 + 64) * 2 + 64 * (c.copies.size() + 1) + 512 >
+                                                   piece_cap_sym(pp->q));
+            if ((piece && r[4] == kMsgStarved) || full || (past && keys[cur] == 1u && fin == 1)) {
+                if (cur == 0) {
+                    pp->halve = full;
+                    return fail(full ? "the piece's first part needs more scratch than its cap"
+                                     : "no start behind the piece's first is landed on");
+                }
+                pp->stopped = true;
+                pp->next_bit = starts[cur];
+                pp->next_key = sub ? keys[cur] : 0ull;
+                pp->next_fin = fin;
+                c.end_bit = starts[cur];
+                return true;
+            }
+        }
+        if (blocks && r[4] == kMsgStarved) {              // the input ends in this part: its complete blocks, and no more
+            const uint32_t *m = &marks[4 * g];
+            if ((uint64_t)m[3] > c.produced + window_len) return fail("a distance reaches in front of the stream");
+            if (m[0]) c.copies.push_back(PartCopy{slot_ptr[g], c.produced, 0, m[0], 0u});
+            c.produced += m[0];
+            c.end_bit = (unsigned long long)m[1] | ((unsigned long long)m[2] << 32);
+            return true;
+        }
+        if (r[4] != kMsgNone || !(ended || r[6] != 0xffffffffu)) {                // error / truncation on the chain
+            c.bad_part = cur;
+            return fail("a part's message, or no end");
+        }
+        if ((uint64_t)r[5] > c.produced + window_len) return fail("a distance reaches in front of the stream");
+        c.copies.push_back(PartCopy{slot_ptr[g], c.produced, 0, r[0], 0u});
+        c.produced += r[0];
+        c.end_bit = (unsigned long long)r[1] | ((unsigned long long)r[2] << 32);
+        if (ended) {
+            c.final = true;
+            return true;
+        }
+        if (sub) {
+            c.subparts += keys[cur] != 0;
+            // handed off inside a block: the next part starts there and learns that block's BFINAL from here (2: this part
+            // did not know it either -- a fixed-code sub-part still in its first block -- so it stays what it was)
+            if (s[4]) fin = s[5] == 2u ? fin : (int)s[5];
+            else fin = -1;
+        }
+        // a part ends on a LATER start of its own stream (so a bad word cannot send the walk round in a circle)
+        if (r[6] <= g || r[6] >= pbase + np) return fail("bad chain link");
+        cur = r[6] - pbase;
+    }
+}
+
+// Segments for the context chain: consecutive parts until kSegmentBytes of output are together; what is left at the end
+// joins the last segment unless it is a segment's worth (32 KiB) itself (only the stream's LAST segment may be short).
+// Returns the index in `copies` of every segment's first part, and copies.size() behind them.
+inline std::vector<size_t> group_segments(const std::vector<PartCopy> &copies, uint64_t produced) {
+    std::vector<size_t> seg_first;
+    size_t first = 0;
+    for (size_t c = 0; c < copies.size(); ++c) {
+        if (copies[c].dst + copies[c].n - copies[first].dst >= kSegmentBytes || c + 1 == copies.size()) {
+            seg_first.push_back(first);
+            first = c + 1;
+        }
+    }
+    if (seg_first.size() > 1 && produced - copies[seg_first.back()].dst < 32768u) seg_first.pop_back();
+    seg_first.push_back(copies.size());
+    return seg_first;
+}
+
+}  // namespace zr
