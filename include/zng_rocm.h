@@ -568,7 +568,7 @@ int  zng_rocm_uncompress_streams_dev(int format, const zng_rocm_inflate_dev_job 
  * one small readback; the raw engine on the payloads; the check values of all outputs in one many-message pass over 512 KiB
  * sub-messages folded per member on the device (the single call: the full-grid checksum kernel over its one output); one
  * small kernel compares the trailers (inflate.c:1105-1147).  Only the FIRST member of a multi-member gzip file is decoded;
- * in_used is where the next one starts.  The header kernel and the checksum pass fetch aligned 16-byte lines: up to 15 bytes
+ * in_used is where the next one starts (every member: zng_rocm_gunzip_members_dev).  The header kernel and the checksum pass fetch aligned 16-byte lines: up to 15 bytes
  * on either side of a member, a dictionary or an output, inside the same 16-byte line, are read (never used).
  * Per job (batch) or per call (single; the text of a data error then in zng_rocm_last_error()):
  *   member complete, check value and length agree   status 1, out_len, in_used = header + payload + trailer (4 / 8 bytes)
@@ -600,6 +600,63 @@ typedef struct zng_rocm_wrapper_info {
     uint32_t fdict;        /* 1 when the zlib header announces a preset dictionary */
 } zng_rocm_wrapper_info;
 int  zng_rocm_wrapper_parse(int format, const uint8_t *src, size_t src_len, zng_rocm_wrapper_info *info, const char **msg);
+
+/* EVERY member of a gzip file that sits in device memory, BGZF (bgzip, BAM, tabix) included: what gzread does with a file
+ * of several members -- gz_look (gzread.c.in:81-154) starts a new member whenever 1f 8b follows a finished one and ignores
+ * anything else as trailing garbage, gz_decomp (:161-207) inflates each -- for a file that is all in memory, in place of the
+ * caller's loop over zng_rocm_uncompress_large_dev(2, ...) along in_used.  The plaintexts land in d_dst one behind the other
+ * in file order.
+ * What happens: one pass over the file marks every position that holds 1f 8b 08 F with F & 0xe0 == 0 (a candidate: the
+ * bytes every accepted header begins with, inflate.c:556-567); the header kernel of the wrapped large calls judges every
+ * candidate; a BGZF 'BC' subfield (SI1 66, SI2 67, SLEN 2: BSIZE = member bytes - 1) says where its member ends, any other
+ * member is guessed to reach the next candidate, and the eight bytes in front of the guessed end are its guessed CRC-32 and
+ * ISIZE.  Discovery synchronises twice: the candidates' number comes down (4 bytes: it sizes the tables), then the candidate
+ * table, once, 40 bytes per candidate; every plan that holds members of the one-wavefront engine reads their results back
+ * (16 bytes each), and the large batch synchronises as zng_rocm_uncompress_large_streams_dev does.  What a file made to hurt
+ * can cost is bounded: the header kernel is shown at most 4 KiB of a candidate (a header that does not end inside them --
+ * legal: FEXTRA alone can be 64 KiB -- counts as cut, and its member is decoded alone by the single call, with the same
+ * results), and a file with more than 2^24 candidates gets no table: it goes through single calls, member by member, and
+ * zng_rocm_gunzip_last_candidates() says -1.  From candidate 0 the host follows the guesses: members below 128 KiB go to
+ * zng_rocm_uncompress_streams_dev in one launch (one wavefront each), the others to zng_rocm_uncompress_large_streams_dev,
+ * every one with exactly its guessed ISIZE as capacity.  A member counts when it decoded with status 1 (so check value and
+ * length agree), consumed exactly its guessed bytes and produced exactly its guessed length, and every member in front of it
+ * counts.  The first one that does not (a candidate inside its data that was no member, an ISIZE that wrapped at 4 GiB) is
+ * decoded alone by zng_rocm_uncompress_large_dev(2, ...) where it really belongs, and the plan is made again from where it
+ * really ended: a re-plan; after 8 of them the rest of the file goes through single calls.  A candidate that was no member
+ * never contributes a byte to d_dst[0, *out_len) or a row to `members` (bytes of d_dst behind *out_len, inside dst_cap, may
+ * have been written).
+ * Results (gz_look / gz_decomp):
+ *   the first member   judged exactly as zng_rocm_uncompress_large_dev(2, ...) judges it: status, text in
+ *                      zng_rocm_last_error(), *out_len, *in_used; src_len == 0 included
+ *   behind a complete member   fewer than 2 bytes, or two bytes other than 1f 8b: trailing garbage (gz_look asks avail_in > 1,
+ *                      gzread.c.in:127), the call returns 1 with *in_used = the end of the last member
+ *                      1f 8b: a member that has to decode; a header refusal, data error or check mismatch returns -3 with the
+ *                      reference's text, a truncated member -5
+ *   on failure         *out_len = the plaintext of the complete members in front + what the failing member's own call
+ *                      reports, *in_used = its offset + its in_used, *nmembers = the complete members in front
+ *   dst_cap            nothing is written at or behind d_dst + dst_cap; a file that does not fit returns -5
+ * Empty members (ISIZE 0, the BGZF end-of-file block) are members; members of 4 GiB and more work (the pieces engine).
+ * `members` (NULL when members_cap is 0) receives one row per complete member, the first members_cap of them; *nmembers is
+ * always the true count.  flags: 0 or ZNG_ROCM_INFLATE_SUBBLOCK, passed to the large engine.  Unknown flag bits, a null buffer
+ * with a non-zero length or a null result pointer return ZNG_ROCM_EINVAL with nothing launched or written and *out_len =
+ * *in_used = *nmembers = 0.  The scan and the header kernel fetch aligned 16-byte lines: up to 15 bytes on either side of the
+ * file inside the same line are read (never used).  Synchronous. */
+typedef struct zng_rocm_gzip_member {
+    uint64_t src_off, src_len;   /* the member in d_src, header and trailer included */
+    uint64_t dst_off, out_len;   /* its plaintext in d_dst */
+    uint32_t crc;                /* CRC-32 of that plaintext (the trailer's, verified) */
+    uint32_t bgzf;               /* 1: the header carried a BGZF 'BC' subfield */
+} zng_rocm_gzip_member;
+int  zng_rocm_gunzip_members_dev(const uint8_t *d_src, size_t src_len, uint8_t *d_dst, size_t dst_cap, uint64_t *out_len,
+                                 size_t *in_used, zng_rocm_gzip_member *members, size_t members_cap, size_t *nmembers,
+                                 uint32_t flags, void *stream);
+/* of the calling thread's last zng_rocm_gunzip_members_dev call (thread-local, like the other last_* counters): candidates
+ * the scan found, re-plans, members the one-wavefront engine decoded, members the large engines decoded (the batch, and the
+ * single call for a member decoded alone) */
+int  zng_rocm_gunzip_last_candidates(void);
+int  zng_rocm_gunzip_last_replans(void);
+int  zng_rocm_gunzip_last_small(void);
+int  zng_rocm_gunzip_last_large(void);
 
 /* ONE raw stream with its host decode spread over `nthreads` threads (zng_rocm_inflate_tokens_decode_threads) and one
  * device pass; same results and status as zng_rocm_inflate_raw_window, which it falls back to for streams that

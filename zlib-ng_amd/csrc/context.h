@@ -83,6 +83,9 @@ enum ScratchSlot {
     kScrFrameLargeHost,     // pinned: the same tables on their way up and down
     kScrCheckCut,           // device: messages | first rows | descriptors, partials and checks of the sub-messages
                             //   (zng_rocm_checksums_cut_dev)
+    kScrMembersScan,        // device: candidate bitmap | per-tile counts | per-tile offsets of zng_rocm_gunzip_members_dev
+    kScrMembersTab,         // device: positions | header jobs, rows and work | candidate table | the small engine's results
+    kScrMembersHost,        // pinned: the candidate table and the small engine's results on their way down
     kScrCount
 };
 

@@ -22,6 +22,7 @@
 
 #include "checksum_args.h"
 #include "context.h"
+#include "framing_large.h"
 #include "framing_parse.h"
 #include "inflate_large_limits.h"
 #include "gf2.h"
@@ -40,11 +41,6 @@ constexpr uint64_t kSubBytes = 512ull << 10;
 // seeds chained through a device word; tests lower it (zng_rocm_debug_uncompress_large_chunk) to reach the chaining
 static uint64_t g_whole_chunk = 8ull << 30;
 constexpr int kCutJobs = 64;                             // messages per launch of large_cut_kernel (they travel as kernel arguments)
-
-struct HeadJob {
-    const uint8_t *src;
-    uint64_t len;
-};
 
 struct TrailJob {
     const uint8_t *src;
@@ -268,10 +264,35 @@ uint32_t host_crc32(const uint8_t *p, size_t n) {
 
 size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
+}  // namespace
+
+// framing_large.h: the header kernels over jobs that already sit in device memory
+size_t header_rows_scratch(size_t n) {
+    return up16(n * sizeof(StreamArgs)) + up16(n * sizeof(FinalArgs)) + n * sizeof(Partial) + n * 2 * sizeof(uint32_t);
+}
+
+int header_rows_device(int format, const HeadJob *d_jobs, size_t n, WrapperHead *d_rows, uint8_t *d_work, hipStream_t st) {
+    Context *c = ctx();
+    const size_t o_fa = up16(n * sizeof(StreamArgs)), o_part = o_fa + up16(n * sizeof(FinalArgs)), o_crc = o_part + n * sizeof(Partial);
+    StreamArgs *d_sa = reinterpret_cast<StreamArgs *>(d_work);
+    FinalArgs *d_fa = reinterpret_cast<FinalArgs *>(d_work + o_fa);
+    hipLaunchKernelGGL(large_header_kernel, dim3((unsigned)n), dim3(64), 0, st, d_jobs, (uint32_t)n, format, c->tables, d_rows, d_sa, d_fa);
+    ZR_HIP(hipGetLastError());
+    if (format == 2) {
+        uint32_t *d_crc = reinterpret_cast<uint32_t *>(d_work + o_crc);
+        if (int rc = launch_checksum_batch_device(false, true, d_sa, d_fa, reinterpret_cast<Partial *>(d_work + o_part), n, d_crc, st))
+            return rc;
+        hipLaunchKernelGGL(large_hcrc_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_rows, d_crc, (uint32_t)n);
+        ZR_HIP(hipGetLastError());
+    }
+    return ZNG_ROCM_OK;
+}
+
+namespace {
+
 // Every header parsed on the device and, for zlib, the Adler-32 of every dictionary given; one readback.
 int header_phase(int format, const zng_rocm_inflate_large_job *jobs, size_t n, Workspace *ws, hipStream_t st,
                  std::vector<WrapperHead> &rows, std::vector<uint32_t> &dict_adler) {
-    Context *c = ctx();
     std::vector<zng_rocm_check_job> dj;
     std::vector<size_t> dj_of;
     if (format == 1)
@@ -282,9 +303,8 @@ int header_phase(int format, const zng_rocm_inflate_large_job *jobs, size_t n, W
             }
     const size_t nd = dj.size();
     const size_t o_dict = n * sizeof(WrapperHead), down = o_dict + nd * 2 * sizeof(uint32_t);
-    const size_t o_jobs = up16(down), o_sa = o_jobs + n * sizeof(HeadJob), o_fa = up16(o_sa + n * sizeof(StreamArgs));
-    const size_t o_part = up16(o_fa + n * sizeof(FinalArgs)), o_crc = o_part + n * sizeof(Partial);
-    const size_t total = o_crc + n * 2 * sizeof(uint32_t), h_down = up16(n * sizeof(HeadJob));
+    const size_t o_jobs = up16(down), o_work = up16(o_jobs + n * sizeof(HeadJob));
+    const size_t total = o_work + header_rows_scratch(n), h_down = up16(n * sizeof(HeadJob));
     uint8_t *d = nullptr, *h = nullptr;
     {
         std::lock_guard<std::mutex> use(ws->mu);
@@ -295,19 +315,9 @@ int header_phase(int format, const zng_rocm_inflate_large_job *jobs, size_t n, W
         for (size_t i = 0; i < n; ++i) hj[i] = HeadJob{jobs[i].d_src, jobs[i].src_len};
         ZR_HIP(hipMemcpyAsync(d + o_jobs, h, n * sizeof(HeadJob), hipMemcpyHostToDevice, st));
         if (int rc = host_tables_release(ws, st)) return rc;
-        WrapperHead *d_rows = reinterpret_cast<WrapperHead *>(d);
-        StreamArgs *d_sa = reinterpret_cast<StreamArgs *>(d + o_sa);
-        FinalArgs *d_fa = reinterpret_cast<FinalArgs *>(d + o_fa);
-        hipLaunchKernelGGL(large_header_kernel, dim3((unsigned)n), dim3(64), 0, st, reinterpret_cast<const HeadJob *>(d + o_jobs),
-                           (uint32_t)n, format, c->tables, d_rows, d_sa, d_fa);
-        ZR_HIP(hipGetLastError());
-        if (format == 2) {
-            uint32_t *d_crc = reinterpret_cast<uint32_t *>(d + o_crc);
-            if (int rc = launch_checksum_batch_device(false, true, d_sa, d_fa, reinterpret_cast<Partial *>(d + o_part), n, d_crc, st))
-                return rc;
-            hipLaunchKernelGGL(large_hcrc_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_rows, d_crc, (uint32_t)n);
-            ZR_HIP(hipGetLastError());
-        }
+        if (int rc = header_rows_device(format, reinterpret_cast<const HeadJob *>(d + o_jobs), n, reinterpret_cast<WrapperHead *>(d),
+                                        d + o_work, st))
+            return rc;
     }
     if (nd)                                              // takes the stream's workspace itself
         if (int rc = zng_rocm_checksums_dev(1, dj.data(), nd, reinterpret_cast<uint32_t *>(d + o_dict), st)) return rc;

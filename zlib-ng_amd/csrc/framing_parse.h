@@ -93,4 +93,29 @@ ZR_HD WrapperHead wrapper_parse_rules(int format, const Bytes &in, uint64_t n) {
     return h;
 }
 
+// BGZF (the blocked gzip of bgzip / BAM / tabix, SAM specification 4.1): every member carries the FEXTRA subfield SI1 66 'B',
+// SI2 67 'C', SLEN 2 whose 16 bits are BSIZE = the member's bytes - 1, header and trailer included.  The subfields of the
+// FEXTRA field (RFC 1952 2.3.1.1: SI1 SI2 SLEN and SLEN bytes, one behind the other inside the XLEN bytes at 12) are walked
+// in order, for host and device alike: the first 'BC' subfield with SLEN 2 is the answer, one with any other SLEN is a
+// subfield like any other, and a subfield that XLEN cuts short ends the walk with no answer.  gz_look (gzread.c.in:81-154)
+// does not look into the field at all -- inflate skips it, inflate.c:599-641 -- so BSIZE is a hint to the member finder
+// (gzip_members.hip) and never decides what a member is.  `n`: bytes of the member that exist; false when they end
+// inside the field or the header has none.
+template <class Bytes>
+ZR_HD bool gzip_bgzf_bsize(const Bytes &in, uint64_t n, uint32_t *bsize) {
+    if (n < 12 || !(in.byte(3) & 4u)) return false;
+    const uint64_t end = 12u + (in.byte(10) | (in.byte(11) << 8));
+    if (end > n) return false;
+    for (uint64_t p = 12; p + 4 <= end;) {
+        const uint32_t si1 = in.byte(p), si2 = in.byte(p + 1), slen = in.byte(p + 2) | (in.byte(p + 3) << 8);
+        if (p + 4 + slen > end) return false;
+        if (si1 == 66u && si2 == 67u && slen == 2u) {
+            *bsize = in.byte(p + 4) | (in.byte(p + 5) << 8);
+            return true;
+        }
+        p += 4u + slen;
+    }
+    return false;
+}
+
 }  // namespace zr

@@ -400,3 +400,35 @@ def uncompress_large_dev(fmt, src_dev, dst, dict=None, piece_bytes=0, stream=Non
                                            int(piece_bytes), fl, rocm._stream_ptr(stream))
     return (st, int(out_len.value), int(in_used.value), int(lib.zng_rocm_inflate_large_last_parts()),
             int(lib.zng_rocm_inflate_large_last_pieces()), int(lib.zng_rocm_inflate_large_last_host_bytes()))
+
+
+class GzipMember(C.Structure):
+    """zng_rocm_gzip_member"""
+    _fields_ = [("src_off", C.c_uint64), ("src_len", C.c_uint64), ("dst_off", C.c_uint64), ("out_len", C.c_uint64),
+                ("crc", C.c_uint32), ("bgzf", C.c_uint32)]
+
+
+def gunzip_members_dev(src_dev, dst, members_cap=None, stream=None, subblock=False, flags=None):
+    """zng_rocm_gunzip_members_dev: EVERY member of a gzip file that is already in device memory (`src_dev`: uint8 CUDA tensor;
+    concatenated members, BGZF), plaintexts one behind the other in the CUDA tensor `dst`.  `members_cap`: rows of the member
+    table to take (None = all: room for src_len / 18 + 1 rows, the most a file can hold, is reserved as address space -- a numpy
+    array that is not initialised, so only the rows the call writes cost memory).  Returns
+    (status, bytes produced, file bytes used, members, nmembers, counters) with members = [(src_off, src_len, dst_off,
+    out_len, crc, bgzf)] and counters = {"candidates", "replans", "small", "large"} (zng_rocm_gunzip_last_*)."""
+    import numpy as np
+    rocm._need_init()
+    lib = rocm.lib()
+    n = int(src_dev.numel())
+    cap = n // 18 + 1 if members_cap is None else int(members_cap)
+    table = np.empty(max(cap, 1) * C.sizeof(GzipMember), dtype=np.uint8)
+    out_len, in_used, nmembers = C.c_uint64(0), C.c_size_t(0), C.c_size_t(0)
+    fl = (SUBBLOCK if subblock else 0) if flags is None else int(flags)
+    st = lib.zng_rocm_gunzip_members_dev(rocm._dev_ptr(src_dev) if n else None, n, rocm._dev_ptr(dst) if dst.numel() else None,
+                                         int(dst.numel()), C.byref(out_len), C.byref(in_used),
+                                         C.c_void_p(table.ctypes.data) if cap else None, cap, C.byref(nmembers), fl,
+                                         rocm._stream_ptr(stream))
+    rows = [(int(m.src_off), int(m.src_len), int(m.dst_off), int(m.out_len), int(m.crc), int(m.bgzf))
+            for m in (GzipMember * min(cap, int(nmembers.value))).from_buffer(table)]
+    counters = {"candidates": int(lib.zng_rocm_gunzip_last_candidates()), "replans": int(lib.zng_rocm_gunzip_last_replans()),
+                "small": int(lib.zng_rocm_gunzip_last_small()), "large": int(lib.zng_rocm_gunzip_last_large())}
+    return st, int(out_len.value), int(in_used.value), rows, int(nmembers.value), counters
