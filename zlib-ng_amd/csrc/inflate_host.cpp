@@ -406,10 +406,10 @@ int decode_stream(const uint8_t *src, size_t src_len, uint64_t window_len, zng_r
                 if (sym == 16) {
                     if (!b.need(e.bits + 2u)) STARVE();
                     b.drop(e.bits);
+                    rep = 3 + b.peek(2);
+                    b.drop(2);                      // (inflate.c:856-859 has the two bits in hand before it refuses the code: in_used counts their byte)
                     if (have == 0) FAIL("invalid bit length repeat");
                     val = lens[have - 1];
-                    rep = 3 + b.peek(2);
-                    b.drop(2);
                 } else if (sym == 17) {
                     if (!b.need(e.bits + 3u)) STARVE();
                     b.drop(e.bits);
@@ -460,7 +460,10 @@ int decode_stream(const uint8_t *src, size_t src_len, uint64_t window_len, zng_r
                 }
                 continue;
             }
-            if (e.kind & K_BAD) FAIL("invalid literal/length code");
+            if (e.kind & K_BAD) {
+                b.drop(e.bits);                     // (the code is taken before it is refused, inflate.c:958-981: in_used counts it)
+                FAIL("invalid literal/length code");
+            }
             if (e.kind & K_EOB) {
                 b.drop(e.bits);
                 break;
@@ -534,6 +537,8 @@ done:
     }
     t->out_len = o.out_pos;
     t->in_used = (size_t)(b.next - src) - (b.cnt >> 3);
+    // (input ran out: the reference has taken every byte it was given before it asks for more -- NEEDBITS / PULLBYTE, inflate.c)
+    if (t->status == Z_BUF_ERROR_) t->in_used = src_len;
     if (blocks && t->status != Z_STREAM_END_) t->in_used = (size_t)(mark.bit >> 3);
     if (ctl) {
         ctl->end_bit = 8ull * (uint64_t)(b.next - src) - b.cnt;
