@@ -658,6 +658,53 @@ int  zng_rocm_gunzip_last_replans(void);
 int  zng_rocm_gunzip_last_small(void);
 int  zng_rocm_gunzip_last_large(void);
 
+/* The write side of the call above: device-resident plaintext -> a BGZF file in device memory (SAM specification 4.1; what
+ * bgzip, BAM and tabix read), nothing crossing PCIe.  d_src[0, src_len) is cut every block_bytes bytes (0 = 65280; 1 .. 65280,
+ * anything above is ZNG_ROCM_EINVAL); piece i becomes member i, the members stand one behind the other from d_dst[0] at byte
+ * granularity; neither buffer has an alignment requirement.
+ *   a member    1f 8b 08 04 00 00 00 00 00 ff 06 00 42 43 02 00 <BSIZE lo> <BSIZE hi> (htslib's header at every level; BSIZE =
+ *               the member's bytes - 1) | raw deflate of the piece, no history, one final stream | CRC-32 of the piece |
+ *               its length, both least significant byte first
+ *   the end     unless ZNG_ROCM_BGZF_NO_EOF is set, the 28 constant bytes of the end-of-file block (an empty member); src_len
+ *               == 0 gives exactly those 28 bytes, with NO_EOF nothing at all
+ *   level       as zng_rocm_compress2_dev: -1 = 6; 1..9 the engine of zng_rocm_deflate_streams_dev, every piece an independent
+ *               stream; 0 = every member one stored block (no engine is launched); with ZNG_ROCM_BGZF_QUICK (level must be 1)
+ *               the payloads come from the engine of zng_rocm_deflate_quick_dev
+ *   64 KiB      a piece of n bytes whose engine output has clen bytes with clen > n + 5 or clen > 65510 gets one final stored
+ *               block (01 LEN NLEN and the n bytes) as its payload instead -- decided on the device from the engine's own
+ *               length; zng_rocm_bgzf_last_stored() counts these members (at level 0: every member).  So a member is at most
+ *               n + 31 bytes and at most 65536, and zng_rocm_bgzf_bound(src_len, block_bytes) = src_len + 31 per member + 28
+ *               bounds the file (0 for a block_bytes the call refuses)
+ *   dst_cap     need not reach the bound: every member's place is known on the device before a byte of it is written, nothing
+ *               is stored at or behind d_dst + dst_cap, and a file that does not fit returns -5 (Z_BUF_ERROR) with *out_len =
+ *               the bytes it needs (and *nmembers, `members` as on success); d_dst[0, dst_cap) then holds the file's beginning
+ *   members     (NULL when members_cap is 0) the first members_cap rows, in the meaning zng_rocm_gunzip_members_dev gives the
+ *               struct -- src_off / src_len the member inside the BGZF file, dst_off / out_len its plaintext range, crc, bgzf 1;
+ *               the end-of-file block is a row with out_len 0 -- exactly the rows that call reports for the file: the content
+ *               of a .gzi index and of virtual offsets.  *nmembers is always the true count
+ *   rounds      scratch is bounded: the pieces go through the device in rounds of at most round_bytes of plaintext (0 = 1 GiB
+ *               + 65280; rounded down to whole pieces, at least one), the running file offset carried on the device from
+ *               round to round; zng_rocm_bgzf_last_rounds() says how many there were
+ * Per round: the CRC-32 of every piece in one many-message pass (the kernels of zng_rocm_checksums_dev), the engine, one
+ * workgroup that turns the engine's lengths into member sizes and scans them, one kernel that writes every header and trailer
+ * and moves every payload to its byte (levels 1..9: straight from the engine's block slots; stored members: from the
+ * plaintext).  Synchronous, one host
+ * synchronisation for the whole call; the members table comes down only when members_cap > 0.  The checksum pass fetches
+ * aligned 16-byte lines: up to 15 bytes on either side of the plaintext inside the same line are read (never used).
+ * Returns 0, -5, or ZNG_ROCM_EINVAL -- unknown flag bits, a level outside -1..9, QUICK with a level other than 1, block_bytes
+ * above 65280, a null buffer with a non-zero length or capacity, a null out_len or nmembers -- with nothing launched or
+ * written and *out_len = *nmembers = 0.  The two counters are thread-local, like the other last_* counters. */
+#define ZNG_ROCM_BGZF_BLOCK   65280u      /* htslib's BGZF_BLOCK_SIZE: the most plaintext one member takes */
+#define ZNG_ROCM_BGZF_NO_EOF  1u          /* do not append the 28-byte end-of-file block (the caller appends more) */
+#define ZNG_ROCM_BGZF_QUICK   2u          /* the level-1 CLASS (zng_rocm_deflate_quick_dev: static Huffman, one kernel); level must be 1 */
+size_t zng_rocm_bgzf_bound(size_t src_len, uint32_t block_bytes);
+int    zng_rocm_bgzf_compress_dev(int level, const uint8_t *d_src, size_t src_len, uint32_t block_bytes,
+                                  uint8_t *d_dst, size_t dst_cap, uint64_t *out_len,
+                                  zng_rocm_gzip_member *members, size_t members_cap, size_t *nmembers,
+                                  size_t round_bytes, uint32_t flags, void *stream);
+int    zng_rocm_bgzf_last_rounds(void);
+int    zng_rocm_bgzf_last_stored(void);
+
 /* ONE raw stream with its host decode spread over `nthreads` threads (zng_rocm_inflate_tokens_decode_threads) and one
  * device pass; same results and status as zng_rocm_inflate_raw_window, which it falls back to for streams that
  * offer no block boundary to cut at or turn out irregular.  Synchronous. */

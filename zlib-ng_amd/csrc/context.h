@@ -86,6 +86,9 @@ enum ScratchSlot {
     kScrMembersScan,        // device: candidate bitmap | per-tile counts | per-tile offsets of zng_rocm_gunzip_members_dev
     kScrMembersTab,         // device: positions | header jobs, rows and work | candidate table | the small engine's results
     kScrMembersHost,        // pinned: the candidate table and the small engine's results on their way down
+    kScrBgzf,               // device: state | member rows | member offsets | checks | payload sizes | the level-1 class's
+                            //   results and its buffer per piece (zng_rocm_bgzf_compress_dev)
+    kScrBgzfHost,           // pinned: the state on its way down
     kScrCount
 };
 

@@ -1,0 +1,48 @@
+// deflate_blocks.h -- what the rows engine (deflate_dyn.hip: lz_rows_kernel, emit_dynamic_kernel, segments_scan_kernel) leaves
+// on the device for a caller that places the blocks itself instead of having gather_segments_kernel pack them into one buffer
+// per stream: the BGZF writer (bgzf.hip) moves every block from its slot straight to its byte in the file.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/zng_rocm.h"
+
+namespace zr {
+
+struct Workspace;
+
+// one BLOCK of the output (K2 .. K4): the tokens of its segment that start in [blo, bhi)
+struct BlkJob {
+    const uint8_t *in;        // stream base (position 0)
+    uint8_t       *out;       // this block's output slot (4-byte aligned)
+    uint8_t       *dst;       // the stream's output buffer (what K4 packs into)
+    uint64_t       dst_cap;
+    uint64_t       bm_off, d16_off;       // its segment's token scratch
+    uint32_t       seg_start, seg_end;    // its segment
+    uint32_t       blo, bhi;
+    uint32_t       hist_idx, hist_prev;   // histogram snapshot of this block's end; 1 if the snapshot before it is the block's begin
+    uint32_t       out_cap;
+    uint32_t       is_last;               // the block that carries BFINAL
+    uint32_t       first_seg;             // index of the first BLOCK of this block's stream
+    uint32_t       stream;                // row of the per-stream result table; 0x80000000 set on the stream's last block
+};
+
+// The blocks of one round, still in their slots (scratch of the workspace: valid until the next call on the same HIP stream
+// that uses the rows engine).  Block k belongs to stream blk[k].stream & 0x7fffffff, holds seg_len[k] bytes at blk[k].out and
+// begins at byte in_stream[k] of its stream's deflate data; sizes[2 * s] is the whole length of stream s.
+struct RowsBlocks {
+    const BlkJob             *blk;
+    const uint32_t           *seg_len;
+    const unsigned long long *in_stream;
+    const unsigned long long *sizes;
+    size_t                    nblk;
+};
+
+// Levels 1..9 over `njobs` independent streams (in / in_len / dict_len / flags of each job; out and out_cap are not looked at),
+// every stream short enough for one segment: matcher, emitter and the scan, no packing, nothing copied to the host.
+// Asynchronous on `st`; the caller holds ws->mu.
+int deflate_rows_enqueue_blocks(int level, const zng_rocm_stream_job *sjobs, size_t njobs, Workspace *ws, hipStream_t st,
+                                RowsBlocks *blocks);
+
+}  // namespace zr

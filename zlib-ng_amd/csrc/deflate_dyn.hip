@@ -25,6 +25,7 @@
 // else static if not larger than dynamic.  Not bit-identical to the reference's stream (different parse, one block
 // per segment); validity is defined by round trip, as in the reference's own tests.
 #include "context.h"
+#include "deflate_blocks.h"
 #include "deflate_dev.h"
 #include "deflate_rows.h"
 
@@ -46,21 +47,7 @@ struct SegJob {
     uint32_t       stream;      // row of the per-stream result table; 0x80000000 set on the stream's last segment
 };
 
-// one BLOCK of the output (K2 .. K4): the tokens of its segment that start in [blo, bhi)
-struct BlkJob {
-    const uint8_t *in;        // stream base (position 0)
-    uint8_t       *out;       // this block's output slot (4-byte aligned)
-    uint8_t       *dst;       // the stream's output buffer (what K4 packs into)
-    uint64_t       dst_cap;
-    uint64_t       bm_off, d16_off;       // its segment's token scratch
-    uint32_t       seg_start, seg_end;    // its segment
-    uint32_t       blo, bhi;
-    uint32_t       hist_idx, hist_prev;   // histogram snapshot of this block's end; 1 if the snapshot before it is the block's begin
-    uint32_t       out_cap;
-    uint32_t       is_last;               // the block that carries BFINAL
-    uint32_t       first_seg;             // index of the first BLOCK of this block's stream
-    uint32_t       stream;                // row of the per-stream result table; 0x80000000 set on the stream's last block
-};
+// BlkJob, one BLOCK of the output (K2 .. K4: the tokens of its segment that start in [blo, bhi)): deflate_blocks.h
 
 constexpr uint32_t kSegBytes = 512u << 10;     // plaintext per segment / per dynamic block: the largest, and ...
 constexpr uint32_t kSegBytesMin = 128u << 10;  // ... the smallest.  A segment is one workgroup and one CU holds one
@@ -863,9 +850,11 @@ constexpr int kZHuffmanOnly = 2, kZRle = 3, kZFixed = 4;
 // The launches of one round: `njobs` streams, all their segments in one job list.  Asynchronous on `st`; *results =
 // pinned host words {compressed size, does-not-fit flag} per stream, valid once the stream has been synchronised.
 // cap_override: out_cap of job 0 when the caller's job struct cannot hold it (a single stream of >= 4 GiB of room).
+// keep: the caller places the blocks itself (deflate_blocks.h) -- K4 and the copy of the results are left out, *keep says where
+// the blocks are, and no job's out / out_cap is looked at.
 static int deflate_rows_enqueue(int level, int strategy, const zng_rocm_stream_job *sjobs, size_t njobs, const size_t *cap_override,
                                 uint32_t seg_bytes, Workspace *ws, hipStream_t st, unsigned long long **results,
-                                unsigned long long *d_results_copy = nullptr) {
+                                unsigned long long *d_results_copy = nullptr, RowsBlocks *keep = nullptr) {
     size_t nseg = 0;
     for (size_t s = 0; s < njobs; ++s) nseg += sjobs[s].in_len ? ((size_t)sjobs[s].in_len + seg_bytes - 1) / seg_bytes : 1;
     const size_t max_blk = nseg * kMaxSub;
@@ -926,7 +915,7 @@ static int deflate_rows_enqueue(int level, int strategy, const zng_rocm_stream_j
                 BlkJob &q = blk[nb++];
                 q.in = jobs[k].in;
                 q.dst = (uint8_t *)j.out;
-                q.dst_cap = cap_override && s == 0 ? *cap_override : j.out_cap;
+                q.dst_cap = keep ? ~0ull : (cap_override && s == 0 ? *cap_override : j.out_cap);
                 q.bm_off = bm_total;
                 q.d16_off = d16_total;
                 q.seg_start = a;
@@ -974,6 +963,10 @@ static int deflate_rows_enqueue(int level, int strategy, const zng_rocm_stream_j
     ZR_HIP(hipGetLastError());
     hipLaunchKernelGGL(segments_scan_kernel, dim3(1), dim3(1024), 0, st, d_blk, d_seg_len, (uint32_t)nb, d_excl, d_dst_off, d_res);
     ZR_HIP(hipGetLastError());
+    if (keep) {
+        *keep = RowsBlocks{d_blk, d_seg_len, d_dst_off, d_res, nb};
+        return host_tables_release(ws, st);
+    }
     hipLaunchKernelGGL(gather_segments_kernel, dim3(njobs > 64 ? 2 : 4, (unsigned)nb), dim3(256), 0, st, d_blk, d_seg_len, d_dst_off);
     ZR_HIP(hipGetLastError());
     if (d_results_copy)
@@ -983,6 +976,12 @@ static int deflate_rows_enqueue(int level, int strategy, const zng_rocm_stream_j
     if (int rc = host_tables_release(ws, st)) return rc;
     *results = h_res;
     return ZNG_ROCM_OK;
+}
+
+int deflate_rows_enqueue_blocks(int level, const zng_rocm_stream_job *sjobs, size_t njobs, Workspace *ws, hipStream_t st,
+                                RowsBlocks *blocks) {
+    unsigned long long *unused = nullptr;
+    return deflate_rows_enqueue(level, 0, sjobs, njobs, nullptr, kSegBytesMin, ws, st, &unused, nullptr, blocks);
 }
 
 }  // namespace zr

@@ -189,3 +189,37 @@ def deflate_async_dev(src, dst, result, level=6, length=None, offset=0, stream=N
     rocm._check(rocm.lib().zng_rocm_deflate_async_dev(level, rocm._dev_ptr(src, offset), n, dict_len, flags, rocm._dev_ptr(dst),
                                                       dst.numel(), rocm._dev_ptr(result), rocm._stream_ptr(stream)),
                 "zng_rocm_deflate_async_dev")
+
+
+BGZF_BLOCK, BGZF_NO_EOF, BGZF_QUICK = 65280, 1, 2
+
+
+def bgzf_bound(n, block_bytes=0):
+    return rocm.lib().zng_rocm_bgzf_bound(int(n), int(block_bytes))
+
+
+def bgzf_compress_dev(src_dev, dst, level=-1, block_bytes=0, members_cap=None, round_bytes=0, no_eof=False, quick=False,
+                      flags=None, stream=None):
+    """zng_rocm_bgzf_compress_dev: the uint8 CUDA tensor `src_dev` written as a BGZF file into the uint8 CUDA tensor `dst`
+    (dst.numel() is dst_cap; it need not reach bgzf_bound()), one member per `block_bytes` (0 = 65280) of plaintext.
+    `members_cap`: rows of the member table to take (None = all).  Returns (status, file bytes -- with status -5 the bytes the
+    file needs --, members, nmembers, counters) with members = [(src_off, src_len, dst_off, out_len, crc, bgzf)], the rows
+    gunzip_members_dev reports for the file, and counters = {"rounds", "stored"} (zng_rocm_bgzf_last_*)."""
+    import numpy as np
+    from .inflate import GzipMember
+    rocm._need_init()
+    lib = rocm.lib()
+    n, bb = int(src_dev.numel()), int(block_bytes)
+    piece = bb if 0 < bb <= BGZF_BLOCK else BGZF_BLOCK
+    cap = -(-n // piece) + 1 if members_cap is None else int(members_cap)
+    table = np.empty(max(cap, 1) * C.sizeof(GzipMember), dtype=np.uint8)
+    out_len, nmembers = C.c_uint64(0), C.c_size_t(0)
+    fl = ((BGZF_NO_EOF if no_eof else 0) | (BGZF_QUICK if quick else 0)) if flags is None else int(flags)
+    st = lib.zng_rocm_bgzf_compress_dev(int(level), rocm._dev_ptr(src_dev) if n else None, n, bb,
+                                        rocm._dev_ptr(dst) if dst.numel() else None, int(dst.numel()), C.byref(out_len),
+                                        C.c_void_p(table.ctypes.data) if cap else None, cap, C.byref(nmembers), int(round_bytes), fl,
+                                        rocm._stream_ptr(stream))
+    rows = [(int(m.src_off), int(m.src_len), int(m.dst_off), int(m.out_len), int(m.crc), int(m.bgzf))
+            for m in (GzipMember * min(cap, int(nmembers.value))).from_buffer(table)]
+    counters = {"rounds": int(lib.zng_rocm_bgzf_last_rounds()), "stored": int(lib.zng_rocm_bgzf_last_stored())}
+    return st, int(out_len.value), rows, int(nmembers.value), counters

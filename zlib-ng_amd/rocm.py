@@ -147,6 +147,12 @@ _PROTOS = {
     "zng_rocm_gunzip_last_replans": (C.c_int, []),
     "zng_rocm_gunzip_last_small": (C.c_int, []),
     "zng_rocm_gunzip_last_large": (C.c_int, []),
+    "zng_rocm_bgzf_bound": (C.c_size_t, [C.c_size_t, C.c_uint32]),
+    "zng_rocm_bgzf_compress_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t,
+                                             C.POINTER(C.c_uint64), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_size_t,
+                                             C.c_uint32, C.c_void_p]),
+    "zng_rocm_bgzf_last_rounds": (C.c_int, []),
+    "zng_rocm_bgzf_last_stored": (C.c_int, []),
     "zng_rocm_wrapper_parse": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_char_p)]),
     "zng_rocm_workspace_bytes": (C.c_size_t, [C.c_void_p]),
     "zng_rocm_hook_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_size_t]),
