@@ -548,11 +548,61 @@ const char *zng_rocm_inflate_message(uint32_t id);
  *   kernel, the check values of all outputs in one many-message pass whose descriptors are filled on the device, every
  *   trailer compared (inflate.c:1105-1147).  d_results: 4 words per job as zng_rocm_inflate_streams_dev, bytes consumed
  *   counting header and trailer; message ids include "incorrect header check", "unknown compression method", "invalid
- *   window size", "header crc mismatch", "need dictionary", "incorrect data check", "incorrect length check". */
+ *   window size", "header crc mismatch", "need dictionary", "incorrect data check", "incorrect length check".  This call
+ *   holds no dictionary, so a zlib member with FDICT is "need dictionary" (-3; uncompr.c:70-75);
+ *   zng_rocm_uncompress_streams_dict_dev below is the call that reads such members. */
 size_t zng_rocm_compress_streams_bound(size_t source_len, int format);
 int  zng_rocm_compress_streams_dev(int format, const zng_rocm_stream_job *jobs, size_t njobs, uint32_t *d_results, void *stream);
 int  zng_rocm_uncompress_streams_dev(int format, const zng_rocm_inflate_dev_job *jobs, size_t njobs, uint32_t *d_results,
                                      void *stream);
+
+/* ---- one preset dictionary shared by many small device-resident streams -----------------------------------------------
+ * deflateSetDictionary / inflateSetDictionary (deflate.c:456-512, inflate.c:1234-1260) for the many-stream calls above.  The
+ * reference amortises a dictionary with one primed state that is deflateCopy'd per message; here the dictionary is prepared
+ * ONCE on the device as an object, and a whole batch of messages -- records, pages, RPC payloads -- is compressed or restored
+ * against it in one set of launches, with no copy of the dictionary in front of any buffer.
+ *
+ * zng_rocm_dict_create_dev: d_dict is device memory, dict_len >= 1 (NULL or 0: ZNG_ROCM_EINVAL, *out = NULL).  The call
+ *   - computes the DICTID, the Adler-32 of ALL dict_len bytes (deflate.c:470-471), with the streaming checksum kernel;
+ *   - copies the last W = min(dict_len, 32768) bytes into memory the object owns (the tail rule, deflate.c:477-486; d_dict
+ *     may be freed afterwards), zero padded so that the matcher's probes stay inside -- the padding never lengthens a match;
+ *   - builds the primed head table of the level-1 class: for every bucket the last position p with p + 4 <= W whose four
+ *     bytes hash there, + 1 (the last 3 positions are left out, deflate.c:494-501) -- one atomic max per position, so the
+ *     table is what entering the positions in order leaves, whatever the scheduling;
+ *   - synchronises `stream` once, to bring the DICTID to the host.
+ * The object is immutable afterwards and may be used from any thread and any HIP stream of the device it was made on.  After
+ * zng_rocm_shutdown() every call with it returns ZNG_ROCM_ENODEV (also under a later zng_rocm_init()); zng_rocm_dict_destroy
+ * frees it then as before (NULL is harmless).  zng_rocm_dict_id: the DICTID; zng_rocm_dict_window: W.
+ *
+ * zng_rocm_compress_streams_dict_dev is zng_rocm_compress_streams_dev with the shared history: format 0 = raw, 1 = zlib; 2
+ * (gzip has no dictionary, deflate.c:467) or a NULL dict is ZNG_ROCM_EINVAL with nothing launched.  Per job as there -- out
+ * 4-byte aligned, out_cap >= zng_rocm_compress_streams_dict_bound(in_len, format) (0 for a format the call refuses), two
+ * result words {total bytes written, Adler-32 of the plaintext} -- with the job's own dict_len 0 and block flags for format
+ * 0 only.  The payload comes from the dictionary form of the level-1 kernel: the head table is loaded from the object
+ * instead of being zeroed and primed, a candidate in the dictionary is probed and extended from the object's window, and a
+ * match whose source begins in the dictionary ends at the dictionary's last byte at the latest.  The zlib wrapper is 16 bytes
+ * so that the block starts 4-byte aligned: CMF / FLG with FDICT as deflate.c:868-888 writes them for the fastest level (78
+ * 3f), the DICTID most significant byte first (deflate.c:889-892), two empty stored blocks; the trailer is the Adler-32 of
+ * the plaintext alone (deflate.c:1098-1101).
+ *
+ * zng_rocm_uncompress_streams_dict_dev is zng_rocm_uncompress_streams_dev with the shared history (format 2 or a NULL dict:
+ * ZNG_ROCM_EINVAL; a job's dict_len and flags are 0).  Format 0: every job decodes with the W bytes as history
+ * (inflateSetDictionary on a raw stream).  Format 1, per member: FDICT set and the DICTID the object's -- decoded with the
+ * history, in_used counts the 6 header bytes; FDICT set and another DICTID -- status -3, out_len 0, in_used 6, message id 0
+ * (inflate.c:1247-1249 sets no text: the one -3 row without a message); FDICT clear -- decoded with NO history, as the large
+ * calls do, so a distance beyond the output is "invalid distance too far back"; a header that ends inside the DICTID is
+ * reported as a short header is (-5, nothing consumed).  Everything else -- result rows, statuses, trailer checks -- as
+ * zng_rocm_uncompress_streams_dev. */
+typedef struct zng_rocm_dict zng_rocm_dict;
+int      zng_rocm_dict_create_dev(const uint8_t *d_dict, size_t dict_len, zng_rocm_dict **out, void *stream);
+void     zng_rocm_dict_destroy(zng_rocm_dict *d);
+uint32_t zng_rocm_dict_id(const zng_rocm_dict *d);      /* Adler-32 of ALL dict_len bytes: the DICTID */
+uint32_t zng_rocm_dict_window(const zng_rocm_dict *d);  /* bytes that serve as history: min(dict_len, 32768) */
+size_t   zng_rocm_compress_streams_dict_bound(size_t source_len, int format);
+int      zng_rocm_compress_streams_dict_dev(int format, const zng_rocm_dict *dict, const zng_rocm_stream_job *jobs,
+                                            size_t njobs, uint32_t *d_results, void *stream);
+int      zng_rocm_uncompress_streams_dict_dev(int format, const zng_rocm_dict *dict, const zng_rocm_inflate_dev_job *jobs,
+                                              size_t njobs, uint32_t *d_results, void *stream);
 
 /* zlib (format 1) / gzip (format 2) members around the LARGE device inflaters: zng_rocm_inflate_large_streams_dev (the
  * batch) and zng_rocm_inflate_large_pieces_dev (one member of any length) for wrapped streams that already sit in device

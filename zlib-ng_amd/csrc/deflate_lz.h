@@ -111,9 +111,13 @@ __device__ __forceinline__ void lz_insert_batch(uint32_t n, uint32_t P, uint32_t
 // FULL: the caller guarantees that every position of the batch has its whole 258-byte lookahead inside the stream
 // (all batches but the last two of a stream) -- lim, maxlen and the end-of-input guards fold to constants, which
 // matters because the scalar instructions they cost are the kernel's bound.
-template <int HBITS, int NW = 4, bool FULL = false>   // NW = wavefronts per workgroup (batch = 64 * NW positions)
+// DICT (zng_rocm_compress_streams_dict_dev): positions below `dlen` name the bytes of a shared window `dwin` that is NOT in
+// front of the stream (in + c must not be read for c < dlen); dwin has 32 readable bytes behind its last.  A candidate there
+// is probed and extended from dwin, and its match is cut at the window's last byte.
+template <int HBITS, int NW = 4, bool FULL = false, bool DICT = false>   // NW = wavefronts per workgroup (batch = 64 * NW positions)
 __device__ __forceinline__ LzPick lz_batch(const uint8_t *__restrict__ in, uint32_t n, uint32_t P,
-                                           const u32x4_unaligned &own, LzShared<HBITS> *sh, int t) {
+                                           const u32x4_unaligned &own, LzShared<HBITS> *sh, int t,
+                                           const uint8_t *dwin = nullptr, uint32_t dlen = 0) {
     const int lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);        // wave-uniform: keeps the parse scalar
     const uint32_t p = P + (uint32_t)t;
@@ -133,10 +137,21 @@ __device__ __forceinline__ LzPick lz_batch(const uint8_t *__restrict__ in, uint3
     {
         const uint32_t c = old - 1u;                     // old == 0 -> 0xffffffff: fails c < p
         if (c < p && p - c <= kLzMaxDist) {
-            uint32_t l = lz_prefix16(FULL ? load_u128(in + c) : load_16_guarded(in, c, n), own);
-            if (l == 16u && maxlen > 16u)
-                l += lz_prefix16(FULL ? load_u128(in + c + 16u) : load_16_guarded(in, c + 16u, n),
-                                 FULL ? load_u128(in + p + 16u) : load_16_guarded(in, p + 16u, n));
+            uint32_t l = 0;
+            if constexpr (!DICT) {
+                l = lz_prefix16(FULL ? load_u128(in + c) : load_16_guarded(in, c, n), own);
+                if (l == 16u && maxlen > 16u)
+                    l += lz_prefix16(FULL ? load_u128(in + c + 16u) : load_16_guarded(in, c + 16u, n),
+                                     FULL ? load_u128(in + p + 16u) : load_16_guarded(in, p + 16u, n));
+            } else {
+                const bool shared = c < dlen;
+                const uint8_t *from = shared ? dwin + c : in + c;
+                l = lz_prefix16(FULL || shared ? load_u128(from) : load_16_guarded(in, c, n), own);
+                if (l == 16u && maxlen > 16u)
+                    l += lz_prefix16(FULL || shared ? load_u128(from + 16u) : load_16_guarded(in, c + 16u, n),
+                                     FULL ? load_u128(in + p + 16u) : load_16_guarded(in, p + 16u, n));
+                if (shared && l > dlen - c) l = dlen - c;        // what lies behind the window never lengthens a match
+            }
             l = l < maxlen ? l : maxlen;
             len = l >= kLzMinMatch ? l : 0u;             // kLzProbe = both rounds matched: the parse extends it
             dist = p - c;
@@ -163,7 +178,14 @@ __device__ __forceinline__ LzPick lz_batch(const uint8_t *__restrict__ in, uint3
                 const uint32_t D = (uint32_t)__builtin_amdgcn_readlane((int)dist, (int)m);
                 uint32_t rem = mlen - L;
                 if (rem > 256u) rem = 256u;
-                L += lz_extend_wave(in + pabs + L, in + pabs - D + L, rem, lane);
+                if constexpr (!DICT) {
+                    L += lz_extend_wave(in + pabs + L, in + pabs - D + L, rem, lane);
+                } else {
+                    const uint32_t c = pabs - D;         // uniform: the source of a match from the shared window stays in it
+                    const bool shared = c < dlen;
+                    if (shared) rem = rem < dlen - c - L ? rem : dlen - c - L;
+                    L += lz_extend_wave(in + pabs + L, shared ? dwin + c + L : in + c + L, rem, lane);
+                }
                 if ((uint32_t)lane == m) len = L;
             }
         }

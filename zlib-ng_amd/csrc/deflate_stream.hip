@@ -21,6 +21,7 @@
 #include "context.h"
 #include "deflate_dev.h"
 #include "deflate_lz.h"
+#include "dict_dev.h"
 
 #include <stdlib.h>
 #include <mutex>
@@ -29,6 +30,8 @@
 namespace zr {
 
 constexpr int kQuickHashBits = 12;      // 16 KiB head table: up to 8 streams in flight per CU (see deflate_lz.h)
+static_assert(kQuickHashBits == (int)kDictHashBits && kLzMinMatch == kDictMinMatch && kLzProbe <= kDictPad,
+              "dict_plan.h describes the head table and the probes of this kernel");
 
 struct StreamJobDev {
     const uint8_t *in;          // first byte of the dictionary (= the plaintext when there is none)
@@ -97,142 +100,18 @@ struct QuickShared {
 
 __global__ __launch_bounds__(256)
 void deflate_quick_kernel(const StreamJobDev *__restrict__ jobs, uint32_t *__restrict__ results) {
-    __shared__ QuickShared sh;
+    constexpr bool DICT = false;
+    const uint32_t *const dhead = nullptr;
+    const uint8_t *const dwin = nullptr;
+#include "deflate_quick_body.h"
+}
 
-    const StreamJobDev job = jobs[blockIdx.x];
-    const uint8_t *in = job.in;
-    const uint32_t n = job.n, start = job.start;
-    const bool final_block = (job.flags & ZNG_ROCM_BLOCK_NOT_FINAL) == 0;
-    uint32_t *outw = reinterpret_cast<uint32_t *>(job.out);
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-
-    for (int i = t; i < (1 << kQuickHashBits); i += 256) sh.lz.head[i] = 0;
-    // block header: BFINAL, BTYPE = 01 (deflate_quick.c:30-34 emits it through zng_tr_emit_tree(s, STATIC_TREES, last))
-    for (int i = t; i < (int)kRingWords; i += 256) sh.ring[i] = i == 0 ? (final_block ? 3u : 2u) : 0u;
-    if (t == 0) sh.lz.cover = start;     // nothing below the first plaintext byte is ever produced
-    __syncthreads();
-
-    // dictionary priming: the whole batches below `start` only enter their positions into the hash
-    uint32_t P0 = 0;
-    for (; P0 + 256u <= start; P0 += 256u) {
-        const uint32_t p = P0 + (uint32_t)t;
-        lz_insert_batch<kQuickHashBits, 4>(n, P0, p + kLzMinMatch <= n ? load_u32(in + p) : 0u, &sh.lz, t);
-    }
-
-    uint32_t cursor = 3;                 // bits placed so far (uniform over the workgroup)
-    uint32_t flushed = 0;                // whole words already written to `out`
-    uint32_t pend_code = 0, pend_nb = 0, pend_pre = 0;     // this lane's token of the previous batch, not yet placed
-    bool have_pending = false;
-    unsigned long long accA = 0, accB = 0;                 // Adler-32, linear form: B += (n - pos) * byte
-
-    // place the pending batch: every lane ORs its token at cursor + (bits of the waves before it) + (its wave prefix)
-    auto place = [&](int parity) {
-        const uint4 wb = sh.wave_bits[parity];
-        const uint32_t before = (wave > 0 ? wb.x : 0u) + (wave > 1 ? wb.y : 0u) + (wave > 2 ? wb.z : 0u);
-        if (pend_nb) {
-            const uint32_t at = cursor + before + pend_pre;
-            const uint32_t word = at >> 5;
-            const unsigned long long wide = (unsigned long long)pend_code << (at & 31u);     // <= 31 + 31 bits
-            atomicOr(&sh.ring[word & (kRingWords - 1u)], (uint32_t)wide);
-            atomicOr(&sh.ring[(word + 1) & (kRingWords - 1u)], (uint32_t)(wide >> 32));
-        }
-        cursor += wb.x + wb.y + wb.z + wb.w;
-    };
-    // stream out complete words; everything below `cursor` was ORed before the last barrier
-    auto flush = [&](uint32_t keep_below) {
-        const uint32_t full = cursor >> 5;
-        if (full - flushed >= keep_below) {
-            const uint32_t cnt = keep_below > 1 ? ((full - flushed) & ~31u) : full - flushed;
-            for (uint32_t i = (uint32_t)t; i < cnt; i += 256) {
-                const uint32_t slot = (flushed + i) & (kRingWords - 1u);
-                __builtin_nontemporal_store(sh.ring[slot], outw + flushed + i);
-                sh.ring[slot] = 0;
-            }
-            flushed += cnt;
-        }
-    };
-
-    u32x4_unaligned own = load_16_guarded(in, P0 + (uint32_t)t, n);  // this lane's 16 bytes of the current batch
-    int parity = 0;
-    for (uint32_t P = P0; P < n; P += 256) {
-        // every position of the NEXT batch has its 16 bytes inside the stream / of this batch its whole lookahead
-        const uint32_t pn = P + 256u + (uint32_t)t;
-        const bool full = n >= 256u + kStdMaxMatch + 4u && P <= n - (256u + kStdMaxMatch + 4u);
-        const bool next_inside = n >= 512u + 16u && P <= n - (512u + 16u);
-        u32x4_unaligned own_next = {0u, 0u, 0u, 0u};                           // prefetch of the next batch
-        if (next_inside) own_next = load_u128(in + pn);
-        else if (pn >= P) own_next = load_16_guarded(in, pn, n);
-        const LzPick r = full ? lz_batch<kQuickHashBits, 4, true>(in, n, P, own, &sh.lz, t)
-                              : lz_batch<kQuickHashBits, 4, false>(in, n, P, own, &sh.lz, t);
-        // (lz_batch ended behind barriers: the wave totals and the ORs of the previous iteration are visible)
-        flush(kFlushWords);
-        if (have_pending) place(parity ^ 1);
-        const uint32_t p = P + (uint32_t)t;
-        const uint32_t byte = p >= start ? own.x & 0xffu : 0u;   // zero beyond the end of the stream; the dictionary
-        accA += byte;                                            // is not part of the checksum
-        accB += (unsigned long long)(n - p) * byte;
-        // both codes are computed and one is selected: no branch (lanes without a token carry r.len = r.dist = 0,
-        // which the match coder turns into harmless garbage that the select drops)
-        uint32_t mcode, mnb, lcode, lnb;
-        static_match(r.kind == 2u ? r.len : 3u, r.kind == 2u ? r.dist : 1u, mcode, mnb);
-        static_literal(byte, lcode, lnb);
-        const uint32_t code = r.kind == 2u ? mcode : (r.kind == 1u ? lcode : 0u);
-        const uint32_t nb = r.kind == 2u ? mnb : (r.kind == 1u ? lnb : 0u);
-        uint32_t incl = nb;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t up = (uint32_t)__shfl_up((int)incl, d, 64);
-            if (lane >= d) incl += up;
-        }
-        if (lane == 63) reinterpret_cast<uint32_t *>(&sh.wave_bits[parity])[wave] = incl;
-        pend_code = code;
-        pend_nb = nb;
-        pend_pre = incl - nb;
-        have_pending = true;
-        parity ^= 1;
-        own = own_next;
-    }
-    __syncthreads();
-    if (have_pending) place(parity ^ 1);
-    __syncthreads();
-    flush(1);                                                // every complete word
-
-    // end-of-block code 256 = seven 0 bits (zng_emit_end_block, trees_emit.h:169-180), then pad to a byte
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        accA += __shfl_xor(accA, m, 64);
-        accB += __shfl_xor(accB, m, 64);
-    }
-    if (lane == 0) {
-        sh.red_a[wave] = accA % kAdlerBase;
-        sh.red_b[wave] = accB % kAdlerBase;
-    }
-    __syncthreads();
-    if (t == 0) {
-        uint8_t *outb = job.out;
-        uint32_t cbits = (cursor & 31u) + 7u;                // the partial word + EOB
-        uint32_t cw = sh.ring[(cursor >> 5) & (kRingWords - 1u)];
-        uint32_t wbase = flushed;                            // == cursor >> 5
-        if (cbits >= 32) {
-            outw[wbase++] = cw;
-            cw = 0;
-            cbits -= 32;
-        }
-        uint32_t bytes = wbase * 4u;
-        const bool sync = !final_block && (job.flags & ZNG_ROCM_BLOCK_SYNC_FLUSH) != 0;
-        if (sync) cbits += 3;                                // header of an empty stored block: BFINAL = 0, BTYPE = 00
-        for (uint32_t k = 0; k < (cbits + 7u) / 8u; ++k) outb[bytes++] = (uint8_t)((unsigned long long)cw >> (8 * k));   // up to 34 bits
-        if (sync) {                                          // ... byte aligned, LEN = 0, NLEN = 0xffff: what Z_SYNC_FLUSH
-            outb[bytes++] = 0x00;                            // appends (deflate.c:1064-1076, zng_tr_stored_block)
-            outb[bytes++] = 0x00;
-            outb[bytes++] = 0xff;
-            outb[bytes++] = 0xff;
-        }
-        const unsigned long long A = (sh.red_a[0] + sh.red_a[1] + sh.red_a[2] + sh.red_a[3]) % kAdlerBase;
-        const unsigned long long B = (sh.red_b[0] + sh.red_b[1] + sh.red_b[2] + sh.red_b[3]) % kAdlerBase;
-        results[2 * blockIdx.x] = bytes;
-        results[2 * blockIdx.x + 1] = (uint32_t)(((1 + A) % kAdlerBase) | ((((unsigned long long)(n - start) + B) % kAdlerBase) << 16));
-    }
+// the dictionary form: one shared window and its primed head table instead of a history in front of every stream
+__global__ __launch_bounds__(256)
+void deflate_quick_dict_kernel(const StreamJobDev *__restrict__ jobs, uint32_t *__restrict__ results,
+                               const uint32_t *__restrict__ dhead, const uint8_t *__restrict__ dwin) {
+    constexpr bool DICT = true;
+#include "deflate_quick_body.h"
 }
 
 // ---- the same coder with ONE wavefront per stream ------------------------------------------------------------------
@@ -497,6 +376,43 @@ void deflate_quick_wave_kernel(const StreamJobDev *__restrict__ jobs, uint32_t *
         results[2 * blockIdx.x] = bytes;
         results[2 * blockIdx.x + 1] = (uint32_t)(((1 + A) % kAdlerBase) | ((((unsigned long long)(n - start) + B) % kAdlerBase) << 16));
     }
+}
+
+}  // namespace zr
+
+extern "C" size_t zng_rocm_deflate_quick_bound(size_t source_len);
+
+namespace zr {
+
+int launch_deflate_quick_dict(const zng_rocm_stream_job *jobs, size_t njobs, uint32_t *d_results, const zng_rocm_dict *dict,
+                              hipStream_t st) {
+    if (!njobs) return ZNG_ROCM_OK;
+    Workspace *ws = workspace_for(st);
+    if (!ws) return ZNG_ROCM_ENOMEM;
+    std::lock_guard<std::mutex> use(ws->mu);
+    StreamJobDev *d_jobs = nullptr, *h_jobs = nullptr;
+    if (int rc = scratch_reserve(ws, kScrQuickJobs, njobs * sizeof(StreamJobDev), false, (void **)&d_jobs)) return rc;
+    if (int rc = host_tables_acquire(ws)) return rc;
+    if (int rc = scratch_reserve(ws, kScrQuickJobsHost, njobs * sizeof(StreamJobDev), true, (void **)&h_jobs)) return rc;
+    const uint32_t W = dict->window;
+    for (size_t i = 0; i < njobs; ++i) {
+        const zng_rocm_stream_job &j = jobs[i];
+        if (!j.out || (j.in_len && !j.in) || ((uintptr_t)j.out & 3) || j.out_cap < zng_rocm_deflate_quick_bound(j.in_len) ||
+            j.dict_len || (uint64_t)j.in_len + W > 0xffffffffull ||
+            (j.flags & ~(uint32_t)(ZNG_ROCM_BLOCK_NOT_FINAL | ZNG_ROCM_BLOCK_SYNC_FLUSH))) {
+            set_error("job %zu: out must be 4-byte aligned with out_cap >= the bound, dict_len 0 (the history is the dictionary "
+                      "object's), known flags, and window + plaintext below 4 GiB", i);
+            return ZNG_ROCM_EINVAL;
+        }
+        // position W + k names plaintext byte k: the address of "position 0" is never read
+        h_jobs[i] = StreamJobDev{(const uint8_t *)((uintptr_t)j.in - W), j.out, j.in_len + W, j.out_cap, W, j.flags};
+    }
+    ZR_HIP(hipMemcpyAsync(d_jobs, h_jobs, njobs * sizeof(StreamJobDev), hipMemcpyHostToDevice, st));
+    if (int rc = host_tables_release(ws, st)) return rc;
+    ZR_LAUNCH_TRACED(deflate_quick_dict_kernel, dim3((unsigned)njobs), dim3(256), st, d_jobs, d_results,
+                     (const uint32_t *)dict->d_head, (const uint8_t *)dict->d_window);
+    ZR_HIP(hipGetLastError());
+    return ZNG_ROCM_OK;
 }
 
 }  // namespace zr

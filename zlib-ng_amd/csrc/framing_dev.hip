@@ -12,6 +12,11 @@
 // The level-1 class writes its block at a 4-byte aligned address, so both headers are 12 bytes long: gzip declares an
 // empty FEXTRA field (XLEN = 0), zlib puts two empty stored blocks (the 5-byte Z_SYNC_FLUSH marker, deflate.c:1064-1076,
 // twice) between its 2-byte header and the block -- valid RFC 1951 that every inflater skips.
+//
+// The *_dict calls are the same two pipelines for raw and zlib streams that share ONE preset dictionary (zng_rocm_dict,
+// dict.hip; deflateSetDictionary / inflateSetDictionary, deflate.c:456-512, inflate.c:1234-1260): the level-1 class and the
+// inflater in their dictionary forms, and a 16-byte zlib wrapper with FDICT and the DICTID (dict_plan.h) -- the kernels
+// frame_compress_dict_kernel, parse_header_dict_kernel and verify_trailer_dict_kernel below.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -19,6 +24,7 @@
 
 #include "checksum_args.h"
 #include "context.h"
+#include "dict_dev.h"
 #include "gf2.h"
 #include "inflate_dev.h"
 
@@ -84,7 +90,8 @@ void parse_header_kernel(const InflateJobDev *__restrict__ given, uint32_t njobs
             if (((cmf << 8) | flg) % 31u) msg = kMsgHeaderCheck;
             else if ((cmf & 15u) != 8u) msg = kMsgMethod;
             else if ((cmf >> 4) + 8u > 15u) msg = kMsgWindow;
-            else if (flg & 0x20u) msg = kMsgNeedDict;    // a preset dictionary: Z_DATA_ERROR for the one-shot caller (uncompr.c:70-75)
+            else if (flg & 0x20u) msg = kMsgNeedDict;    // a preset dictionary: Z_DATA_ERROR for the one-shot caller (uncompr.c:70-75);
+                                                         // zng_rocm_uncompress_streams_dict_dev is the call that holds one
             pos = 2;
         }
     } else if (format == 2) {                            // inflate.c:556-700
@@ -178,6 +185,89 @@ void verify_trailer_kernel(const InflateJobDev *__restrict__ given, const uint32
                 const uint32_t isize = t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) | ((uint32_t)t[7] << 24);
                 if (crc != checks[2 * i + 1]) { status = (uint32_t)-3; msg = kMsgDataCheck; }
                 else if (isize != out_len) { status = (uint32_t)-3; msg = kMsgLengthCheck; }
+            }
+            used = (uint32_t)(at + tail);
+        }
+    } else {
+        used += hdr;
+    }
+    results[4 * i] = out_len;
+    results[4 * i + 1] = used;
+    results[4 * i + 2] = status;
+    results[4 * i + 3] = msg;
+}
+
+// ---- the same with a shared preset dictionary (raw and zlib) --------------------------------------------------------------
+__global__ __launch_bounds__(256)
+void frame_compress_dict_kernel(const FrameJob *__restrict__ jobs, uint32_t njobs, int format, uint32_t dictid,
+                                const uint32_t *__restrict__ quick, uint32_t *__restrict__ results) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= njobs) return;
+    const uint32_t clen = quick[2 * i], adler = quick[2 * i + 1];
+    results[2 * i + 1] = adler;                          // of the plaintext alone: the dictionary is in no check value
+    if (format == 0) {
+        results[2 * i] = clen;
+        return;
+    }
+    uint8_t *out = jobs[i].out;
+    dict_put_header(out, dictid);
+    uint8_t *t = out + kDictWrapHead + clen;
+    for (uint32_t k = 0; k < 4u; ++k) t[k] = dict_trailer_byte(k, adler);
+    results[2 * i] = kDictWrapHead + clen + 4u;
+}
+
+// format 0: every job decodes with the W bytes of the window as history.  format 1: dict_parse_header's verdict per member
+__global__ __launch_bounds__(256)
+void parse_header_dict_kernel(const InflateJobDev *__restrict__ given, uint32_t njobs, int format, uint32_t dictid, uint32_t W,
+                              InflateJobDev *__restrict__ patched, uint32_t *__restrict__ head /* 2 per job: header bytes, verdict */) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= njobs) return;
+    const InflateJobDev j = given[i];
+    DictHeader h = {0u, kMsgNone, 1u};
+    if (format == 1) h = dict_parse_header(j.in, j.in_len, dictid);
+    InflateJobDev p = j;
+    p.dict_len = h.history ? W : 0u;
+    if (h.msg != kMsgNone) {                             // nothing to decode: an empty job costs the inflater nothing
+        p.in_len = 0;
+        p.out_cap = 0;
+    } else {
+        p.in = j.in + h.pos;
+        p.in_len = j.in_len - h.pos;
+    }
+    patched[i] = p;
+    head[2 * i] = h.pos;
+    head[2 * i + 1] = h.msg;
+}
+
+__global__ __launch_bounds__(256)
+void verify_trailer_dict_kernel(const InflateJobDev *__restrict__ given, const uint32_t *__restrict__ head,
+                                const uint32_t *__restrict__ checks, uint32_t njobs, int format, uint32_t *__restrict__ results) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= njobs) return;
+    uint32_t out_len = results[4 * i], used = results[4 * i + 1], status = results[4 * i + 2], msg = results[4 * i + 3];
+    const uint32_t hdr = head[2 * i], hmsg = head[2 * i + 1];
+    if (hmsg == kDictMismatch) {                         // Z_DATA_ERROR without a text (inflate.c:1247-1249), the DICTID consumed
+        out_len = 0;
+        used = hdr;
+        msg = kMsgNone;
+        status = (uint32_t)-3;
+    } else if (hmsg != kMsgNone) {
+        out_len = 0;
+        used = 0;
+        msg = hmsg;
+        status = hmsg == kMsgStarved ? (uint32_t)-5 : (uint32_t)-3;
+    } else if ((int32_t)status == 1) {
+        const uint32_t tail = wrap_tail(format);
+        const uint64_t at = (uint64_t)hdr + used;
+        if (at + tail > given[i].in_len) {               // the stream ends before its trailer
+            status = (uint32_t)-5;
+            msg = kMsgStarved;
+            used = (uint32_t)given[i].in_len;
+        } else {
+            if (format == 1) {
+                const uint8_t *t = given[i].in + at;
+                const uint32_t stored = ((uint32_t)t[0] << 24) | ((uint32_t)t[1] << 16) | ((uint32_t)t[2] << 8) | t[3];
+                if (stored != checks[2 * i]) { status = (uint32_t)-3; msg = kMsgDataCheck; }
             }
             used = (uint32_t)(at + tail);
         }
@@ -302,6 +392,115 @@ int zng_rocm_uncompress_streams_dev(int format, const zng_rocm_inflate_dev_job *
         if (int rc = launch_checksum_batch_device(adler, crc, d_sa, d_fa, d_part, njobs, d_checks, st)) return rc;
     }
     hipLaunchKernelGGL(verify_trailer_kernel, grid, block, 0, st, d_given, d_head, d_checks, (uint32_t)njobs, format, d_results);
+    ZR_HIP(hipGetLastError());
+    return ZNG_ROCM_OK;
+}
+
+size_t zng_rocm_compress_streams_dict_bound(size_t source_len, int format) {
+    if (format != 0 && format != 1) return 0;
+    return zng_rocm_deflate_quick_bound(source_len) + (format ? kDictWrapHead + wrap_tail(format) + 4 : 0);
+}
+
+int zng_rocm_compress_streams_dict_dev(int format, const zng_rocm_dict *dict, const zng_rocm_stream_job *jobs, size_t njobs,
+                                       uint32_t *d_results, void *stream) {
+    if (int rc = dict_usable(dict)) return rc;
+    if (!dict || format < 0 || format > 1) {
+        set_error("a dictionary object and format 0 (raw) or 1 (zlib): gzip has no preset dictionary");
+        return ZNG_ROCM_EINVAL;
+    }
+    if (!njobs) return ZNG_ROCM_OK;
+    if (!jobs || !d_results || njobs > 0x7fffffffull) return ZNG_ROCM_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    DeviceGuard dev;
+    Workspace *ws = workspace_for(st);
+    if (!ws) return ZNG_ROCM_ENOMEM;
+    const uint32_t head = format ? kDictWrapHead : 0u, tail = wrap_tail(format);
+    uint32_t *d_quick = nullptr;
+    FrameJob *d_fj = nullptr, *h_fj = nullptr;
+    std::vector<zng_rocm_stream_job> inner(njobs);
+    {
+        std::lock_guard<std::mutex> use(ws->mu);
+        if (int rc = scratch_reserve(ws, kScrFrameWords, njobs * 4 * sizeof(uint32_t), false, (void **)&d_quick)) return rc;
+        if (int rc = scratch_reserve(ws, kScrFrameJobs, njobs * sizeof(FrameJob), false, (void **)&d_fj)) return rc;
+        if (int rc = host_tables_acquire(ws)) return rc;
+        if (int rc = scratch_reserve(ws, kScrFrameJobsHost, njobs * sizeof(FrameJob), true, (void **)&h_fj)) return rc;
+        for (size_t i = 0; i < njobs; ++i) {
+            const zng_rocm_stream_job &j = jobs[i];
+            if (!j.out || ((uintptr_t)j.out & 3) || (j.in_len && !j.in) ||
+                j.out_cap < zng_rocm_compress_streams_dict_bound(j.in_len, format) || j.dict_len || (format && j.flags) ||
+                (j.flags & ~(uint32_t)(ZNG_ROCM_BLOCK_NOT_FINAL | ZNG_ROCM_BLOCK_SYNC_FLUSH))) {
+                set_error("job %zu: out must be 4-byte aligned with out_cap >= zng_rocm_compress_streams_dict_bound(); the job's "
+                          "dict_len must be 0 (the history is the dictionary object's) and a zlib stream takes no block flags", i);
+                return ZNG_ROCM_EINVAL;
+            }
+            inner[i] = j;
+            inner[i].out = (uint8_t *)j.out + head;
+            inner[i].out_cap = j.out_cap - head - tail;
+            h_fj[i] = FrameJob{(uint8_t *)j.out, j.in_len};
+        }
+        ZR_HIP(hipMemcpyAsync(d_fj, h_fj, njobs * sizeof(FrameJob), hipMemcpyHostToDevice, st));
+        if (int rc = host_tables_release(ws, st)) return rc;
+    }
+    if (int rc = launch_deflate_quick_dict(inner.data(), njobs, d_quick, dict, st)) return rc;      // takes the workspace itself
+    hipLaunchKernelGGL(frame_compress_dict_kernel, dim3((unsigned)((njobs + 255) / 256)), dim3(256), 0, st, d_fj, (uint32_t)njobs,
+                       format, dict->id, d_quick, d_results);
+    ZR_HIP(hipGetLastError());
+    return ZNG_ROCM_OK;
+}
+
+int zng_rocm_uncompress_streams_dict_dev(int format, const zng_rocm_dict *dict, const zng_rocm_inflate_dev_job *jobs,
+                                         size_t njobs, uint32_t *d_results, void *stream) {
+    if (int rc = dict_usable(dict)) return rc;
+    if (!dict || format < 0 || format > 1) {
+        set_error("a dictionary object and format 0 (raw) or 1 (zlib): gzip has no preset dictionary");
+        return ZNG_ROCM_EINVAL;
+    }
+    Context *c = ctx();
+    if (!njobs) return ZNG_ROCM_OK;
+    if (!jobs || !d_results || njobs > 0x7fffffffull) return ZNG_ROCM_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    DeviceGuard dev;
+    Workspace *ws = workspace_for(st);
+    if (!ws) return ZNG_ROCM_ENOMEM;
+    std::lock_guard<std::mutex> use(ws->mu);
+    InflateJobDev *d_given = nullptr, *h_given = nullptr, *d_patched = nullptr;
+    uint32_t *d_words = nullptr;
+    uint8_t *d_msg = nullptr;
+    Partial *d_part = nullptr;
+    if (int rc = scratch_reserve(ws, kScrInflateDevJobs, 2 * njobs * sizeof(InflateJobDev), false, (void **)&d_given)) return rc;
+    d_patched = d_given + njobs;
+    if (int rc = scratch_reserve(ws, kScrFrameWords, njobs * 4 * sizeof(uint32_t), false, (void **)&d_words)) return rc;
+    uint32_t *d_head = d_words, *d_checks = d_words + 2 * njobs;
+    if (int rc = scratch_reserve(ws, kScrCheckMessages, njobs * (sizeof(StreamArgs) + sizeof(FinalArgs)), false, (void **)&d_msg)) return rc;
+    if (int rc = scratch_reserve(ws, kScrCheckPartials, njobs * sizeof(Partial), false, (void **)&d_part)) return rc;
+    if (int rc = host_tables_acquire(ws)) return rc;
+    if (int rc = scratch_reserve(ws, kScrInflateDevJobsHost, njobs * sizeof(InflateJobDev), true, (void **)&h_given)) return rc;
+    for (size_t i = 0; i < njobs; ++i) {
+        const zng_rocm_inflate_dev_job &j = jobs[i];
+        if ((j.in_len && !j.in) || (j.out_cap && !j.out) || j.in_len > 0x7fffffffull || j.out_cap > 0x7fffffffull ||
+            j.dict_len || j.flags) {
+            set_error("job %zu: null buffer, a stream or output of 2 GiB and more, or dict_len / flags (the history is the "
+                      "dictionary object's)", i);
+            return ZNG_ROCM_EINVAL;
+        }
+        h_given[i] = InflateJobDev{(const uint8_t *)j.in, (uint8_t *)j.out, j.in_len, j.out_cap, 0u, 0u};
+    }
+    ZR_HIP(hipMemcpyAsync(d_given, h_given, njobs * sizeof(InflateJobDev), hipMemcpyHostToDevice, st));
+    if (int rc = host_tables_release(ws, st)) return rc;
+    const dim3 grid((unsigned)((njobs + 255) / 256)), block(256);
+    hipLaunchKernelGGL(parse_header_dict_kernel, grid, block, 0, st, d_given, (uint32_t)njobs, format, dict->id, dict->window,
+                       d_patched, d_head);
+    ZR_HIP(hipGetLastError());
+    if (int rc = launch_inflate_streams_dict_device(d_patched, njobs, d_results, dict->d_window + dict->window, st)) return rc;
+    if (format) {
+        StreamArgs *d_sa = reinterpret_cast<StreamArgs *>(d_msg);
+        FinalArgs *d_fa = reinterpret_cast<FinalArgs *>(d_msg + njobs * sizeof(StreamArgs));
+        hipLaunchKernelGGL(fill_check_args_kernel, grid, block, 0, st, d_patched, d_results, (uint32_t)njobs, c->tables, 1, 0,
+                           d_sa, d_fa);
+        ZR_HIP(hipGetLastError());
+        if (int rc = launch_checksum_batch_device(true, false, d_sa, d_fa, d_part, njobs, d_checks, st)) return rc;
+    }
+    hipLaunchKernelGGL(verify_trailer_dict_kernel, grid, block, 0, st, d_given, d_head, d_checks, (uint32_t)njobs, format, d_results);
     ZR_HIP(hipGetLastError());
     return ZNG_ROCM_OK;
 }

@@ -17,6 +17,10 @@ struct InflateJobDev {
 
 // one wavefront per job; d_jobs and d_results are device memory (results: 4 words per job)
 int launch_inflate_streams_device(const InflateJobDev *d_jobs, size_t njobs, uint32_t *d_results, hipStream_t stream);
+// the same with every job's dict_len bytes of history taken from ONE shared window: the bytes in front of d_hist_end
+// (zng_rocm_uncompress_streams_dict_dev: a job decodes with the whole window or, dict_len 0, with none)
+int launch_inflate_streams_dict_device(const InflateJobDev *d_jobs, size_t njobs, uint32_t *d_results, const uint8_t *d_hist_end,
+                                       hipStream_t stream);
 
 // the parts of ONE large stream, 16-bit symbols out (inflate_large.hip); results: 8 words per part; d_marks (or null):
 // (or of several streams, each stream's starts together and in order: then every job carries in `flags` the index one past

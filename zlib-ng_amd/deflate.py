@@ -72,16 +72,41 @@ class QuickBatch:
         return self.dst[o:o + clen].cpu().numpy().tobytes()
 
 
+class Dictionary:
+    """zng_rocm_dict: one preset dictionary prepared once on the device (DICTID, window, primed head table) and shared by
+    every stream of WrappedBatch.run_dict / InflateDevBatch.run_dict.  `data`: uint8 CUDA tensor (or bytes, copied to the
+    device first).  .id = Adler-32 of all of it, .window = min(len, 32768).  close() frees the object."""
+
+    def __init__(self, data, stream=None):
+        import numpy as np
+        import torch
+        rocm._need_init()
+        if not isinstance(data, torch.Tensor):
+            data = torch.from_numpy(np.frombuffer(bytes(data), dtype=np.uint8).copy()).to("cuda")
+        self.h = C.c_void_p()
+        rocm._check(rocm.lib().zng_rocm_dict_create_dev(rocm._dev_ptr(data) if data.numel() else None, int(data.numel()),
+                                                        C.byref(self.h), rocm._stream_ptr(stream)), "zng_rocm_dict_create_dev")
+        self.id = int(rocm.lib().zng_rocm_dict_id(self.h))
+        self.window = int(rocm.lib().zng_rocm_dict_window(self.h))
+
+    def close(self):
+        if self.h:
+            rocm.lib().zng_rocm_dict_destroy(self.h)
+            self.h = C.c_void_p()
+
+
 class WrappedBatch:
     """zng_rocm_compress_streams_dev: many streams, level-1 class, with their zlib (fmt 1) / gzip (fmt 2) wrapper written on
     the device.  Layout as QuickBatch; results: int32 CUDA tensor [n, 2] = {total bytes, check value}."""
 
-    def __init__(self, src, in_off, in_len, fmt):
+    def __init__(self, src, in_off, in_len, fmt, for_dict=False):
+        """for_dict: slots sized by zng_rocm_compress_streams_dict_bound (the 16-byte wrapper), for run_dict"""
         import torch
         rocm._need_init()
         self.src, self.fmt = src, fmt
         self.n = len(in_len)
-        self.bounds = [(rocm.lib().zng_rocm_compress_streams_bound(int(v), fmt) + 15) & ~15 for v in in_len]
+        bound = rocm.lib().zng_rocm_compress_streams_dict_bound if for_dict else rocm.lib().zng_rocm_compress_streams_bound
+        self.bounds = [(bound(int(v), fmt) + 15) & ~15 for v in in_len]
         self.out_off, total = [], 0
         for b in self.bounds:
             self.out_off.append(total)
@@ -101,6 +126,13 @@ class WrappedBatch:
     def run(self, stream=None):
         rocm._check(rocm.lib().zng_rocm_compress_streams_dev(self.fmt, C.byref(self.jobs), self.n, rocm._dev_ptr(self.results),
                                                              rocm._stream_ptr(stream)), "zng_rocm_compress_streams_dev")
+
+    def run_dict(self, dictionary, stream=None):
+        """the same streams against a shared preset Dictionary (fmt 0 raw, 1 zlib with FDICT / DICTID):
+        zng_rocm_compress_streams_dict_dev.  The batch must have been made with for_dict=True."""
+        rocm._check(rocm.lib().zng_rocm_compress_streams_dict_dev(self.fmt, dictionary.h, C.byref(self.jobs), self.n,
+                                                                  rocm._dev_ptr(self.results), rocm._stream_ptr(stream)),
+                    "zng_rocm_compress_streams_dict_dev")
 
     def compressed(self, i, results_host=None):
         res = self.results.cpu() if results_host is None else results_host

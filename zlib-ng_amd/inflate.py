@@ -252,6 +252,14 @@ class InflateDevBatch:
         rocm._check(rocm.lib().zng_rocm_uncompress_streams_dev(fmt, C.byref(self.jobs), self.n, rocm._dev_ptr(self.results),
                                                                rocm._stream_ptr(stream)), "zng_rocm_uncompress_streams_dev")
 
+    def run_dict(self, fmt, dictionary, stream=None):
+        """the same streams decoded against a shared preset dictionary (deflate.Dictionary): fmt 0 raw -- every stream with
+        the dictionary's window as history --, fmt 1 zlib with FDICT / DICTID judged per member
+        (zng_rocm_uncompress_streams_dict_dev).  The jobs' own dict_len must be 0."""
+        rocm._check(rocm.lib().zng_rocm_uncompress_streams_dict_dev(fmt, dictionary.h, C.byref(self.jobs), self.n,
+                                                                    rocm._dev_ptr(self.results), rocm._stream_ptr(stream)),
+                    "zng_rocm_uncompress_streams_dict_dev")
+
     def rows(self):
         """[(status, out_len, in_used, message)] (synchronises)"""
         r = self.results.cpu().tolist()
