@@ -226,6 +226,40 @@ def test_neighbours_of_trouble(mods, subblock):
     assert by_name["runs-of-zeros"][0] == 1 and by_name["runs-of-zeros"][4] > 0 and launches == 2, (by_name["runs-of-zeros"], launches)
 
 
+@pytest.fixture(scope="module")
+def singles(mods):
+    """three streams that take the pass's different ways: plain, with history, and with parts of a ratio far above 64 (the
+    runs-of-zeros job of test_neighbours_of_trouble, at its size: the second part launch is what it is here for)"""
+    torch, _, _ = mods
+    plain = synth.silesia_like(2 * MiB, seed=0x51A61E).tobytes()
+    window = plain[-1000:]
+    runs = synth.silesia_like(2 * MiB, seed=0x7B0 + 13).tobytes() + bytes(24 * MiB) + synth.silesia_like(2 * MiB, seed=0x7B0 + 14).tobytes()
+    return [Job(torch, "cpy6-2", _raw(plain, 6), plain, odd=7),
+            Job(torch, "cpy6-win1000-2", _raw(plain, 6, zdict=window), plain, window=window, odd=3),
+            Job(torch, "runs-of-zeros", _raw(runs, 6), runs, odd=5)]
+
+
+@pytest.mark.parametrize("subblock", [False, True])
+def test_a_batch_of_one_is_the_one_stream_call(mods, singles, subblock):
+    """both go through the same pass: the same status, counts and bytes, and the same parts and sub-parts on the chain"""
+    torch, inf, _ = mods
+    zr = importlib.import_module("zlib-ng_amd")
+    for j in singles:
+        rst, rn, rused, rparts, _, rwhole, rdst = _alone(torch, inf, zr, j, subblock)
+        rsub = inf.inflate_large_last_subparts()
+        rc, rows, rounds, launches, bufs = _run_batch(torch, inf, [j], subblock)
+        st, n, used, msg, parts, subparts = rows[0]
+        whole, dst = bufs[0]
+        print(j.name, subblock, (rst, rn, rused, rparts, rsub), rows[0], rounds, launches)
+        assert rc == 0 and rounds == 1, (j.name, rc, rounds)
+        assert (st, n, used, msg) == (1, len(j.plain), len(j.comp), None) and (rst, rn, rused) == (st, n, used), (j.name, rows[0])
+        assert torch.equal(dst[:n], rdst[:n]) and dst[:n].cpu().numpy().tobytes() == j.plain, j.name
+        assert parts > 0 and (parts, subparts) == (rparts, rsub), (j.name, rows[0], rparts, rsub)
+        assert launches == (2 if j.name == "runs-of-zeros" else 1), (j.name, launches)
+        for w in (whole, rwhole):                         # nothing in front of the destination, nothing at or behind its end
+            assert int(w[j.odd + j.cap:].min()) == 0xAB and int(w[:j.odd].min()) == 0xAB, j.name
+
+
 def test_refusals_launch_nothing(mods, mixed):
     torch, inf, _ = mods
     jobs, _ = mixed

@@ -11,7 +11,20 @@ by hand from the rules in the header's and the part kernel's comments:
   part 0 is genuine; the part a genuine part links to is genuine; nothing else is.  A link points forward and into its own
   stream.  A reach may not pass the bytes in front of the part (produced + window_len).  A key-1 part that begins inside the
   BFINAL block ends the stream where its first block ended.  Segments are closed at >= 40960 symbols; a last one below 32768
-  joins the one in front of it unless it is the only one."""
+  joins the one in front of it unless it is the only one.
+
+The rules the device pass reads its scratch and its second launch from are driven the same way (the driver's `layout`, `retry`
+and `segs` arguments):
+
+  part tables  jobs (40 bytes per part) | starts (8; SUBBLOCK: | keys, 8) | results (8 words; blocks mode: | marks, 4 words;
+               SUBBLOCK: | side words, 8 words) | slots, every table at a multiple of 256 bytes; the pinned mirror ends where
+               the slots begin
+  retry        a part that said "output full" (message 13) runs again with retry_cap = (1032 x its compressed bytes + 655360,
+               rounded up to 8) symbols of room, the parts one behind the other; a stream whose parts want more than the
+               limit in bytes (2 per symbol) is reported and left out
+  symbol array streams one behind the other, each behind a gap of 32768 symbols, the first at 32768; a copy's dst is re-based
+               to the array, gstart / first name the first copy of its segment; a segment's bytes end where the next segment
+               of the same stream begins, the last one's where the stream's do"""
 import os
 import subprocess
 import tempfile
@@ -20,7 +33,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NONE = 0xFFFFFFFF
-STARVED, LITLEN_CODE = 12, 9                     # InflateMsg: kMsgStarved, kMsgLitLenCode
+STARVED, LITLEN_CODE, OUT_FULL = 12, 9, 13        # InflateMsg: kMsgStarved, kMsgLitLenCode, kMsgOutFull
 NO_SIDE = [NONE, 0, 0, 0, 0, 0, 0, 0]
 
 
@@ -163,3 +176,87 @@ def test_segments(driver, sizes, segs):
     res = [part(n, 1000 * (i + 1), link=i + 1) for i, n in enumerate(sizes[:-1])] + [part(sizes[-1], 1000 * len(sizes), ended=1)]
     got = walk(driver, starts, res)
     assert got[0] == "ok" and got[1] == sum(sizes) and got[6] == segs
+
+
+def rule(exe, name, words):
+    """-> {line name: [numbers]} of the driver's `name` rule (a line without a name: "")"""
+    out = subprocess.run([exe, name], input=" ".join(str(w) for w in words), capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stderr
+    got = {}
+    for ln in out.stdout.strip("\n").split("\n"):
+        head, _, rest = ln.partition(":") if ":" in ln else ("", "", ln)
+        got[head] = [int(x) for x in rest.split()]
+    return got
+
+
+@pytest.mark.parametrize("np_, sub, blocks, want", [
+    # jobs, starts, keys, res, extra, up_bytes, res_words, mirror; 40 np, 8 np (16 np), 32 np (+ 16 np, + 32 np), each up to 256
+    (1, 0, 0, (0, 256, 264, 512, 544, 264, 8, 768)),
+    (1, 1, 0, (0, 256, 264, 512, 544, 272, 16, 768)),
+    (1, 0, 1, (0, 256, 264, 512, 544, 264, 12, 768)),
+    (5, 0, 0, (0, 256, 296, 512, 672, 296, 8, 768)),
+    (5, 1, 0, (0, 256, 296, 512, 672, 336, 16, 1024)),            # results | side words: 320 bytes -> 512
+    (5, 0, 1, (0, 256, 296, 512, 672, 296, 12, 768)),             # results | marks: 240 bytes
+])
+def test_part_table_layout(driver, np_, sub, blocks, want):
+    slot_symbols = 123456
+    jobs, starts, keys, res, extra, slots, up, res_words, mirror, device = rule(driver, "layout", [np_, sub, blocks, slot_symbols])[""]
+    assert (jobs, starts, keys, res, extra, up, res_words, mirror) == want
+    # 256-aligned, in order and not overlapping: each table ends before the next begins
+    assert all(o % 256 == 0 for o in (jobs, starts, res, slots))
+    assert jobs + 40 * np_ <= starts and starts + (16 if sub else 8) * np_ <= res and res + 4 * res_words * np_ <= slots
+    assert keys == starts + 8 * np_                               # the keys follow the starts ...
+    assert up == starts + (16 if sub else 8) * np_                # ... and go up with them and the jobs
+    assert extra == res + 32 * np_                                # marks or side words follow the 8 result words per part
+    assert res_words == 8 + (4 if blocks else 0) + (8 if sub else 0)
+    assert slots == mirror and device == mirror + 2 * slot_symbols
+
+
+def retry_cap(part_bytes):
+    return (part_bytes * 1032 + (640 << 10) + 7) & ~7
+
+
+def test_retry_plan(driver):
+    # two streams of 3 and 2 parts; parts 1 and 4 were full
+    spans, part_bytes = [0, 3, 3, 2], [100, 200, 300, 400, 500]
+    msgs = [0, OUT_FULL, 0, LITLEN_CODE, OUT_FULL]
+    assert (retry_cap(200), retry_cap(500)) == (861760, 1171360)
+    got = rule(driver, "retry", [24 << 30, 2] + spans + [5] + part_bytes + msgs)
+    assert got == {"again": [1, 4], "off": [0, 861760], "cap": [861760, 1171360], "total": [2033120], "over": []}
+    # the second stream wants 2 x 1171360 bytes: one byte less is over its limit, and the first stream's part is still planned
+    got = rule(driver, "retry", [2 * 1171360 - 1, 2] + spans + [5] + part_bytes + msgs)
+    assert got == {"again": [1], "off": [0], "cap": [861760], "total": [861760], "over": [1]}
+    got = rule(driver, "retry", [2 * 1171360, 2] + spans + [5] + part_bytes + msgs)
+    assert got["again"] == [1, 4] and got["over"] == []
+    # no part full: nothing to run again
+    got = rule(driver, "retry", [24 << 30, 2] + spans + [5] + part_bytes + [0, 0, STARVED, 0, 0])
+    assert got == {"again": [], "off": [], "cap": [], "total": [0], "over": []}
+
+
+def test_symbol_tables_of_one_stream(driver):
+    # three copies: 30000 + 20000 close a segment (50000 >= 40960), the third (50000 >= 32768) is one of its own
+    got = rule(driver, "segs", [1, 100000, 7000000, 3, 0, 30000, 30000, 20000, 50000, 50000])
+    assert got["v"] == [32768]
+    assert got["copies"] == [0, 32768, 32768, 30000, 0,
+                             1, 62768, 32768, 20000, 0,
+                             2, 82768, 82768, 50000, 2]
+    assert got["segs"] == [32768 + 0, 32768 + 50000, 32768 + 100000]          # the last: the closing triple
+    assert got["seg_dst"] == [7000000, 7050000]
+    assert got["seg_end"] == [82768, 32768 + 100000]
+    assert got["v_end"] == [132768]
+
+
+def test_symbol_tables_of_streams_one_behind_the_other(driver):
+    first = [100000, 7000000, 3, 0, 30000, 30000, 20000, 50000, 50000]
+    nothing = [0, 8000000, 1, 0, 0]                               # produced nothing: no place in the array
+    second = [40000, 9000000, 2, 0, 15000, 15000, 25000]
+    got = rule(driver, "segs", [3] + first + nothing + second)
+    v2 = 132768 + 32768                                           # behind the first stream's end and its own gap
+    assert got["v"] == [32768, 0, v2]
+    # the second stream's copies are numbers 4 and 5 of the input (slot) and 3 and 4 of the table: its one segment begins at 3
+    assert got["copies"][15:] == [4, v2, v2, 15000, 3, 5, v2 + 15000, v2, 25000, 3]
+    assert got["copies"][:15] == [0, 32768, 32768, 30000, 0, 1, 62768, 32768, 20000, 0, 2, 82768, 82768, 50000, 2]
+    assert got["segs"] == [32768, 82768, v2, v2 + 40000]
+    assert got["seg_dst"] == [7000000, 7050000, 9000000]           # its own destination
+    assert got["seg_end"] == [82768, 132768, v2 + 40000]
+    assert got["v_end"] == [v2 + 40000]

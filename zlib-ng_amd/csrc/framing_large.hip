@@ -24,12 +24,11 @@
 #include "context.h"
 #include "framing_large.h"
 #include "framing_parse.h"
+#include "inflate_dev.h"
 #include "inflate_large_limits.h"
 #include "gf2.h"
 
 namespace zr {
-
-void inflate_large_reset_counters();                     // inflate_large.hip
 
 // One sub-message of the check pass: 32 units of 16 KiB.  One workgroup streams about 26 GB/s (derived), so a
 // sub-message is its workgroup's ~20 us and a round of 100 MiB is one sub-message per CU.  4 MiB was measured first

@@ -6,6 +6,7 @@
 // Host pointers in, host pointers out: staging is this file's business (bounded: one block).
 #include "context.h"
 #include "deflate_dev.h"
+#include "inflate_dev.h"
 
 #include <string.h>
 
@@ -22,14 +23,6 @@ struct zng_rocm_hook {
     uint32_t    *d_check;             // 2 words
     uint32_t    *h_check;             // pinned
 };
-
-namespace zr {
-int inflate_large_device_only(const uint8_t *d_src, size_t src_len, const uint8_t *d_window, uint32_t window_len, uint8_t *d_dst,
-                              size_t dst_cap, uint64_t *out_len, size_t *in_used, hipStream_t st);      // inflate_large.hip
-int inflate_large_blocks_device_only(const uint8_t *d_src, size_t src_len, unsigned start_bit, const uint8_t *d_window,
-                                     uint32_t window_len, uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, uint64_t *end_bit,
-                                     int *final, hipStream_t st);                                         // inflate_large.hip
-}
 
 namespace {
 constexpr uint32_t kHist = 32768u;

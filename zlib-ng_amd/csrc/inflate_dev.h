@@ -1,19 +1,11 @@
-// inflate_dev.h -- what inflate_dev.hip shares with framing_dev.hip: the device job descriptor, the message ids of
-// d_results (texts: zng_rocm_inflate_message) and the launcher for a job table that already sits in device memory.
+// inflate_dev.h -- what the inflate translation units share: the device job descriptor and the message ids of d_results
+// (inflate_dev_types.h; texts: zng_rocm_inflate_message), the launchers for job tables that already sit in device memory,
+// and every other internal function that one of them defines and another calls.
 #pragma once
 #include "context.h"
 #include "inflate_dev_types.h"
 
 namespace zr {
-
-struct InflateJobDev {
-    const uint8_t *in;
-    uint8_t       *out;
-    uint64_t       in_len;
-    uint64_t       out_cap;
-    uint32_t       dict_len;
-    uint32_t       flags;
-};
 
 // one wavefront per job; d_jobs and d_results are device memory (results: 4 words per job)
 int launch_inflate_streams_device(const InflateJobDev *d_jobs, size_t njobs, uint32_t *d_results, hipStream_t stream);
@@ -34,5 +26,35 @@ int launch_inflate_parts_device(const InflateJobDev *d_jobs, size_t njobs, uint3
 // the sync kernel over a table of regions (SubRegionDev: inflate_dev_types.h)
 int launch_subblock_sync(const uint8_t *d_src, size_t src_len, const SubRegionDev *d_regions, size_t nregions,
                          unsigned long long *d_bit, unsigned long long *d_key, hipStream_t stream);
+
+// ---- inflate_resolve.hip ------------------------------------------------------------------------------------------------
+// a stream of a batch laid out in symbol space (inflate_resolve_batch, inflate_resolve_symbols_batch: d_streams)
+struct BatchStream {
+    uint64_t       v_start;     // symbol index of the stream's first byte
+    const uint8_t *d_window;    // its window_len bytes of history (device) or null
+    uint64_t       window_len;
+};
+// symbols that are already in place (inflate_large.hip) -> bytes: the windows in front, the context chain, the translation;
+// the layout of inflate_resolve_batch (context.h) without K1
+int inflate_resolve_symbols_batch(const uint64_t *d_segs, size_t nsegs, uint16_t *sym, const uint64_t *d_seg_dst,
+                                  const uint64_t *d_seg_end, const BatchStream *d_streams, size_t nstreams, hipStream_t st);
+// the sequential decoder on the calling thread + the device resolve: what every irregular stream ends up in; *msg (when
+// given) = the decoder's message of a data error (static storage), else null
+int inflate_raw_window_sequential(const uint8_t *src, size_t src_len, const uint8_t *d_window, uint32_t window_len, uint8_t *d_dst,
+                                  size_t dst_cap, uint64_t *out_len, size_t *in_used, hipStream_t st);
+int inflate_raw_window_sequential_msg(const uint8_t *src, size_t src_len, const uint8_t *d_window, uint32_t window_len,
+                                      uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, size_t *in_used, const char **msg,
+                                      hipStream_t st);
+
+// ---- inflate_large.hip (return conventions: see there) ------------------------------------------------------------------
+int inflate_large_from_host(const uint8_t *src, size_t src_len, const uint8_t *d_window, uint32_t window_len, uint8_t *d_dst,
+                            size_t dst_cap, uint64_t *out_len, size_t *in_used, hipStream_t st);
+int inflate_large_device_only(const uint8_t *d_src, size_t src_len, const uint8_t *d_window, uint32_t window_len, uint8_t *d_dst,
+                              size_t dst_cap, uint64_t *out_len, size_t *in_used, hipStream_t st);
+int inflate_large_blocks_device_only(const uint8_t *d_src, size_t src_len, unsigned start_bit, const uint8_t *d_window,
+                                     uint32_t window_len, uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, uint64_t *end_bit,
+                                     int *final, hipStream_t st);
+void inflate_large_forget_parts();       // the part counters of the calling thread back to 0 ("the sequential decoder did it")
+void inflate_large_reset_counters();     // all of the calling thread's last_* counters: nothing ran
 
 }  // namespace zr

@@ -1,9 +1,18 @@
-// inflate_dev_types.h -- the part of inflate_dev.h that needs no HIP: the message ids of d_results and the sync kernel's work
-// item.  inflate_large_plan.h (plain host code, compiled by a CPU test as well) is built on these.
+// inflate_dev_types.h -- the part of inflate_dev.h that needs no HIP: the device job descriptor, the message ids of d_results
+// and the sync kernel's work item.  inflate_large_plan.h (plain host code, compiled by a CPU test as well) is built on these.
 #pragma once
 #include <stdint.h>
 
 namespace zr {
+
+struct InflateJobDev {
+    const uint8_t *in;
+    uint8_t       *out;
+    uint64_t       in_len;
+    uint64_t       out_cap;
+    uint32_t       dict_len;
+    uint32_t       flags;
+};
 
 enum InflateMsg : uint32_t {
     kMsgNone = 0, kMsgBlockType, kMsgStoredLen, kMsgTooMany, kMsgCodeLengthsSet, kMsgBitRepeat, kMsgNoEob,

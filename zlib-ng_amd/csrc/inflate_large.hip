@@ -26,12 +26,15 @@
 //        K2 / K3 of inflate_resolve.hip resolve and translate.
 // Anything irregular on the chain -- a data error, a truncated stream, a distance too far back, no candidates (a stream of fixed-Huffman blocks only) -- sends the call to the sequential host decoder, which
 // then reports exactly what the reference would (status, message, bytes produced, bytes consumed).
-// A BATCH of such streams (zng_rocm_inflate_large_streams_dev, at the end of this file) runs the same steps once per round
-// over the parts of all its streams: the finder over a table of (stream, range) items, one part launch, one compaction,
-// one resolve.
-// What the host does between the launches -- the steps named above, the SUBBLOCK regions and their merge, the slot sizes --
-// is in inflate_large_plan.h, one copy for the one-stream path (inflate_large_try) and the batch (round_run).  This file
-// keeps the kernels, scratch and table uploads, the launches and synchronisations, and each entry point's policy for a
+// The steps from P on are written ONCE, for N streams (pass_run): one part launch over the parts of all of them, one more for
+// the parts whose slot was too small, one chain per stream, one compaction, one resolve.  In front of it are two finders:
+// inflate_large_try's (F1 / F2 above, over ONE stream: the one-pass call, every piece of zng_rocm_inflate_large_pieces_dev, the
+// hook's blocks mode, a host-resident stream) and round_find's (the same scan over a table of (stream, range) items:
+// zng_rocm_inflate_large_streams_dev, a round of streams at a time).  Each caller maps what the pass says about a stream --
+// done, too large for dst_cap, or "left the pass" -- to its own convention.
+// What the host does between the launches -- the steps named above, the SUBBLOCK regions and their merge, the slot sizes,
+// where the tables lie in scratch, which parts run again, the symbol array's layout -- is in inflate_large_plan.h.  This file
+// keeps the kernels, the scratch and table uploads, the launches and synchronisations, and each entry point's policy for a
 // stream the device path cannot do.
 #include <algorithm>
 #include <cstdio>
@@ -478,13 +481,6 @@ void compact_parts_kernel(const PartCopy *__restrict__ parts, uint16_t *__restri
     }
 }
 
-// inflate_resolve.hip: the sequential decoder + device resolve
-int inflate_raw_window_sequential(const uint8_t *src, size_t src_len, const uint8_t *d_window, uint32_t window_len, uint8_t *d_dst,
-                                  size_t dst_cap, uint64_t *out_len, size_t *in_used, hipStream_t st);
-// inflate_resolve.hip: symbols -> bytes (window in front, context chain, translate)
-int inflate_resolve_symbols(const uint64_t *d_segs, size_t nsegs, uint16_t *sym, uint8_t *d_out, const uint8_t *d_window,
-                            uint32_t window_len, hipStream_t st);
-
 static thread_local int t_large_parts = 0;
 static thread_local int t_large_subparts = 0;           // of them, parts that began inside a block
 static thread_local int t_large_substarts = 0;          // SUBBLOCK: sub-starts placed (the sync kernel's boundaries, deduplicated)
@@ -523,12 +519,277 @@ void inflate_large_forget_parts() {
 }
 
 
-// returns 1 with *out_len / *in_used set, or 0 = "irregular: use the sequential decoder", or a negative error.
-// Blocks mode (`blocks`, the streaming hook): the stream starts at bit `start_bit` of d_src, and input that ends inside a
-// block is no irregularity -- the chain stops at the first part that ran out of input, that part's complete blocks (its
-// marks) are kept, and *end_bit / *final say where the delivered blocks end and whether the BFINAL one is among them.
-// `sub` (ZNG_ROCM_INFLATE_SUBBLOCK; never with `blocks`): starts inside blocks too -- guesses in the gaps the finder leaves, the
-// sync kernel's dry parse, hand-offs on the chain (inflate_dev.hip, inflate_streams_kernel<..., SUB>).
+// ---- the pass -----------------------------------------------------------------------------------------------------------
+// One stream of a device pass: what its finder found, and what pass_run made of it.
+struct PassStream {
+    // in
+    const uint8_t *d_src = nullptr;
+    size_t         src_len = 0;
+    const uint8_t *d_window = nullptr;
+    uint32_t       window_len = 0;
+    uint8_t       *d_dst = nullptr;
+    size_t         dst_cap = 0;
+    unsigned long long start_bit = 0;                     // the stream begins at this bit of d_src (blocks mode, pieces)
+    unsigned long long key0 = 0;                          // pieces: the first start may lie inside a block itself (PiecePass)
+    uint16_t       b0 = 0;                                // the two bytes at start_bit (SUBBLOCK, when F1 + F2 ran)
+    bool           patterns_do = false;                   // the byte patterns alone cut the stream
+    std::vector<unsigned long long> starts;               // sorted (thin_starts)
+    size_t         heavy = 1;
+    long           job = -1;                              // a batch: its index in the caller's array, for why_chain
+    // out
+    bool           left = false;                          // not done here (set on entry: not taken up at all); the reason went
+                                                          // through why() / why_chain()
+    int            status = 0;                            // 1: chain.produced bytes are at d_dst; -5: they do not fit dst_cap and
+                                                          // nothing was written (the chain's counts hold either way)
+    Chain          chain;                                 // parts: chain.copies.size(), subparts: chain.subparts
+    size_t         substarts = 0;                         // SUBBLOCK: sub-starts placed (deduplicated)
+    std::vector<unsigned long long> keys;                 // SUBBLOCK, per start: 0 a block start, 1 inside a fixed-code block,
+                                                          // H + 2 inside the dynamic block at H
+    size_t         pbase = 0;                             // its first part in the launch's tables
+    const uint32_t *res = nullptr;                        // its parts' result words in the pinned mirror, once they ran (they
+                                                          // stay until the workspace's next pass)
+};
+static void leave(PassStream &s, const char *reason) {
+    s.left = true;
+    why(reason);
+}
+
+// The device pass over the streams `ss` whose starts are found, ONE of each step for all of them: the SUBBLOCK sync launch,
+// one part launch over the parts of all streams (each stream's starts together; a part looks for its end among its own
+// stream's only: InflateJobDev::flags) and one more for the parts whose slot was too small, one chain walk per stream on
+// the host, one compaction and one resolve over a symbol array that holds the streams one behind the other (symbol_tables).
+// So the long parts of one stream run under the short parts of the others, and the host round trips between the kernels
+// are paid once.  The rules are inflate_large_plan.h's; here are the launches, the copies and the scratch.
+// `sub` (ZNG_ROCM_INFLATE_SUBBLOCK): starts inside blocks too -- guesses in the gaps the finder leaves, the sync kernel's dry
+// parse, hand-offs on the chain (inflate_dev.hip, inflate_streams_kernel<..., SUB>).  `blocks` (the streaming hook; never
+// with `sub`): input that ends inside a block is no irregularity -- the chain stops at the first part that ran out of
+// input and that part's complete blocks (its marks) are kept.  `pp`: a piece (PiecePass); its caps bound the scratch, and a
+// pass over one of them sets pp->halve.  `blocks` and `pp` take ONE stream.
+// A stream the pass cannot do leaves it (PassStream::left); the others do not notice.  The streams from *taken on were not
+// taken up: their parts and those in front of them would be more than one launch (and the compaction grid) takes.
+// *launches counts the part launches.  Negative returns are HIP and allocation errors of the whole pass.
+static int pass_run(Workspace *ws, std::vector<PassStream> &ss, bool sub, bool blocks, PiecePass *pp, hipStream_t st, size_t *taken,
+                    int *launches) {
+    *taken = ss.size();
+    if (((blocks || pp) && ss.size() != 1) || (sub && blocks)) {
+        set_error("inflate_large: blocks mode and pieces take one stream, blocks mode no sub-starts");
+        return ZNG_ROCM_EINVAL;
+    }
+    const size_t cus = (size_t)ctx()->cus;
+    // ---- SUBBLOCK: guesses in the gaps (plan_sub_regions), with a step that fills the chip once per PASS (a stream never
+    // gets a coarser step than a sixteenth of itself: a small stream among large ones is still cut).
+    // No guesses when the pattern pass alone cut the stream: its writer (this library's level-6 class, pigz) already closed
+    // a block every few tens of KiB, and that kernel is bound by throughput, not by a long part.  Dynamic
+    // blocks are split while the Huffman starts found are no more than the chip's resident parts (12 per CU): the 256 MiB
+    // CPython level-6 stream (about 2700 of them) takes 10.3 ms split against 10.6 ms whole (DESIGN 3.10); with more
+    // starts than slots the chip is full without splitting. ----
+    if (sub) {
+        uint64_t pass_bits = 0;
+        size_t pass_heavy = 0;
+        for (const PassStream &s : ss) {
+            if (s.left) continue;
+            pass_bits += 8ull * s.src_len - s.start_bit;
+            pass_heavy += s.heavy;
+        }
+        const unsigned long long pass_step = std::max<unsigned long long>(kSubMinStep, pass_bits / (kSubPerSlot * 12ull * cus));
+        const uint32_t split_dynamic = pass_heavy <= 12u * cus ? 1u : 0u;
+        std::vector<SubRegionDev> regions;
+        std::vector<std::pair<uint32_t, uint32_t>> span(ss.size(), {0u, 0u});      // a stream's guess slots: two per guess
+        uint32_t nguess = 0;
+        for (size_t k = 0; k < ss.size(); ++k) {
+            PassStream &s = ss[k];
+            if (s.left) continue;
+            s.keys.assign(s.starts.size(), 0ull);
+            s.keys[0] = s.key0;
+            span[k].first = nguess;
+            const unsigned long long own = 8ull * s.src_len - s.start_bit;
+            const unsigned long long step = std::max<unsigned long long>(kSubMinStep, std::min<unsigned long long>(pass_step, own / 16));
+            const bool fixed_first = !s.patterns_do && (s.key0 == 1u || (s.key0 == 0u && (((unsigned)s.b0 >> ((s.start_bit & 7u) + 1u)) & 3u) == 1u));
+            // (every region carries its own stream: the sync kernel's launch names none)
+            if (!s.patterns_do)
+                plan_sub_regions(s.starts, 8ull * s.src_len, step, split_dynamic, fixed_first, s.key0, s.d_src, s.src_len, regions, nguess);
+            span[k].second = nguess;
+        }
+        if (nguess) {
+            TableLayout l;
+            l.add(regions.size() * sizeof(SubRegionDev));
+            const size_t reg_b = l.bytes, out_b = (size_t)nguess * 16;
+            uint8_t *dp = nullptr, *hp2 = nullptr;
+            if (pp && reg_b + out_b > piece_cap_sub(pp->q)) {
+                pp->halve = true;
+                leave(ss[0], "the piece's sub-starts need more scratch than its cap");
+            } else if (scratch_reserve(ws, kScrLargeSub, reg_b + out_b, false, (void **)&dp) == ZNG_ROCM_OK &&
+                       scratch_reserve(ws, kScrLargeSubHost, reg_b + out_b, true, (void **)&hp2) == ZNG_ROCM_OK) {
+                // (without the scratch: no sub-starts, the streams go on with the starts found)
+                std::copy(regions.begin(), regions.end(), (SubRegionDev *)hp2);
+                unsigned long long *d_bit = (unsigned long long *)(dp + reg_b), *h_bit = (unsigned long long *)(hp2 + reg_b);
+                ZR_HIP(hipMemcpyAsync(dp, hp2, regions.size() * sizeof(SubRegionDev), hipMemcpyHostToDevice, st));
+                if (int rc = launch_subblock_sync(nullptr, 0, (const SubRegionDev *)dp, regions.size(), d_bit, d_bit + nguess, st)) return rc;
+                ZR_HIP(hipMemcpyAsync(h_bit, d_bit, out_b, hipMemcpyDeviceToHost, st));
+                ZR_HIP(hipStreamSynchronize(st));
+                for (size_t k = 0; k < ss.size(); ++k) {
+                    PassStream &s = ss[k];
+                    if (s.left || span[k].first == span[k].second) continue;
+                    s.substarts = merge_sub_starts(s.starts, s.keys, h_bit, h_bit + nguess, span[k].first, span[k].second, s.start_bit,
+                                                   s.src_len, s.heavy);
+                }
+            }
+        }
+    }
+    // ---- the pass's parts: each stream's together, the streams one behind the other ---------------------------------------
+    size_t np = 0, heavy = 0;
+    std::vector<size_t> on;                               // streams in the part launch
+    for (size_t k = 0; k < ss.size(); ++k) {
+        PassStream &s = ss[k];
+        if (s.left) continue;
+        if (s.starts.size() < 4) {
+            leave(s, "fewer than four block starts found");
+            continue;
+        }
+        if (np + s.starts.size() > kPieceMaxParts) {      // more parts than one launch (and the compaction grid's y) takes
+            if (on.empty()) {                             // one stream alone has them: not a stream for the device path
+                if (pp) pp->halve = true;
+                leave(s, "more parts in one stream than one launch takes");
+                continue;
+            }
+            *taken = k;                                   // this stream and the ones behind it: the next pass
+            break;
+        }
+        s.pbase = np;
+        np += s.starts.size();
+        heavy += s.heavy;
+        on.push_back(k);
+    }
+    if (on.empty()) return ZNG_ROCM_OK;
+    auto all_out = [&](const char *reason) {
+        for (size_t k : on) ss[k].left = true;
+        return why(reason);
+    };
+    const bool many = heavy > 12u * cus;
+    std::vector<uint64_t> slot_off(np + 1, 0), part_bytes(np, 0);
+    // (slot_slack sees the parts of the whole pass: the slack of all slots together is what has to stay in bounds)
+    for (size_t k : on)
+        slot_caps(ss[k].starts.data(), ss[k].starts.size(), 8ull * ss[k].src_len, slot_slack(np, pp), &slot_off[ss[k].pbase],
+                  &part_bytes[ss[k].pbase]);
+    const PartTables T = part_tables(np, sub, blocks, slot_off[np]);
+    // what comes back from and goes up to the device between the launches passes through pinned memory (pageable copies of
+    // these few hundred KiB were a good part of the 0.55 ms the host spends between the kernels of a 256 MiB stream)
+    uint8_t *sp = nullptr, *hq = nullptr;
+    if (scratch_reserve(ws, kScrLargeParts, T.device_bytes, false, (void **)&sp) != ZNG_ROCM_OK) return all_out("no room for the part slots");
+    if (scratch_reserve(ws, kScrLargePartsHost, T.mirror_bytes, true, (void **)&hq) != ZNG_ROCM_OK)
+        return all_out("no pinned memory for the part tables");
+    InflateJobDev *d_jobs = (InflateJobDev *)(sp + T.jobs), *pj = (InflateJobDev *)(hq + T.jobs);
+    unsigned long long *d_starts = (unsigned long long *)(sp + T.starts), *h_starts = (unsigned long long *)(hq + T.starts);
+    uint32_t *d_res = (uint32_t *)(sp + T.res), *res = (uint32_t *)(hq + T.res);
+    uint16_t *d_slots = (uint16_t *)(sp + T.slots);
+    uint32_t *d_extra = (uint32_t *)(sp + T.extra), *extra = (uint32_t *)(hq + T.extra);     // marks (blocks mode) or side words (SUBBLOCK)
+    for (size_t k : on) {
+        const PassStream &s = ss[k];
+        const size_t n = s.starts.size();
+        std::copy(s.starts.begin(), s.starts.end(), h_starts + s.pbase);
+        if (sub) std::copy(s.keys.begin(), s.keys.end(), (unsigned long long *)(hq + T.keys) + s.pbase);
+        for (size_t i = 0; i < n; ++i)
+            pj[s.pbase + i] = InflateJobDev{s.d_src, (uint8_t *)(d_slots + slot_off[s.pbase + i]), s.src_len,
+                                            slot_off[s.pbase + i + 1] - slot_off[s.pbase + i], i == 0 ? s.window_len : 32768u,
+                                            (uint32_t)(s.pbase + n)};
+    }
+    auto launch_parts = [&]() -> int {
+        if (int rc = launch_inflate_parts_device(d_jobs, np, d_res, d_starts, many, st, blocks ? d_extra : nullptr, sub ? d_extra : nullptr))
+            return rc;
+        ++*launches;
+        ZR_HIP(hipMemcpyAsync(res, d_res, np * 4 * T.res_words, hipMemcpyDeviceToHost, st));
+        ZR_HIP(hipStreamSynchronize(st));
+        return ZNG_ROCM_OK;
+    };
+    ZR_HIP(hipMemcpyAsync(sp, hq, T.up_bytes, hipMemcpyHostToDevice, st));       // jobs | starts (| keys) in one copy
+    if (int rc = launch_parts()) return rc;
+    // parts whose slot was too small, of all streams: ONE launch more, with retry_cap's room (plan_retry).  A stream whose
+    // parts want more than its limit leaves the pass; the others' parts are run again without it.
+    std::vector<uint16_t *> slot_ptr(np);
+    for (size_t i = 0; i < np; ++i) slot_ptr[i] = d_slots + slot_off[i];
+    {
+        std::vector<std::pair<size_t, size_t>> spans;
+        for (size_t k : on) spans.emplace_back(ss[k].pbase, ss[k].starts.size());
+        const RetryPlan retry = plan_retry(res, spans, part_bytes.data(), pp ? piece_cap_retry(pp->q) : 24ull << 30);
+        for (size_t o : retry.over) {
+            if (pp) pp->halve = true;
+            leave(ss[on[o]], pp ? "the piece's parts above a ratio of 64 need more scratch than its cap"
+                                : "parts with a ratio above 64 need more scratch than is reasonable");
+        }
+        uint8_t *bigp = nullptr;
+        if (!retry.again.empty() && scratch_reserve(ws, kScrLargeRetry, retry.total * 2, false, (void **)&bigp) != ZNG_ROCM_OK) {
+            for (size_t k : on)                           // (the streams that asked leave; the others are complete)
+                for (size_t i : retry.again)
+                    if (i >= ss[k].pbase && i < ss[k].pbase + ss[k].starts.size()) ss[k].left = true;
+            why("no room for the parts with a ratio above 64");
+        } else if (!retry.again.empty()) {
+            for (size_t i = 0; i < np; ++i) pj[i].out_cap = 0;
+            for (size_t a = 0; a < retry.again.size(); ++a) {
+                const size_t i = retry.again[a];
+                slot_ptr[i] = (uint16_t *)bigp + retry.off[a];
+                pj[i].out = (uint8_t *)slot_ptr[i];
+                pj[i].out_cap = retry.cap[a];
+            }
+            ZR_HIP(hipMemcpyAsync(d_jobs, pj, np * sizeof(InflateJobDev), hipMemcpyHostToDevice, st));
+            if (int rc = launch_parts()) return rc;
+        }
+    }
+    // ---- one chain per stream from its first part; a stream whose walk fails leaves the pass -------------------------------
+    std::vector<SymStream> placed;
+    std::vector<BatchStream> wins;
+    for (size_t k : on) {
+        PassStream &s = ss[k];
+        s.res = res + 8 * s.pbase;
+        if (s.left) continue;
+        const unsigned long long *keys = sub ? s.keys.data() : nullptr;
+        if (!walk_chain(res, extra, extra, slot_ptr.data(), s.pbase, s.starts.size(), s.starts.data(), keys, s.window_len, s.src_len, sub,
+                        blocks, pp, s.chain)) {
+            why_chain(s.chain, s.starts.size(), s.starts.data(), keys, s.res, pj + s.pbase, s.job);
+            s.left = true;
+            continue;
+        }
+        s.status = s.chain.produced > s.dst_cap ? -5 : 1;  // (too small: this stream's trouble alone, nothing of it is written)
+        if (s.status == 1 && s.chain.produced) {
+            placed.push_back(SymStream{&s.chain.copies, s.chain.produced, (uint64_t)(uintptr_t)s.d_dst});
+            wins.push_back(BatchStream{0, s.window_len ? s.d_window : nullptr, s.window_len});
+        }
+    }
+    // ---- the streams one behind the other in ONE symbol array; compaction, resolve, translate ----------------------------
+    if (placed.empty()) return ZNG_ROCM_OK;
+    const SymTables Y = symbol_tables(placed);
+    for (size_t w = 0; w < wins.size(); ++w) wins[w].v_start = placed[w].v;
+    const size_t nsegs = Y.seg_dst.size();                // (and Y.copies.size() <= np <= kPieceMaxParts, the grid's y limit)
+    TableLayout l;
+    const size_t o_segs = l.add(Y.segs.size() * 8), o_sd = l.add(nsegs * 8), o_se = l.add(nsegs * 8),
+                 o_win = l.add(wins.size() * sizeof(BatchStream)), o_cp = l.add(Y.copies.size() * sizeof(PartCopy)), o_sym = l.bytes;
+    uint8_t *yp = nullptr;
+    if (scratch_reserve(ws, kScrLargeSym, o_sym + ((size_t)Y.v_end + 64) * 2, false, (void **)&yp) != ZNG_ROCM_OK) {
+        for (size_t k : on)
+            if (!ss[k].left && ss[k].status == 1 && ss[k].chain.produced) ss[k].left = true;     // (the -5 streams keep their status)
+        return why("no room for the symbols");
+    }
+    uint16_t *sym = (uint16_t *)(yp + o_sym);
+    // (the five tables go up in ONE copy: each copy from pageable memory costs the host tens of microseconds)
+    std::vector<uint8_t> up(o_sym);
+    memcpy(up.data() + o_segs, Y.segs.data(), Y.segs.size() * 8);
+    memcpy(up.data() + o_sd, Y.seg_dst.data(), nsegs * 8);
+    memcpy(up.data() + o_se, Y.seg_end.data(), nsegs * 8);
+    memcpy(up.data() + o_win, wins.data(), wins.size() * sizeof(BatchStream));
+    memcpy(up.data() + o_cp, Y.copies.data(), Y.copies.size() * sizeof(PartCopy));
+    ZR_HIP(hipMemcpyAsync(yp, up.data(), up.size(), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(compact_parts_kernel, dim3(16, (unsigned)Y.copies.size()), dim3(256), 0, st, (const PartCopy *)(yp + o_cp), sym);
+    ZR_HIP(hipGetLastError());
+    if (int rc = inflate_resolve_symbols_batch((const uint64_t *)(yp + o_segs), nsegs, sym, (const uint64_t *)(yp + o_sd),
+                                               (const uint64_t *)(yp + o_se), (const BatchStream *)(yp + o_win), wins.size(), st))
+        return rc;
+    ZR_HIP(hipStreamSynchronize(st));
+    return ZNG_ROCM_OK;
+}
+
+// ONE stream through its own finder and the pass: returns 1 with *out_len / *in_used set, or 0 = "irregular: use the
+// sequential decoder", or a negative error (-5 with *out_len set: dst_cap is too small).
+// Blocks mode (`blocks`, the streaming hook): the stream starts at bit `start_bit` of d_src, and *end_bit / *final say where
+// the delivered blocks end and whether the BFINAL one is among them.  `sub`, `pp`: see pass_run.
 static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len, const uint8_t *d_window, uint32_t window_len,
                              uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, size_t *in_used, hipStream_t st,
                              bool blocks = false, uint64_t start_bit = 0, uint64_t *end_bit_out = nullptr, int *final_out = nullptr,
@@ -540,21 +801,22 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
     const unsigned long long lo_bits = 8ull * scan_lo;
     const uint32_t cap1 = (uint32_t)std::min<size_t>(scan_len / 64 + 4096, 64u << 20);
     const uint32_t cap2 = (uint32_t)std::min<size_t>(scan_len / 512 + 4096, 8u << 20);      // starts are >= 2 KiB apart in the end
-    uint8_t *fp = nullptr;
-    if (int rc = scratch_reserve(ws, kScrLargeCand, ((size_t)cap1 + cap2) * 8 + 64, false, (void **)&fp)) return rc;
-    unsigned long long *d_cand = (unsigned long long *)fp, *d_good = d_cand + cap1;
-    uint32_t *d_n = (uint32_t *)(d_good + cap2);          // [0] survivors of F1, [1] of F2
     // first pass: the byte patterns alone (sync markers, byte-aligned stored blocks); when they leave no 128 KiB of compressed
     // bytes without a start, that is all the cutting the stream needs and the search of every bit position (F1's
     // main loop) and F2 are skipped -- 1.3 of 9.4 ms for the 256 MiB cfg3 stream of this library's level-6 class
-    std::vector<unsigned long long> good;
     const uint32_t first = patterns_first(scan_len);
-    // what comes back from and goes up to the device between the launches passes through pinned memory (pageable copies of
-    // these few hundred KiB were a good part of the 0.55 ms the host spends between the kernels of a 256 MiB stream)
-    uint8_t *hp = nullptr;
-    if (int rc = scratch_reserve(ws, kScrLargeCandHost, 64 + (size_t)first * 8, true, (void **)&hp)) return rc;
-    uint32_t *n12 = (uint32_t *)hp;
-    unsigned long long *h_good = (unsigned long long *)(hp + 64);
+    TableLayout dl, hl;
+    const size_t o_cand = dl.add((size_t)cap1 * 8), o_good = dl.add((size_t)cap2 * 8), o_n = dl.add(64);
+    const size_t o_n12 = hl.add(64), o_hgood = hl.add((size_t)first * 8);
+    // what comes back from the device passes through pinned memory (see pass_run)
+    uint8_t *fp = nullptr, *hp = nullptr;
+    if (int rc = scratch_reserve(ws, kScrLargeCand, dl.bytes, false, (void **)&fp)) return rc;
+    if (int rc = scratch_reserve(ws, kScrLargeCandHost, hl.bytes, true, (void **)&hp)) return rc;
+    unsigned long long *d_cand = (unsigned long long *)(fp + o_cand), *d_good = (unsigned long long *)(fp + o_good);
+    uint32_t *d_n = (uint32_t *)(fp + o_n);               // [0] survivors of F1, [1] of F2
+    uint32_t *n12 = (uint32_t *)(hp + o_n12);
+    unsigned long long *h_good = (unsigned long long *)(hp + o_hgood);
+    std::vector<unsigned long long> good;
     n12[0] = n12[1] = 0;
     ZR_HIP(hipMemsetAsync(d_n, 0, 8, st));
     hipLaunchKernelGGL(find_headers_kernel<true>, dim3(4096), dim3(256), 0, st, d_src + scan_lo, (unsigned long long)scan_len, d_good,
@@ -580,7 +842,7 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
         ZR_HIP(hipGetLastError());
         // the counts and (what is almost always all of) the list in one round trip (SUBBLOCK: and the first block's header)
         ZR_HIP(hipMemcpyAsync(n12, d_n, 8, hipMemcpyDeviceToHost, st));
-        if (sub) ZR_HIP(hipMemcpyAsync(hp + 8, d_src + (start_bit >> 3), 2, hipMemcpyDeviceToHost, st));
+        if (sub) ZR_HIP(hipMemcpyAsync(n12 + 2, d_src + (start_bit >> 3), 2, hipMemcpyDeviceToHost, st));
         ZR_HIP(hipMemcpyAsync(h_good, d_good, (size_t)first * 8, hipMemcpyDeviceToHost, st));
         ZR_HIP(hipStreamSynchronize(st));
         // (SUBBLOCK goes on without candidates: a stream of fixed-code blocks is cut inside them)
@@ -598,184 +860,48 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
         for (unsigned long long &b : good) b = (b & ~(1ull << 63)) + lo_bits;
         std::sort(good.begin(), good.end(), by_bit);
     }
-    std::vector<unsigned long long> starts;
-    size_t heavy = 0;
-    thin_starts(good, start_bit, src_len, starts, heavy);
-    // ---- SUBBLOCK: starts inside blocks (plan_sub_regions) --------------------------------------------------------
-    // No guesses when the pattern pass alone cut the stream: its writer (this library's level-6 class, pigz) already closed
-    // a block every few tens of KiB, and that kernel is bound by throughput, not by a long part.  Dynamic
-    // blocks are split while the Huffman starts found are no more than the chip's resident parts (12 per CU): the 256 MiB
-    // CPython level-6 stream (about 2700 of them) takes 10.3 ms split against 10.6 ms whole (DESIGN 3.10); with more
-    // starts than slots the chip is full without splitting.
-    std::vector<unsigned long long> keys;                 // per start: 0 a block start, 1 inside a fixed-code block, H + 2 inside the dynamic block at H
-    const unsigned long long key0 = pp ? pp->key0 : 0ull;   // (pieces: the first start may lie inside a block itself)
-    if (sub) {
-        keys.assign(starts.size(), 0ull);
-        keys[0] = key0;
-        const unsigned long long total = 8ull * src_len - start_bit;
-        const unsigned long long step = std::max<unsigned long long>(kSubMinStep, total / (kSubPerSlot * 12ull * (unsigned long long)ctx()->cus));
-        std::vector<SubRegionDev> regions;
-        uint32_t nguess = 0;                              // guess slots: two per guess
-        const uint8_t *b0 = hp + 8;                        // (copied with the finder's counts when F1 + F2 ran)
-        const bool fixed_first = !patterns_do && (key0 == 1u || (key0 == 0u &&
-                                 ((((unsigned)b0[0] | ((unsigned)b0[1] << 8)) >> ((start_bit & 7u) + 1u)) & 3u) == 1u));
-        const uint32_t split_dynamic = heavy <= 12u * (size_t)ctx()->cus ? 1u : 0u;
-        // (the regions' own stream stays null: the sync kernel's launch names it)
-        if (!patterns_do) plan_sub_regions(starts, 8ull * src_len, step, split_dynamic, fixed_first, key0, nullptr, 0, regions, nguess);
-        if (nguess) {
-            const size_t reg_b = (regions.size() * sizeof(SubRegionDev) + 255) & ~(size_t)255, out_b = (size_t)nguess * 16;
-            if (pp && reg_b + out_b > piece_cap_sub(pp->q)) {
-                pp->halve = true;
-                return why("the piece's sub-starts need more scratch than its cap");
-            }
-            uint8_t *dp = nullptr, *hp2 = nullptr;
-            if (int rc = scratch_reserve(ws, kScrLargeSub, reg_b + out_b, false, (void **)&dp)) return rc;
-            if (int rc = scratch_reserve(ws, kScrLargeSubHost, reg_b + out_b, true, (void **)&hp2)) return rc;
-            std::copy(regions.begin(), regions.end(), (SubRegionDev *)hp2);
-            unsigned long long *d_bit = (unsigned long long *)(dp + reg_b), *h_bit = (unsigned long long *)(hp2 + reg_b);
-            ZR_HIP(hipMemcpyAsync(dp, hp2, regions.size() * sizeof(SubRegionDev), hipMemcpyHostToDevice, st));
-            if (int rc = launch_subblock_sync(d_src, src_len, (const SubRegionDev *)dp, regions.size(), d_bit, d_bit + nguess, st)) return rc;
-            ZR_HIP(hipMemcpyAsync(h_bit, d_bit, out_b, hipMemcpyDeviceToHost, st));
-            ZR_HIP(hipStreamSynchronize(st));
-            t_large_substarts += (int)merge_sub_starts(starts, keys, h_bit, h_bit + nguess, 0, nguess, start_bit, src_len, heavy);
-        }
-    }
-    const size_t np = starts.size();
-    const bool many = heavy > 12u * (size_t)ctx()->cus;
-    if (np < 4) return why("fewer than four block starts found");
-    if (pp && np > kPieceMaxParts) {
-        pp->halve = true;
-        return why("more parts in the piece than one launch takes");
-    }
-
-    // ---- parts ----------------------------------------------------------------------------------------------------
-    std::vector<uint64_t> slot_off(np + 1, 0), part_bytes(np, 0);
-    slot_caps(starts.data(), np, 8ull * src_len, slot_slack(np, pp), slot_off.data(), part_bytes.data());
-    uint8_t *sp = nullptr;
-    // (SUBBLOCK: the keys follow the start bits, and 8 words per part follow the results)
-    const size_t jobs_b = (np * sizeof(InflateJobDev) + 255) & ~(size_t)255, starts_b = (np * (sub ? 16 : 8) + 255) & ~(size_t)255,
-                 res_b = (np * 32 + (blocks ? np * 16 : 0) + (sub ? np * 32 : 0) + 255) & ~(size_t)255, slots_b = slot_off[np] * 2;
-    if (scratch_reserve(ws, kScrLargeParts, jobs_b + starts_b + res_b + slots_b, false, (void **)&sp) != ZNG_ROCM_OK)
-        return why("no room for the part slots");
-    InflateJobDev *d_jobs = (InflateJobDev *)sp;
-    unsigned long long *d_starts = (unsigned long long *)(sp + jobs_b);
-    uint32_t *d_res = (uint32_t *)(sp + jobs_b + starts_b);
-    uint16_t *d_slots = (uint16_t *)(sp + jobs_b + starts_b + res_b);
-    uint8_t *hq = nullptr;
-    if (scratch_reserve(ws, kScrLargePartsHost, jobs_b + starts_b + res_b, true, (void **)&hq) != ZNG_ROCM_OK)
-        return why("no pinned memory for the part tables");
-    InflateJobDev *jobs = (InflateJobDev *)hq;
-    unsigned long long *h_starts = (unsigned long long *)(hq + jobs_b);
-    uint32_t *res = (uint32_t *)(hq + jobs_b + starts_b);
-    uint32_t *d_marks = blocks ? d_res + 8 * np : nullptr, *marks = res + 8 * np;    // blocks mode: 4 words per part behind the results
-    uint32_t *d_side = sub ? d_res + 8 * np : nullptr, *side = res + 8 * np;        // SUBBLOCK: 8 words per part behind the results
-    const size_t res_words = blocks ? 12 : sub ? 16 : 8;
-    std::copy(starts.begin(), starts.end(), h_starts);
-    if (sub) std::copy(keys.begin(), keys.end(), h_starts + np);
-    for (size_t i = 0; i < np; ++i)
-        jobs[i] = InflateJobDev{d_src, (uint8_t *)(d_slots + slot_off[i]), src_len, slot_off[i + 1] - slot_off[i],
-                                i == 0 ? window_len : 32768u, 0u};
-    ZR_HIP(hipMemcpyAsync(d_jobs, jobs, np * sizeof(InflateJobDev), hipMemcpyHostToDevice, st));
-    ZR_HIP(hipMemcpyAsync(d_starts, h_starts, np * (sub ? 16 : 8), hipMemcpyHostToDevice, st));
-    if (int rc = launch_inflate_parts_device(d_jobs, np, d_res, d_starts, many, st, d_marks, d_side)) return rc;
-    ZR_HIP(hipMemcpyAsync(res, d_res, np * 4 * res_words, hipMemcpyDeviceToHost, st));
-    ZR_HIP(hipStreamSynchronize(st));
-    // parts whose slot was too small: once more, with retry_cap's room
-    uint8_t *bigp = nullptr;
-    std::vector<uint16_t *> slot_ptr(np);
-    for (size_t i = 0; i < np; ++i) slot_ptr[i] = d_slots + slot_off[i];
-    {
-        std::vector<size_t> again;
-        uint64_t need = 0;
-        for (size_t i = 0; i < np; ++i)
-            if (res[8 * i + 4] == kMsgOutFull) {
-                again.push_back(i);
-                need += retry_cap(part_bytes[i]);
-            }
-        if (!again.empty()) {
-            if (pp && need * 2 > piece_cap_retry(pp->q)) {
-                pp->halve = true;
-                return why("the piece's parts above a ratio of 64 need more scratch than its cap");
-            }
-            if (need * 2 > (24ull << 30) || scratch_reserve(ws, kScrLargeRetry, need * 2, false, (void **)&bigp) != ZNG_ROCM_OK)
-                return why("parts with a ratio above 64 need more scratch than is reasonable");
-            for (size_t i = 0; i < np; ++i) jobs[i].out_cap = 0;
-            uint64_t at = 0;
-            for (size_t i : again) {
-                const uint64_t capi = retry_cap(part_bytes[i]);
-                slot_ptr[i] = (uint16_t *)bigp + at;
-                jobs[i].out = (uint8_t *)slot_ptr[i];
-                jobs[i].out_cap = capi;
-                at += capi;
-            }
-            ZR_HIP(hipMemcpyAsync(d_jobs, jobs, np * sizeof(InflateJobDev), hipMemcpyHostToDevice, st));
-            if (int rc = launch_inflate_parts_device(d_jobs, np, d_res, d_starts, many, st, d_marks, d_side)) return rc;
-            ZR_HIP(hipMemcpyAsync(res, d_res, np * 4 * res_words, hipMemcpyDeviceToHost, st));
-            ZR_HIP(hipStreamSynchronize(st));
-        }
-    }
-
+    // ---- the pass over this one stream ------------------------------------------------------------------------------
+    std::vector<PassStream> ss(1);
+    PassStream &s = ss[0];
+    s.d_src = d_src;
+    s.src_len = src_len;
+    s.d_window = d_window;
+    s.window_len = window_len;
+    s.d_dst = d_dst;
+    s.dst_cap = dst_cap;
+    s.start_bit = start_bit;
+    s.key0 = pp ? pp->key0 : 0ull;
+    s.b0 = (uint16_t)n12[2];                              // (copied with the finder's counts when F1 + F2 ran)
+    s.patterns_do = patterns_do;
+    thin_starts(good, start_bit, src_len, s.starts, s.heavy);
+    size_t taken = 0;
+    int launches = 0;
+    const int rc = pass_run(ws, ss, sub, blocks, pp, st, &taken, &launches);
+    t_large_substarts += (int)s.substarts;
 #ifdef ZR_INFLATE_STATS
-    g_dbg_starts = starts;
-    g_dbg_res.assign(res, res + np * 8);
-#endif
-    // ---- the chain from bit 0 -------------------------------------------------------------------------------------
-    Chain chain;
-    if (!walk_chain(res, side, marks, slot_ptr.data(), 0, np, starts.data(), sub ? keys.data() : nullptr, window_len, src_len, sub,
-                    blocks, pp, chain))
-        return why_chain(chain, np, starts.data(), sub ? keys.data() : nullptr, res, jobs, -1);
-    std::vector<PartCopy> &copies = chain.copies;
-    const uint64_t produced = chain.produced;
-    const unsigned long long end_bit = chain.end_bit;
-    const bool final = chain.final;
-    const size_t subparts = chain.subparts;
-    std::vector<uint64_t> segs;                           // triples as inflate_resolve.hip wants them; only [3 s + 1] is used
-    {
-        const std::vector<size_t> seg_first = group_segments(copies, produced);
-        for (size_t g = 0; g + 1 < seg_first.size(); ++g) {
-            for (size_t c = seg_first[g]; c < seg_first[g + 1]; ++c) {
-                copies[c].gstart = copies[seg_first[g]].dst;
-                copies[c].first = (uint32_t)seg_first[g];
-            }
-            segs.push_back(0);
-            segs.push_back(copies[seg_first[g]].dst);
-            segs.push_back(0);
-        }
+    if (s.res) {
+        g_dbg_starts = s.starts;
+        g_dbg_res.assign(s.res, s.res + 8 * s.starts.size());
     }
-    segs.push_back(0);
-    segs.push_back(produced);
-    segs.push_back(0);
+#endif
+    if (rc) return rc;
+    if (s.left) return 0;
+    const uint64_t produced = s.chain.produced;
     if (out_len) *out_len = produced;
-    if (in_used) *in_used = (size_t)((end_bit + 7) >> 3);
-    if (end_bit_out) *end_bit_out = end_bit;
-    if (final_out) *final_out = final ? 1 : 0;
-    if ((blocks || (pp && pp->stopped)) && produced == 0) {       // no block complete yet (pieces: no symbol): nothing to launch
+    if (in_used) *in_used = (size_t)((s.chain.end_bit + 7) >> 3);
+    if (end_bit_out) *end_bit_out = s.chain.end_bit;
+    if (final_out) *final_out = s.chain.final ? 1 : 0;
+    if ((blocks || (pp && pp->stopped)) && produced == 0) {       // no block complete yet (pieces: no symbol): nothing was launched
         t_large_parts = 0;
         t_large_subparts = 0;
         return 1;
     }
-    if (produced > dst_cap) {
+    if (s.status == -5) {
         set_error("inflate output (%llu bytes) exceeds dst_cap", (unsigned long long)produced);
         return -5;
     }
-    const size_t nparts = copies.size();
-    const size_t nsegs = segs.size() / 3 - 1;
-    // ---- symbols in place, resolve, translate ---------------------------------------------------------------------
-    uint8_t *yp = nullptr;
-    const size_t sym_b = ((size_t)produced + 32768 + 64) * 2, segs_b = (segs.size() * 8 + 255) & ~(size_t)255,
-                 cp_b = (nparts * sizeof(PartCopy) + 255) & ~(size_t)255;
-    if (scratch_reserve(ws, kScrLargeSym, segs_b + cp_b + sym_b, false, (void **)&yp) != ZNG_ROCM_OK) return why("no room for the symbols");
-    uint64_t *d_segs = (uint64_t *)yp;
-    PartCopy *d_cp = (PartCopy *)(yp + segs_b);
-    uint16_t *sym = (uint16_t *)(yp + segs_b + cp_b) + 32768;
-    ZR_HIP(hipMemcpyAsync(d_segs, segs.data(), segs.size() * 8, hipMemcpyHostToDevice, st));
-    ZR_HIP(hipMemcpyAsync(d_cp, copies.data(), nparts * sizeof(PartCopy), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(compact_parts_kernel, dim3(16, (unsigned)nparts), dim3(256), 0, st, d_cp, sym);
-    ZR_HIP(hipGetLastError());
-    if (int rc = inflate_resolve_symbols(d_segs, nsegs, sym, d_dst, d_window, window_len, st)) return rc;
-    ZR_HIP(hipStreamSynchronize(st));
-    t_large_parts = (int)nparts;
-    t_large_subparts = (int)subparts;
+    t_large_parts = (int)s.chain.copies.size();
+    t_large_subparts = (int)s.chain.subparts;
     return 1;
 }
 
@@ -1115,22 +1241,11 @@ int zng_rocm_inflate_large_ex_dev(const uint8_t *d_src, size_t src_len, const ui
 }  // extern "C"
 
 // ---- many large streams: zng_rocm_inflate_large_streams_dev ---------------------------------------------------------------
-// The device path of inflate_large_try (stream mode; no pieces, no blocks) for a ROUND of streams at once: ONE finder pass
-// over a table of (stream, range) items whose survivors carry their stream, ONE part launch over the parts of all streams
-// (each stream's starts together; a part looks for its end among its own stream's only: InflateJobDev::flags), one chain per
-// stream on the host, ONE compaction and ONE resolve over a symbol array that holds the streams one behind the other, each
-// behind its own 32768-symbol window gap (the layout of inflate_resolve_batch).  So the long parts of one stream run under
-// the short parts of the others, and the host round trips between the kernels are paid per round.  A stream the device
-// path cannot do leaves the round and is decoded as zng_rocm_inflate_large_ex_dev does it (a host copy, the sequential
-// decoder) behind the round's device work; the others do not notice.
-namespace zr {
-int inflate_resolve_symbols_batch(const uint64_t *d_segs, size_t nsegs, uint16_t *sym, const uint64_t *d_seg_dst,
-                                  const uint64_t *d_seg_end, const void *d_streams, size_t nstreams, hipStream_t st);
-int inflate_raw_window_sequential_msg(const uint8_t *src, size_t src_len, const uint8_t *d_window, uint32_t window_len,
-                                      uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, size_t *in_used, const char **msg,
-                                      hipStream_t st);
-}  // namespace zr
-
+// A ROUND of streams at once: ONE finder pass over a table of (stream, range) items whose survivors carry their stream,
+// then ONE pass (pass_run: stream mode; no pieces, no blocks) over the parts of all the round's streams.  So the long parts
+// of one stream run under the short parts of the others, and the host round trips between the kernels are paid per round.
+// A stream the device path cannot do leaves the round and is decoded as zng_rocm_inflate_large_ex_dev does it (a host
+// copy, the sequential decoder) behind the round's device work; the others do not notice.
 // kRoundMin / kRoundEnd / kRoundDefault: inflate_large_limits.h
 static thread_local int t_batch_rounds = 0;
 static thread_local int t_batch_part_launches = 0;
@@ -1146,66 +1261,47 @@ void inflate_large_reset_counters() {
 }
 }  // namespace zr
 
-namespace {
-
-struct RoundStream {
-    size_t job = 0;                                       // index in the caller's array
-    bool dev = true;                                      // still on the device path
-    bool patterns_do = false;
-    uint16_t b0 = 0;                                      // the stream's first two bytes (SUBBLOCK, when F1 + F2 ran)
-    std::vector<unsigned long long> good, starts, keys;
-    size_t heavy = 1;
-    uint32_t pbase = 0;                                   // its first part in the round's tables
-    Chain chain;                                          // its walk (walk_chain)
-    std::vector<size_t> seg_first;
-    bool placed = false;                                  // has symbols in the round's array
-};
-
-struct BatchWindowDev {                                   // BatchStream of inflate_resolve.hip
-    uint64_t       v_start;
-    const uint8_t *d_window;
-    uint64_t       window_len;
-};
-
-}  // namespace
-
-// One finder pass over the streams `which` (indices into rs): the patterns alone, or F1 + F2 (and, `bytes`, every stream's
-// first two bytes).  Fills rs[..].good with each stream's survivors, sorted; a stream whose list cannot be had leaves
-// the device path.  One synchronisation (a second one when the list is longer than what comes back with the counts).
-static int round_find(Workspace *ws, zng_rocm_inflate_large_job *jobs, std::vector<RoundStream> &rs, const std::vector<size_t> &which,
-                      bool patterns, bool bytes, hipStream_t st) {
+// One finder pass over the streams `which` (indices into ss and good): the patterns alone, or F1 + F2 (and, `bytes`, every
+// stream's first two bytes).  Fills good[..] with each stream's survivors, sorted; when the lists cannot be had the streams
+// leave the device path.  One synchronisation (a second one when the list is longer than what comes back with the counts).
+static int round_find(Workspace *ws, std::vector<PassStream> &ss, std::vector<std::vector<unsigned long long>> &good,
+                      const std::vector<size_t> &which, bool patterns, bool bytes, hipStream_t st) {
     const size_t ns = which.size();
     if (!ns) return ZNG_ROCM_OK;
     uint64_t total = 0;
-    for (size_t w : which) total += jobs[rs[w].job].src_len;
+    for (size_t w : which) total += ss[w].src_len;
     const uint64_t item_bytes = std::max<uint64_t>(4096, std::min<uint64_t>(65536, (total / 4096 + 4095) & ~4095ull));
     std::vector<FindItemDev> items;
     for (size_t k = 0; k < ns; ++k) {
-        const uint64_t len = jobs[rs[which[k]].job].src_len;
+        const uint64_t len = ss[which[k]].src_len;
         for (uint64_t lo = 0; lo < len; lo += item_bytes) items.push_back(FindItemDev{lo, std::min(lo + item_bytes, len), (uint32_t)k, 0u});
     }
     const uint32_t cap1 = (uint32_t)(total / 64 + 4096 * ns), cap2 = (uint32_t)(total / 512 + 4096 * ns);
     const uint32_t first = (uint32_t)std::min<size_t>(cap2, 16384 + 64 * ns);
-    const size_t tab_b = (ns * sizeof(FindStreamDev) + 255) & ~(size_t)255, items_b = (items.size() * sizeof(FindItemDev) + 255) & ~(size_t)255,
-                 b0_b = (ns * 2 + 255) & ~(size_t)255;
+    // streams | items | counts | first bytes on both sides; behind them the candidates (device), the first survivors (pinned)
+    TableLayout dl;
+    const size_t o_tab = dl.add(ns * sizeof(FindStreamDev)), o_items = dl.add(items.size() * sizeof(FindItemDev)), o_n = dl.add(64),
+                 o_b0 = dl.add(ns * 2);
+    TableLayout hl = dl;
+    const size_t o_cand = dl.add((size_t)cap1 * 8), o_good = dl.add((size_t)cap2 * 8), o_hgood = hl.add((size_t)first * 8);
     uint8_t *fp = nullptr, *hp = nullptr;
     auto out = [&](const char *reason) {
-        for (size_t w : which) rs[w].dev = false;
+        for (size_t w : which) ss[w].left = true;
         return why(reason);
     };
-    if (scratch_reserve(ws, kScrLargeCand, tab_b + items_b + 64 + b0_b + ((size_t)cap1 + cap2) * 8, false, (void **)&fp) != ZNG_ROCM_OK ||
-        scratch_reserve(ws, kScrLargeCandHost, tab_b + items_b + 64 + b0_b + (size_t)first * 8, true, (void **)&hp) != ZNG_ROCM_OK)
+    if (scratch_reserve(ws, kScrLargeCand, dl.bytes, false, (void **)&fp) != ZNG_ROCM_OK ||
+        scratch_reserve(ws, kScrLargeCandHost, hl.bytes, true, (void **)&hp) != ZNG_ROCM_OK)
         return out("no room for the round's candidates");
-    FindStreamDev *d_tab = (FindStreamDev *)fp, *h_tab = (FindStreamDev *)hp;
-    FindItemDev *d_items = (FindItemDev *)(fp + tab_b);
-    uint32_t *d_n = (uint32_t *)(fp + tab_b + items_b), *n12 = (uint32_t *)(hp + tab_b + items_b);
-    uint16_t *d_b0 = (uint16_t *)(fp + tab_b + items_b + 64), *h_b0 = (uint16_t *)(hp + tab_b + items_b + 64);
-    unsigned long long *d_cand = (unsigned long long *)(fp + tab_b + items_b + 64 + b0_b), *d_good = d_cand + cap1;
-    unsigned long long *h_good = (unsigned long long *)(hp + tab_b + items_b + 64 + b0_b);
-    for (size_t k = 0; k < ns; ++k) h_tab[k] = FindStreamDev{jobs[rs[which[k]].job].d_src, jobs[rs[which[k]].job].src_len};
-    std::copy(items.begin(), items.end(), (FindItemDev *)(hp + tab_b));
+    FindStreamDev *d_tab = (FindStreamDev *)(fp + o_tab), *h_tab = (FindStreamDev *)(hp + o_tab);
+    FindItemDev *d_items = (FindItemDev *)(fp + o_items);
+    uint32_t *d_n = (uint32_t *)(fp + o_n), *n12 = (uint32_t *)(hp + o_n);
+    uint16_t *d_b0 = (uint16_t *)(fp + o_b0), *h_b0 = (uint16_t *)(hp + o_b0);
+    unsigned long long *d_cand = (unsigned long long *)(fp + o_cand), *d_good = (unsigned long long *)(fp + o_good);
+    unsigned long long *h_good = (unsigned long long *)(hp + o_hgood);
+    for (size_t k = 0; k < ns; ++k) h_tab[k] = FindStreamDev{ss[which[k]].d_src, ss[which[k]].src_len};
+    std::copy(items.begin(), items.end(), (FindItemDev *)(hp + o_items));
     n12[0] = n12[1] = 0;
-    ZR_HIP(hipMemcpyAsync(fp, hp, tab_b + items_b, hipMemcpyHostToDevice, st));
+    ZR_HIP(hipMemcpyAsync(fp, hp, o_n, hipMemcpyHostToDevice, st));              // streams | items
     ZR_HIP(hipMemsetAsync(d_n, 0, 8, st));
     if (patterns) {
         hipLaunchKernelGGL(find_headers_table_kernel<true>, dim3((unsigned)items.size()), dim3(256), 0, st, d_tab, d_items, d_good, d_n + 1, cap2);
@@ -1233,314 +1329,73 @@ static int round_find(Workspace *ws, zng_rocm_inflate_large_job *jobs, std::vect
         ZR_HIP(hipStreamSynchronize(st));
     }
     for (size_t k = 0; k < ns; ++k) {
-        rs[which[k]].good.clear();
-        if (bytes && !patterns) rs[which[k]].b0 = h_b0[k];
+        good[which[k]].clear();
+        if (bytes && !patterns) ss[which[k]].b0 = h_b0[k];
     }
     for (uint32_t i = 0; i < n2; ++i) {
         const unsigned long long c = i < first ? h_good[i] : rest[i - first];
         const size_t k = (size_t)((c & kFindTagMask) >> kFindTagShift);
-        if (k < ns) rs[which[k]].good.push_back(c & ~kFindTagMask & ~(1ull << 63));
+        if (k < ns) good[which[k]].push_back(c & ~kFindTagMask & ~(1ull << 63));
     }
-    for (size_t w : which) std::sort(rs[w].good.begin(), rs[w].good.end(), by_bit);
+    for (size_t w : which) std::sort(good[w].begin(), good[w].end(), by_bit);
     return ZNG_ROCM_OK;
 }
 
-// One round: the jobs idx[0 .. *taken) (all of idx unless their parts together pass one launch's).  Jobs done on the device
-// have their output fields set; the others are appended to `host` (the caller decodes them sequentially).
+// One round: the jobs idx[0 .. *taken) (all of idx unless their parts together pass one launch's) through the table finder
+// and the pass.  Jobs done on the device have their output fields set; the others are appended to `host` (the caller
+// decodes them sequentially, as zng_rocm_inflate_large_ex_dev does it, behind the round's device work).
 static int round_run(Workspace *ws, zng_rocm_inflate_large_job *jobs, const std::vector<size_t> &idx, bool sub, hipStream_t st,
                      std::vector<size_t> &host, size_t *taken) {
-    *taken = idx.size();
-    const size_t cus = (size_t)ctx()->cus;
-    std::vector<RoundStream> rs(idx.size());
+    std::vector<PassStream> ss(idx.size());
+    std::vector<std::vector<unsigned long long>> good(idx.size());
     std::vector<size_t> scan;
     for (size_t k = 0; k < idx.size(); ++k) {
-        rs[k].job = idx[k];
-        if (!large_length_ok(jobs[idx[k]].src_len)) rs[k].dev = false;
+        const zng_rocm_inflate_large_job &J = jobs[idx[k]];
+        PassStream &s = ss[k];
+        s.d_src = J.d_src;
+        s.src_len = J.src_len;
+        s.d_window = J.d_window;
+        s.window_len = J.window_len;
+        s.d_dst = J.d_dst;
+        s.dst_cap = J.dst_cap;
+        s.job = (long)idx[k];
+        if (!large_length_ok(J.src_len)) s.left = true;
         else scan.push_back(k);
     }
     // ---- candidates: the byte patterns for every stream; F1 + F2 for those they do not cut ---------------------------
-    if (int rc = round_find(ws, jobs, rs, scan, true, false, st)) return rc;
+    if (int rc = round_find(ws, ss, good, scan, true, false, st)) return rc;
     std::vector<size_t> full;
     for (size_t k : scan) {
-        RoundStream &s = rs[k];
-        if (!s.dev) continue;
-        const size_t len = jobs[s.job].src_len;
-        s.patterns_do = s.good.size() <= patterns_first(len) && patterns_cut(s.good, 0, 8ull * len);
+        PassStream &s = ss[k];
+        if (s.left) continue;
+        s.patterns_do = good[k].size() <= patterns_first(s.src_len) && patterns_cut(good[k], 0, 8ull * s.src_len);
         if (!s.patterns_do) full.push_back(k);
     }
-    if (int rc = round_find(ws, jobs, rs, full, false, sub, st)) return rc;
-    uint64_t round_bits = 0;
-    size_t round_heavy = 0;
+    if (int rc = round_find(ws, ss, good, full, false, sub, st)) return rc;
     for (size_t k : scan) {
-        RoundStream &s = rs[k];
-        if (!s.dev) continue;
-        const size_t len = jobs[s.job].src_len;
-        if (s.good.size() > len / 512 + 4096) {
-            s.dev = false;
-            why("far more valid block headers than a deflate stream has");
+        PassStream &s = ss[k];
+        if (s.left) continue;
+        if (good[k].size() > s.src_len / 512 + 4096) leave(s, "far more valid block headers than a deflate stream has");
+        else thin_starts(good[k], 0, s.src_len, s.starts, s.heavy);
+    }
+    int launches = 0;
+    const int rc = pass_run(ws, ss, sub, false, nullptr, st, taken, &launches);
+    t_batch_part_launches += launches;
+    if (rc) return rc;
+    for (size_t k = 0; k < *taken; ++k) {
+        const PassStream &s = ss[k];
+        zng_rocm_inflate_large_job &J = jobs[idx[k]];
+        if (s.left) {
+            host.push_back(idx[k]);
             continue;
         }
-        thin_starts(s.good, 0, len, s.starts, s.heavy);
-        round_bits += 8ull * len;
-        round_heavy += s.heavy;
-    }
-    // ---- SUBBLOCK: guesses in the gaps (plan_sub_regions), with a step that fills the chip once per ROUND (a stream never
-    // gets a coarser step than a sixteenth of itself: a small stream among large ones is still cut) ----
-    if (sub) {
-        const unsigned long long round_step = std::max<unsigned long long>(kSubMinStep, round_bits / (kSubPerSlot * 12ull * cus));
-        const uint32_t split_dynamic = round_heavy <= 12u * cus ? 1u : 0u;
-        std::vector<SubRegionDev> regions;
-        std::vector<std::pair<uint32_t, uint32_t>> span(rs.size(), {0u, 0u});      // a stream's guess slots
-        uint32_t nguess = 0;
-        for (size_t k : scan) {
-            RoundStream &s = rs[k];
-            if (!s.dev) continue;
-            const zng_rocm_inflate_large_job &J = jobs[s.job];
-            s.keys.assign(s.starts.size(), 0ull);
-            span[k].first = nguess;
-            const unsigned long long step = std::max<unsigned long long>(kSubMinStep, std::min<unsigned long long>(round_step, 8ull * J.src_len / 16));
-            const bool fixed_first = !s.patterns_do && ((unsigned)s.b0 >> 1 & 3u) == 1u;
-            if (!s.patterns_do)
-                plan_sub_regions(s.starts, 8ull * J.src_len, step, split_dynamic, fixed_first, 0, J.d_src, J.src_len, regions, nguess);
-            span[k].second = nguess;
-        }
-        if (nguess) {
-            const size_t reg_b = (regions.size() * sizeof(SubRegionDev) + 255) & ~(size_t)255, out_b = (size_t)nguess * 16;
-            uint8_t *dp = nullptr, *hp2 = nullptr;
-            if (scratch_reserve(ws, kScrLargeSub, reg_b + out_b, false, (void **)&dp) != ZNG_ROCM_OK ||
-                scratch_reserve(ws, kScrLargeSubHost, reg_b + out_b, true, (void **)&hp2) != ZNG_ROCM_OK) {
-                nguess = 0;                               // (no sub-starts: the streams go on with the starts found)
-            } else {
-                std::copy(regions.begin(), regions.end(), (SubRegionDev *)hp2);
-                unsigned long long *d_bit = (unsigned long long *)(dp + reg_b), *h_bit = (unsigned long long *)(hp2 + reg_b);
-                ZR_HIP(hipMemcpyAsync(dp, hp2, regions.size() * sizeof(SubRegionDev), hipMemcpyHostToDevice, st));
-                if (int rc = launch_subblock_sync(nullptr, 0, (const SubRegionDev *)dp, regions.size(), d_bit, d_bit + nguess, st)) return rc;
-                ZR_HIP(hipMemcpyAsync(h_bit, d_bit, out_b, hipMemcpyDeviceToHost, st));
-                ZR_HIP(hipStreamSynchronize(st));
-                for (size_t k : scan) {
-                    RoundStream &s = rs[k];
-                    if (!s.dev || span[k].first == span[k].second) continue;
-                    merge_sub_starts(s.starts, s.keys, h_bit, h_bit + nguess, span[k].first, span[k].second, 0, jobs[s.job].src_len, s.heavy);
-                }
-            }
-        }
-    }
-    // ---- the round's parts: each stream's together, the streams one behind the other ------------------------------------
-    size_t np = 0, heavy = 0;
-    std::vector<size_t> on;                               // streams in the part launch
-    for (size_t k : scan) {
-        RoundStream &s = rs[k];
-        if (!s.dev) continue;
-        if (s.starts.size() < 4) {
-            s.dev = false;
-            why("fewer than four block starts found");
-            continue;
-        }
-        if (np + s.starts.size() > kPieceMaxParts) {      // more parts than one launch (and the compaction grid) takes
-            if (on.empty()) {
-                s.dev = false;                            // one stream alone has them: not a stream for this call's device path
-                why("more parts in one stream than one launch takes");
-                continue;
-            }
-            *taken = k;                                   // this job and the ones behind it: the next round
-            break;
-        }
-        s.pbase = (uint32_t)np;
-        np += s.starts.size();
-        heavy += s.heavy;
-        on.push_back(k);
-    }
-    rs.resize(*taken);
-    auto to_host = [&]() {
-        for (const RoundStream &s : rs)
-            if (!s.dev) host.push_back(s.job);
-    };
-    if (on.empty()) {
-        to_host();
-        return ZNG_ROCM_OK;
-    }
-    auto all_out = [&](const char *reason) {
-        for (size_t k : on) rs[k].dev = false;
-        why(reason);
-        to_host();
-        return ZNG_ROCM_OK;
-    };
-    const bool many = heavy > 12u * cus;
-    std::vector<uint64_t> slot_off(np + 1, 0), part_bytes(np, 0);
-    for (size_t k : on) {
-        const RoundStream &s = rs[k];
-        slot_caps(s.starts.data(), s.starts.size(), 8ull * jobs[s.job].src_len, slot_slack(np, nullptr), &slot_off[s.pbase],
-                  &part_bytes[s.pbase]);
-    }
-    uint8_t *sp = nullptr, *hq = nullptr;
-    const size_t jobs_b = (np * sizeof(InflateJobDev) + 255) & ~(size_t)255, starts_b = (np * (sub ? 16 : 8) + 255) & ~(size_t)255,
-                 res_b = (np * 32 + (sub ? np * 32 : 0) + 255) & ~(size_t)255, slots_b = slot_off[np] * 2;
-    if (scratch_reserve(ws, kScrLargeParts, jobs_b + starts_b + res_b + slots_b, false, (void **)&sp) != ZNG_ROCM_OK)
-        return all_out("no room for the round's part slots");
-    if (scratch_reserve(ws, kScrLargePartsHost, jobs_b + starts_b + res_b, true, (void **)&hq) != ZNG_ROCM_OK)
-        return all_out("no pinned memory for the round's part tables");
-    InflateJobDev *d_jobs = (InflateJobDev *)sp, *pj = (InflateJobDev *)hq;
-    unsigned long long *d_starts = (unsigned long long *)(sp + jobs_b), *h_starts = (unsigned long long *)(hq + jobs_b);
-    uint32_t *d_res = (uint32_t *)(sp + jobs_b + starts_b), *res = (uint32_t *)(hq + jobs_b + starts_b);
-    uint16_t *d_slots = (uint16_t *)(sp + jobs_b + starts_b + res_b);
-    uint32_t *d_side = sub ? d_res + 8 * np : nullptr, *side = res + 8 * np;
-    const size_t res_words = sub ? 16 : 8;
-    for (size_t k : on) {
-        const RoundStream &s = rs[k];
-        const zng_rocm_inflate_large_job &J = jobs[s.job];
-        const size_t n = s.starts.size();
-        std::copy(s.starts.begin(), s.starts.end(), h_starts + s.pbase);
-        if (sub) std::copy(s.keys.begin(), s.keys.end(), h_starts + np + s.pbase);
-        for (size_t i = 0; i < n; ++i)
-            pj[s.pbase + i] = InflateJobDev{J.d_src, (uint8_t *)(d_slots + slot_off[s.pbase + i]), J.src_len,
-                                            slot_off[s.pbase + i + 1] - slot_off[s.pbase + i], i == 0 ? J.window_len : 32768u,
-                                            (uint32_t)(s.pbase + n)};
-    }
-    ZR_HIP(hipMemcpyAsync(sp, hq, jobs_b + np * (sub ? 16 : 8), hipMemcpyHostToDevice, st));      // jobs | starts (| keys)
-    if (int rc = launch_inflate_parts_device(d_jobs, np, d_res, d_starts, many, st, nullptr, d_side)) return rc;
-    ++t_batch_part_launches;
-    ZR_HIP(hipMemcpyAsync(res, d_res, np * 4 * res_words, hipMemcpyDeviceToHost, st));
-    ZR_HIP(hipStreamSynchronize(st));
-    // parts whose slot was too small, of all streams: ONE launch more, with retry_cap's room.  A
-    // stream whose parts want more than is reasonable leaves the round; the others' parts are run again without it.
-    std::vector<uint16_t *> slot_ptr(np);
-    for (size_t i = 0; i < np; ++i) slot_ptr[i] = d_slots + slot_off[i];
-    {
-        std::vector<size_t> again;
-        uint64_t need = 0;
-        for (size_t k : on) {
-            RoundStream &s = rs[k];
-            uint64_t own = 0;
-            for (size_t i = s.pbase; i < s.pbase + s.starts.size(); ++i)
-                if (res[8 * i + 4] == kMsgOutFull) own += retry_cap(part_bytes[i]);
-            if (own * 2 > (24ull << 30)) {
-                s.dev = false;
-                why("parts with a ratio above 64 need more scratch than is reasonable");
-                continue;
-            }
-            for (size_t i = s.pbase; i < s.pbase + s.starts.size() && own; ++i)
-                if (res[8 * i + 4] == kMsgOutFull) again.push_back(i);
-            need += own;
-        }
-        if (!again.empty()) {
-            uint8_t *bigp = nullptr;
-            if (scratch_reserve(ws, kScrLargeRetry, need * 2, false, (void **)&bigp) != ZNG_ROCM_OK) {
-                for (size_t k : on) {                    // (the streams that asked leave; the others are complete)
-                    bool asked = false;
-                    for (size_t i = rs[k].pbase; i < rs[k].pbase + rs[k].starts.size(); ++i) asked |= res[8 * i + 4] == kMsgOutFull;
-                    if (asked) rs[k].dev = false;
-                }
-                why("no room for the parts with a ratio above 64");
-            } else {
-                for (size_t i = 0; i < np; ++i) pj[i].out_cap = 0;
-                uint64_t at = 0;
-                for (size_t i : again) {
-                    const uint64_t capi = retry_cap(part_bytes[i]);
-                    slot_ptr[i] = (uint16_t *)bigp + at;
-                    pj[i].out = (uint8_t *)slot_ptr[i];
-                    pj[i].out_cap = capi;
-                    at += capi;
-                }
-                ZR_HIP(hipMemcpyAsync(d_jobs, pj, np * sizeof(InflateJobDev), hipMemcpyHostToDevice, st));
-                if (int rc = launch_inflate_parts_device(d_jobs, np, d_res, d_starts, many, st, nullptr, d_side)) return rc;
-                ++t_batch_part_launches;
-                ZR_HIP(hipMemcpyAsync(res, d_res, np * 4 * res_words, hipMemcpyDeviceToHost, st));
-                ZR_HIP(hipStreamSynchronize(st));
-            }
-        }
-    }
-    // ---- one chain per stream: stream mode, and a stream whose walk fails leaves the round ---------------------------------
-    for (size_t k : on) {
-        RoundStream &s = rs[k];
-        if (!s.dev) continue;
-        zng_rocm_inflate_large_job &J = jobs[s.job];
-        const unsigned long long *keys = sub ? s.keys.data() : nullptr;
-        if (!walk_chain(res, side, nullptr, slot_ptr.data(), s.pbase, s.starts.size(), s.starts.data(), keys, J.window_len, J.src_len,
-                        sub, false, nullptr, s.chain)) {
-            why_chain(s.chain, s.starts.size(), s.starts.data(), keys, res + 8 * s.pbase, pj + s.pbase, (long)s.job);
-            s.dev = false;
-            continue;
-        }
+        J.status = s.status;
         J.out_len = s.chain.produced;
         J.in_used = (size_t)((s.chain.end_bit + 7) >> 3);
         J.msg = nullptr;
         J.parts = (uint32_t)s.chain.copies.size();
         J.subparts = (uint32_t)s.chain.subparts;
-        if (s.chain.produced > J.dst_cap) {               // this job's trouble alone: nothing of it is written
-            J.status = -5;
-            continue;
-        }
-        J.status = 1;
-        if (!s.chain.produced) continue;
-        s.seg_first = group_segments(s.chain.copies, s.chain.produced);
-        s.placed = true;
     }
-    // ---- the streams one behind the other in ONE symbol array; compaction, resolve, translate ----------------------------
-    std::vector<uint64_t> segs, seg_dst, seg_end;
-    std::vector<BatchWindowDev> wins;
-    std::vector<PartCopy> copies;
-    uint64_t v = 32768, v_end = 0;
-    for (size_t k : on) {
-        RoundStream &s = rs[k];
-        if (!s.placed) continue;
-        const zng_rocm_inflate_large_job &J = jobs[s.job];
-        wins.push_back(BatchWindowDev{v, J.window_len ? J.d_window : nullptr, J.window_len});
-        const uint32_t c0 = (uint32_t)copies.size();
-        for (size_t g = 0; g + 1 < s.seg_first.size(); ++g) {
-            const std::vector<PartCopy> &sc = s.chain.copies;
-            const uint64_t o0 = sc[s.seg_first[g]].dst;
-            const uint64_t o1 = g + 2 < s.seg_first.size() ? sc[s.seg_first[g + 1]].dst : s.chain.produced;
-            for (size_t c = s.seg_first[g]; c < s.seg_first[g + 1]; ++c) {
-                PartCopy p = sc[c];
-                p.dst += v;
-                p.gstart = v + o0;
-                p.first = c0 + (uint32_t)s.seg_first[g];
-                copies.push_back(p);
-            }
-            segs.push_back(0);
-            segs.push_back(v + o0);
-            segs.push_back(0);
-            seg_dst.push_back((uint64_t)(uintptr_t)(J.d_dst + o0));
-            seg_end.push_back(v + o1);
-        }
-        v_end = v + s.chain.produced;
-        v = v_end + 32768;                                // (a stream's last segment runs on through the gap behind it)
-    }
-    if (!copies.empty()) {
-        if (copies.size() > kPieceMaxParts) return all_out("more parts on the chains than the compaction grid takes");
-        segs.push_back(0);
-        segs.push_back(v_end);
-        segs.push_back(0);
-        const size_t nsegs = seg_dst.size();
-        const size_t segs_b = (segs.size() * 8 + 255) & ~(size_t)255, sd_b = (nsegs * 8 + 255) & ~(size_t)255,
-                     win_b = (wins.size() * sizeof(BatchWindowDev) + 255) & ~(size_t)255,
-                     cp_b = (copies.size() * sizeof(PartCopy) + 255) & ~(size_t)255, sym_b = ((size_t)v_end + 64) * 2;
-        uint8_t *yp = nullptr;
-        if (scratch_reserve(ws, kScrLargeSym, segs_b + 2 * sd_b + win_b + cp_b + sym_b, false, (void **)&yp) != ZNG_ROCM_OK) {
-            for (size_t k : on)
-                if (rs[k].placed) rs[k].dev = false;     // (the -5 jobs keep their status)
-            why("no room for the round's symbols");
-            to_host();
-            return ZNG_ROCM_OK;
-        }
-        uint64_t *d_segs = (uint64_t *)yp, *d_sd = (uint64_t *)(yp + segs_b), *d_se = (uint64_t *)(yp + segs_b + sd_b);
-        BatchWindowDev *d_win = (BatchWindowDev *)(yp + segs_b + 2 * sd_b);
-        PartCopy *d_cp = (PartCopy *)(yp + segs_b + 2 * sd_b + win_b);
-        uint16_t *sym = (uint16_t *)(yp + segs_b + 2 * sd_b + win_b + cp_b);
-        // (the five tables go up in ONE copy: each copy from pageable memory costs the host tens of microseconds)
-        std::vector<uint8_t> up(segs_b + 2 * sd_b + win_b + cp_b);
-        memcpy(up.data(), segs.data(), segs.size() * 8);
-        memcpy(up.data() + segs_b, seg_dst.data(), nsegs * 8);
-        memcpy(up.data() + segs_b + sd_b, seg_end.data(), nsegs * 8);
-        memcpy(up.data() + segs_b + 2 * sd_b, wins.data(), wins.size() * sizeof(BatchWindowDev));
-        memcpy(up.data() + segs_b + 2 * sd_b + win_b, copies.data(), copies.size() * sizeof(PartCopy));
-        ZR_HIP(hipMemcpyAsync(yp, up.data(), up.size(), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(compact_parts_kernel, dim3(16, (unsigned)copies.size()), dim3(256), 0, st, d_cp, sym);
-        ZR_HIP(hipGetLastError());
-        if (int rc = inflate_resolve_symbols_batch(d_segs, nsegs, sym, d_sd, d_se, d_win, wins.size(), st)) return rc;
-        ZR_HIP(hipStreamSynchronize(st));
-    }
-    to_host();
     return ZNG_ROCM_OK;
 }
 

@@ -1,8 +1,8 @@
-// inflate_large_plan.h -- the host steps between the kernel launches of inflate_large.hip, once for the one-stream path
-// (inflate_large_try: one pass, pieces, blocks mode) and the batch (round_run).  Plain C++ over integers and the part
-// tables, no HIP: every rule that decides what a valid result is -- which candidates become starts, where guesses go, how
-// large a slot is, which parts are genuine, how parts are grouped for the context chain -- lives here, and a CPU test
-// (tests/test_large_plan_cpu.py) drives the walk and the grouping with hand-written tables.
+// inflate_large_plan.h -- the host steps between the kernel launches of inflate_large.hip (pass_run, and the finders in front
+// of it).  Plain C++ over integers and the part tables, no HIP: every rule that decides what a valid result is -- which
+// candidates become starts, where guesses go, how large a slot is, where the tables lie in scratch, which parts run again,
+// which parts are genuine, how parts are grouped for the context chain and laid out in the symbol array -- lives here, and a
+// CPU test (tests/test_large_plan_cpu.py) drives them with hand-written tables.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -55,6 +55,42 @@ constexpr uint32_t kPieceMaxParts = 65535;                      // also the comp
 inline uint64_t piece_cap_sub(uint64_t q) { return q / 8 + (1u << 20); }
 inline uint64_t piece_cap_retry(uint64_t q) { return 32 * q; }
 inline uint64_t piece_cap_sym(uint64_t q) { return 48 * q; }
+
+// ---- scratch layouts ----------------------------------------------------------------------------------------------------
+// tables one behind the other in one scratch buffer, each at a multiple of 256 bytes: add() gives the next table's offset
+struct TableLayout {
+    size_t bytes = 0;
+    size_t add(size_t n) {
+        const size_t at = bytes;
+        bytes += (n + 255) & ~(size_t)255;
+        return at;
+    }
+};
+
+// The part tables of one launch over `np` parts: jobs | starts (| keys) | results (| marks, or | side words) | slots.  The
+// keys (SUBBLOCK: 8 bytes per part) follow the starts, and the marks (blocks mode: 4 words per part) or side words (SUBBLOCK:
+// 8 words per part) follow the 8 result words per part, so that jobs | starts | keys go up in one copy and results | marks
+// or side words come down in one.  The pinned mirror has the same offsets without the slots.
+struct PartTables {
+    size_t jobs = 0, starts = 0, keys = 0, res = 0, extra = 0, slots = 0;      // byte offsets (keys / extra: where they would be)
+    size_t up_bytes = 0;                                  // jobs | starts (| keys), from offset 0
+    size_t res_words = 8;                                 // words per part that come down, from `res`
+    size_t mirror_bytes = 0, device_bytes = 0;
+};
+inline PartTables part_tables(size_t np, bool sub, bool blocks, uint64_t slot_symbols) {
+    PartTables t;
+    TableLayout l;
+    t.jobs = l.add(np * sizeof(InflateJobDev));
+    t.starts = l.add(np * (sub ? 16 : 8));
+    t.keys = t.starts + np * 8;
+    t.up_bytes = t.starts + np * (sub ? 16 : 8);
+    t.res_words = 8 + (blocks ? 4 : 0) + (sub ? 8 : 0);
+    t.res = l.add(np * 4 * t.res_words);
+    t.extra = t.res + np * 32;
+    t.slots = t.mirror_bytes = l.bytes;
+    t.device_bytes = t.mirror_bytes + (size_t)slot_symbols * 2;
+    return t;
+}
 
 // what the device path takes: shorter streams are the sequential decoder's, and a bit position has to fit the tables' words
 inline bool large_length_ok(uint64_t src_len) { return src_len >= (128u << 10) && src_len < (1ull << 31); }
@@ -179,6 +215,39 @@ inline void slot_caps(const unsigned long long *starts, size_t n, unsigned long 
 // a part whose slot was too small (more than kSlotRatio : 1) is run once more with room for deflate's worst case, 1032 : 1
 inline uint64_t retry_cap(uint64_t part_bytes) { return (part_bytes * 1032u + kSlotSlack + 7) & ~7ull; }
 
+// Which parts run again after a launch (result words `res`, 8 per part; part_bytes per part), for streams whose parts are
+// rows [first, first + n) of the tables (`spans`): every part that said kMsgOutFull, with retry_cap's room, one behind the
+// other in ONE retry buffer.  A stream whose parts together want more than `limit_bytes` is reported in `over` and
+// contributes nothing (it leaves the pass); the other streams' parts are still planned.
+struct RetryPlan {
+    std::vector<size_t> again;                            // rows of the tables
+    std::vector<uint64_t> off, cap;                       // per entry of `again`: place and room in the retry buffer, in symbols
+    uint64_t total = 0;                                   // symbols
+    std::vector<size_t> over;                             // indices into `spans`
+};
+inline RetryPlan plan_retry(const uint32_t *res, const std::vector<std::pair<size_t, size_t>> &spans, const uint64_t *part_bytes,
+                            uint64_t limit_bytes) {
+    RetryPlan r;
+    for (size_t k = 0; k < spans.size(); ++k) {
+        const size_t i0 = spans[k].first, i1 = i0 + spans[k].second;
+        uint64_t own = 0;
+        for (size_t i = i0; i < i1; ++i)
+            if (res[8 * i + 4] == kMsgOutFull) own += retry_cap(part_bytes[i]);
+        if (own * 2 > limit_bytes) {
+            r.over.push_back(k);
+            continue;
+        }
+        for (size_t i = i0; i < i1; ++i) {
+            if (res[8 * i + 4] != kMsgOutFull) continue;
+            r.again.push_back(i);
+            r.off.push_back(r.total);
+            r.cap.push_back(retry_cap(part_bytes[i]));
+            r.total += r.cap.back();
+        }
+    }
+    return r;
+}
+
 // ---- the chain from the stream's first part ---------------------------------------------------------------------------
 // Part 0 is genuine, the part that starts where it ended is therefore genuine too, ...; a candidate that was noise is never
 // reached.  Result words of a part (inflate_streams_kernel<PART>): r[0] symbols, r[1..2] the bit it ended on, r[3] = 1 when
@@ -188,7 +257,7 @@ inline uint64_t retry_cap(uint64_t part_bytes) { return (part_bytes * 1032u + kS
 // != 0 when the part handed off inside a block, whose BFINAL is s[5] (2: unknown).  Blocks mode marks: m[0] symbols of the
 // part's complete blocks, m[1..2] where they end, m[3] the reach within them.
 struct Chain {
-    std::vector<PartCopy> copies;                         // the genuine parts in order; gstart / first: group_segments' caller
+    std::vector<PartCopy> copies;                         // the genuine parts in order; gstart / first: symbol_tables
     uint64_t produced = 0;
     unsigned long long end_bit = 0;
     bool final = false;                                   // the BFINAL block is among what was delivered
@@ -232,8 +301,9 @@ inline bool walk_chain(const uint32_t *res, const uint32_t *side, const uint32_t
         }
         if (pp) {
             // pieces: the first part on the chain that ran out of the piece's input is where the next piece begins; so is a
-            // part whose symbols would take the symbol array past its cap (in the last piece too)
-            const bool full = r[4] == kMsgNone && ((c.produced + r[0] + 32768 + 64) * 2 + 64 * (c.copies.size() + 1) + 512 >
+            // part whose symbols would take the symbol array past its cap (in the last piece too; in front of the array lie
+            // the pass's tables: 32 bytes per copy, at most 40 per segment, the closing triple, the window entry and padding)
+            const bool full = r[4] == kMsgNone && ((c.produced + r[0] + 32768 + 64) * 2 + 72 * (c.copies.size() + 1) + 1536 >
                                                    piece_cap_sym(pp->q));
             if ((piece && r[4] == kMsgStarved) || full || (past && keys[cur] == 1u && fin == 1)) {
                 if (cur == 0) {
@@ -297,6 +367,57 @@ inline std::vector<size_t> group_segments(const std::vector<PartCopy> &copies, u
     if (seg_first.size() > 1 && produced - copies[seg_first.back()].dst < 32768u) seg_first.pop_back();
     seg_first.push_back(copies.size());
     return seg_first;
+}
+
+// ---- the symbol array ---------------------------------------------------------------------------------------------------
+// The streams of a pass one behind the other in ONE symbol array, each behind its own gap of 32768 symbols (its window: the
+// layout of inflate_resolve_batch), stream k at v_k = v_(k-1) + produced_(k-1) + 32768, the first at 32768.  A stream that
+// produced nothing has no place (v = 0).  Per stream in: the copies of its chain (dst counted from the stream's first
+// symbol), what it produced, and the address of its destination.  Out, for the compaction and the resolve:
+//   copies   all streams' copies, dst re-based to the array, gstart = the first symbol of the copy's segment and first = the
+//            index in `copies` of that segment's first copy (group_segments decides the segments)
+//   segs     a triple per segment as inflate_resolve.hip wants them -- only [3 s + 1], the segment's first symbol, is used --
+//            and the closing triple with v_end, the end of the last stream
+//   seg_dst  the address the segment's first byte goes to; seg_end: where its bytes end in the array (a stream's last segment
+//            runs on through the gap behind it for the context chain, its bytes do not)
+struct SymStream {
+    const std::vector<PartCopy> *copies;
+    uint64_t produced, dst;
+    uint64_t v = 0;                                       // out
+};
+struct SymTables {
+    std::vector<PartCopy> copies;
+    std::vector<uint64_t> segs, seg_dst, seg_end;
+    uint64_t v_end = 0;
+};
+inline SymTables symbol_tables(std::vector<SymStream> &streams) {
+    SymTables t;
+    uint64_t v = 32768;
+    for (SymStream &s : streams) {
+        if (!s.produced) continue;
+        s.v = v;
+        const std::vector<PartCopy> &sc = *s.copies;
+        const std::vector<size_t> seg_first = group_segments(sc, s.produced);
+        const uint32_t c0 = (uint32_t)t.copies.size();
+        for (size_t g = 0; g + 1 < seg_first.size(); ++g) {
+            const uint64_t o0 = sc[seg_first[g]].dst;
+            const uint64_t o1 = g + 2 < seg_first.size() ? sc[seg_first[g + 1]].dst : s.produced;
+            for (size_t c = seg_first[g]; c < seg_first[g + 1]; ++c) {
+                PartCopy p = sc[c];
+                p.dst += v;
+                p.gstart = v + o0;
+                p.first = c0 + (uint32_t)seg_first[g];
+                t.copies.push_back(p);
+            }
+            t.segs.insert(t.segs.end(), {0, v + o0, 0});
+            t.seg_dst.push_back(s.dst + o0);
+            t.seg_end.push_back(v + o1);
+        }
+        t.v_end = v + s.produced;
+        v = t.v_end + 32768;
+    }
+    if (!t.copies.empty()) t.segs.insert(t.segs.end(), {0, t.v_end, 0});
+    return t;
 }
 
 }  // namespace zr

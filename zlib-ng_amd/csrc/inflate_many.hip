@@ -28,13 +28,6 @@
 #include <thread>
 #include <vector>
 
-extern "C" int zng_rocm_inflate_resolve_window_dev(const uint32_t *d_tokens, size_t ntokens, const uint8_t *d_literals,
-                                                   size_t nliterals, const uint64_t *d_segs, size_t nsegs,
-                                                   uint16_t *d_symbols, uint8_t *d_out, uint64_t out_len,
-                                                   const uint8_t *d_window, uint32_t window_len, void *stream);
-int zr_inflate_decode_reuse(const uint8_t *src, size_t src_len, uint32_t window_len, zng_rocm_inflate_tokens *t,
-                            size_t caps[3], void *(*re)(void *, size_t, size_t));
-
 namespace zr {
 
 // The token arrays live in PINNED host memory and are kept across streams and calls: the copy to the device is a

@@ -16,19 +16,12 @@
 // Algorithmic bytes: C + U per stream; the symbol detour adds 4U of HBM traffic.
 #include "context.h"
 #include "deflate_dev.h"
+#include "inflate_dev.h"
 
 namespace zr {
 
 constexpr long long kCtx = 32768;        // MAX_WBITS 15: a distance never exceeds this
 constexpr size_t kLargeHostStream = 4u << 20;   // compressed bytes from which a host-resident stream is decoded on the device
-int inflate_large_from_host(const uint8_t *src, size_t src_len, const uint8_t *d_window, uint32_t window_len, uint8_t *d_dst,
-                            size_t dst_cap, uint64_t *out_len, size_t *in_used, hipStream_t st);      // inflate_large.hip
-void inflate_large_forget_parts();       // the part counter of the calling thread back to 0 ("the sequential decoder did it")
-int inflate_raw_window_sequential(const uint8_t *src, size_t src_len, const uint8_t *d_window, uint32_t window_len, uint8_t *d_dst,
-                                  size_t dst_cap, uint64_t *out_len, size_t *in_used, hipStream_t st);
-int inflate_raw_window_sequential_msg(const uint8_t *src, size_t src_len, const uint8_t *d_window, uint32_t window_len,
-                                      uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, size_t *in_used, const char **msg,
-                                      hipStream_t st);
 
 // K1.  One wavefront per segment, four per workgroup.  Per wave in LDS: a ring with the last 4096 symbols it
 // produced (recent back-references never touch HBM, and a match no longer waits for the wave's own stores to
@@ -231,12 +224,7 @@ void inflate_window_kernel(const uint8_t *__restrict__ window, uint32_t window_l
 }
 
 // the same for a BATCH of streams laid out one behind the other in symbol space, each behind its own 32768-symbol
-// window gap (see resolve_batch below): blockIdx.y = stream
-struct BatchStream {
-    uint64_t       v_start;     // symbol index of the stream's first byte
-    const uint8_t *d_window;    // its window_len bytes of history (device) or null
-    uint64_t       window_len;
-};
+// window gap (see resolve_batch below; BatchStream: inflate_dev.h): blockIdx.y = stream
 __global__ __launch_bounds__(256)
 void inflate_windows_kernel(const BatchStream *__restrict__ streams, uint16_t *__restrict__ sym) {
     const BatchStream b = streams[blockIdx.y];
@@ -338,6 +326,28 @@ void inflate_translate_kernel(const uint64_t *__restrict__ segs, size_t nsegs, c
         __builtin_nontemporal_store((uint8_t)resolve(sym[i], i), out + i);
 }
 
+// K2 + K3 behind symbols that are in place: the context groups, the chain over them, the translation (`traced`: that
+// launch may be timed, context.h)
+static int resolve_context_translate(const uint64_t *d_segs, size_t nsegs, uint16_t *sym, int has_window, uint8_t *d_out,
+                                     const uint64_t *d_seg_dst, const uint64_t *d_seg_end, bool traced, hipStream_t st) {
+    if (nsegs > 1) {
+        const unsigned ngroups = (unsigned)((nsegs - 1 + kGroup - 1) / kGroup);
+        hipLaunchKernelGGL(inflate_context_group_kernel, dim3(ngroups), dim3(1024), 0, st, d_segs, nsegs, sym, has_window);
+        ZR_HIP(hipGetLastError());
+        if (ngroups > 1) {
+            hipLaunchKernelGGL(inflate_context_chain_kernel, dim3(1), dim3(1024), 0, st, d_segs, nsegs, sym);
+            ZR_HIP(hipGetLastError());
+        }
+    }
+    if (traced)
+        ZR_LAUNCH_TRACED(inflate_translate_kernel, dim3((unsigned)nsegs), dim3(1024), st, d_segs, nsegs, sym, d_out, d_seg_dst, d_seg_end);
+    else
+        hipLaunchKernelGGL(inflate_translate_kernel, dim3((unsigned)nsegs), dim3(1024), 0, st, d_segs, nsegs, sym, d_out, d_seg_dst,
+                           d_seg_end);
+    ZR_HIP(hipGetLastError());
+    return ZNG_ROCM_OK;
+}
+
 // Device stage for a batch of independent streams in ONE set of launches (inflate_many.hip).  The streams sit one
 // behind the other in symbol space, stream k at v_start_k = v_start_(k-1) + len_(k-1) + 32768: the 32768 symbols in
 // front of each are its window (the caller's history, or zeros), and the LAST segment of every stream is extended
@@ -355,63 +365,17 @@ int inflate_resolve_batch(const uint32_t *d_tokens, const uint8_t *d_literals, s
     ZR_LAUNCH_TRACED(inflate_segments_kernel, dim3((unsigned)((nsegs + 3) / 4)), dim3(256), st, d_tokens, d_literals,
                      nliterals, d_segs, nsegs, sym);
     ZR_HIP(hipGetLastError());
-    if (nsegs > 1) {
-        const unsigned ngroups = (unsigned)((nsegs - 1 + kGroup - 1) / kGroup);
-        hipLaunchKernelGGL(inflate_context_group_kernel, dim3(ngroups), dim3(1024), 0, st, d_segs, nsegs, sym, 1);
-        ZR_HIP(hipGetLastError());
-        if (ngroups > 1) {
-            hipLaunchKernelGGL(inflate_context_chain_kernel, dim3(1), dim3(1024), 0, st, d_segs, nsegs, sym);
-            ZR_HIP(hipGetLastError());
-        }
-    }
-    hipLaunchKernelGGL(inflate_translate_kernel, dim3((unsigned)nsegs), dim3(1024), 0, st, d_segs, nsegs, sym,
-                       (uint8_t *)nullptr, d_seg_dst, d_seg_end);
-    ZR_HIP(hipGetLastError());
-    return ZNG_ROCM_OK;
+    return resolve_context_translate(d_segs, nsegs, sym, 1, nullptr, d_seg_dst, d_seg_end, false, st);
 }
 
-// symbols that are already in place (inflate_large.hip) -> bytes: the window in front, the context chain, the translation
-int inflate_resolve_symbols(const uint64_t *d_segs, size_t nsegs, uint16_t *sym, uint8_t *d_out, const uint8_t *d_window,
-                            uint32_t window_len, hipStream_t st) {
-    if (!nsegs) return ZNG_ROCM_OK;
-    hipLaunchKernelGGL(inflate_window_kernel, dim3((unsigned)(kCtx / 256)), dim3(256), 0, st, d_window, window_len, sym);
-    ZR_HIP(hipGetLastError());
-    if (nsegs > 1) {
-        const unsigned ngroups = (unsigned)((nsegs - 1 + kGroup - 1) / kGroup);
-        hipLaunchKernelGGL(inflate_context_group_kernel, dim3(ngroups), dim3(1024), 0, st, d_segs, nsegs, sym, 1);
-        ZR_HIP(hipGetLastError());
-        if (ngroups > 1) {
-            hipLaunchKernelGGL(inflate_context_chain_kernel, dim3(1), dim3(1024), 0, st, d_segs, nsegs, sym);
-            ZR_HIP(hipGetLastError());
-        }
-    }
-    ZR_LAUNCH_TRACED(inflate_translate_kernel, dim3((unsigned)nsegs), dim3(1024), st, d_segs, nsegs, sym, d_out,
-                     (const uint64_t *)nullptr, (const uint64_t *)nullptr);
-    ZR_HIP(hipGetLastError());
-    return ZNG_ROCM_OK;
-}
-
-// the same for the streams of a batch whose symbols are in place (inflate_large.hip, zng_rocm_inflate_large_streams_dev):
-// the layout of inflate_resolve_batch above, without K1
+// the same for streams whose symbols are in place (inflate_large.hip: one stream or a round of them): the layout of
+// inflate_resolve_batch above, without K1
 int inflate_resolve_symbols_batch(const uint64_t *d_segs, size_t nsegs, uint16_t *sym, const uint64_t *d_seg_dst,
-                                  const uint64_t *d_seg_end, const void *d_streams, size_t nstreams, hipStream_t st) {
+                                  const uint64_t *d_seg_end, const BatchStream *d_streams, size_t nstreams, hipStream_t st) {
     if (!nsegs || !nstreams) return ZNG_ROCM_OK;
-    hipLaunchKernelGGL(inflate_windows_kernel, dim3((unsigned)(kCtx / 256), (unsigned)nstreams), dim3(256), 0, st,
-                       (const BatchStream *)d_streams, sym);
+    hipLaunchKernelGGL(inflate_windows_kernel, dim3((unsigned)(kCtx / 256), (unsigned)nstreams), dim3(256), 0, st, d_streams, sym);
     ZR_HIP(hipGetLastError());
-    if (nsegs > 1) {
-        const unsigned ngroups = (unsigned)((nsegs - 1 + kGroup - 1) / kGroup);
-        hipLaunchKernelGGL(inflate_context_group_kernel, dim3(ngroups), dim3(1024), 0, st, d_segs, nsegs, sym, 1);
-        ZR_HIP(hipGetLastError());
-        if (ngroups > 1) {
-            hipLaunchKernelGGL(inflate_context_chain_kernel, dim3(1), dim3(1024), 0, st, d_segs, nsegs, sym);
-            ZR_HIP(hipGetLastError());
-        }
-    }
-    ZR_LAUNCH_TRACED(inflate_translate_kernel, dim3((unsigned)nsegs), dim3(1024), st, d_segs, nsegs, sym, (uint8_t *)nullptr,
-                     d_seg_dst, d_seg_end);
-    ZR_HIP(hipGetLastError());
-    return ZNG_ROCM_OK;
+    return resolve_context_translate(d_segs, nsegs, sym, 1, nullptr, d_seg_dst, d_seg_end, true, st);
 }
 
 }  // namespace zr
@@ -433,20 +397,7 @@ static int resolve_impl(const uint32_t *d_tokens, const uint8_t *d_literals, siz
     ZR_LAUNCH_TRACED(inflate_segments_kernel, dim3((unsigned)((nsegs + 3) / 4)), dim3(256), st, d_tokens, d_literals,
                      nliterals, d_segs, nsegs, sym);
     ZR_HIP(hipGetLastError());
-    if (nsegs > 1) {
-        const unsigned ngroups = (unsigned)((nsegs - 1 + kGroup - 1) / kGroup);
-        hipLaunchKernelGGL(inflate_context_group_kernel, dim3(ngroups), dim3(1024), 0, st, d_segs, nsegs, sym,
-                           has_window ? 1 : 0);
-        ZR_HIP(hipGetLastError());
-        if (ngroups > 1) {
-            hipLaunchKernelGGL(inflate_context_chain_kernel, dim3(1), dim3(1024), 0, st, d_segs, nsegs, sym);
-            ZR_HIP(hipGetLastError());
-        }
-    }
-    hipLaunchKernelGGL(inflate_translate_kernel, dim3((unsigned)nsegs), dim3(1024), 0, st, d_segs, nsegs, sym, d_out,
-                       (const uint64_t *)nullptr, (const uint64_t *)nullptr);
-    ZR_HIP(hipGetLastError());
-    return ZNG_ROCM_OK;
+    return resolve_context_translate(d_segs, nsegs, sym, has_window ? 1 : 0, d_out, nullptr, nullptr, false, st);
 }
 
 int zng_rocm_inflate_resolve_dev(const uint32_t *d_tokens, size_t ntokens, const uint8_t *d_literals,

@@ -47,5 +47,8 @@ int zr_inflate_decode_threads(const uint8_t *src, size_t src_len, uint32_t windo
 // the stream form of zng_rocm_inflate_tokens_decode_window from the block header at `start_bit` of src (statuses, message and
 // out_len as there; in_used counted from src)
 int zr_inflate_decode_from(const uint8_t *src, size_t src_len, uint64_t start_bit, uint32_t window_len, zng_rocm_inflate_tokens *t);
+// zng_rocm_inflate_tokens_decode_window into arrays the caller keeps across streams (caps: their capacities; they grow through `re`)
+int zr_inflate_decode_reuse(const uint8_t *src, size_t src_len, uint32_t window_len, zng_rocm_inflate_tokens *t,
+                            size_t caps[3], void *(*re)(void *, size_t, size_t));
 void zr_inflate_note_parts(int n);        // for zng_rocm_inflate_threads_last_parts()
 unsigned zr_default_threads();            // hardware threads, capped by the control group's CPU quota
