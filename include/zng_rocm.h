@@ -755,6 +755,87 @@ int    zng_rocm_bgzf_compress_dev(int level, const uint8_t *d_src, size_t src_le
 int    zng_rocm_bgzf_last_rounds(void);
 int    zng_rocm_bgzf_last_stored(void);
 
+/* ---- BGZF random access: what the members of at most 64 KiB are for (SAM specification 4.1; bgzip, BAM, tabix) ------------
+ * zng_rocm_bgzf_index_dev: the members table of a device-resident BGZF file WITHOUT decoding it -- the cost of a scan, not of
+ * an inflate.  For a well-formed file the rows are exactly the rows zng_rocm_gunzip_members_dev reports for it: src_off,
+ * src_len (BSIZE + 1), dst_off (the running sum of ISIZE), out_len (ISIZE), crc (the trailer's word), bgzf 1; the end-of-file
+ * block is a row with out_len 0; *plain_len is their sum, *in_used the end of the last member; members_cap / *nmembers as in
+ * that call.  The rows are what the file CLAIMS (BSIZE of the 'BC' subfield, the eight bytes in front of the claimed end): no
+ * inflate kernel is launched, and zng_rocm_bgzf_read_dev below verifies what it uses.
+ * What happens: the candidate scan, scatter and header kernel of zng_rocm_gunzip_members_dev (same bounds: a candidate's
+ * header is shown at most 4 KiB); one lane per candidate writes a row for every accepted header with a 'BC' subfield; the
+ * table comes down once (32 bytes per candidate; two synchronisations in all); the host follows the chain from offset 0 by
+ * binary search, so candidates inside a member's bytes are never looked at.
+ * Results (what follows a member is judged as gz_look judges it, gzread.c.in:81-154):
+ *   0    the chain reached the end of the file, or trailing garbage behind a complete member -- fewer than 2 bytes, or two
+ *        bytes other than 1f 8b (gz_look asks avail_in > 1, gzread.c.in:127) -- with *in_used in front of the garbage;
+ *        src_len == 0: no members
+ *   -3   behind a complete member, or at offset 0, 1f 8b (at offset 0: anything) where no accepted BGZF header begins -- a
+ *        plain gzip member, a refused header, one longer than 4 KiB, a BSIZE that leaves no room for header, two bytes of
+ *        deflate and trailer, an ISIZE above 65536; zng_rocm_last_error() names the offset; *nmembers, *plain_len, *in_used
+ *        and `members` describe the members in front
+ *   -5   a member whose BSIZE end lies behind src_len, or a header the file's end cuts (1f 8b with fewer than two bytes
+ *        behind it, and a file shorter than 18 bytes, included); the same outputs
+ *   ZNG_ROCM_EINVAL   a null buffer with a non-zero length or a null result pointer: nothing launched or written, the outputs
+ *        zeroed; more than 2^24 candidates (known behind the scan): the outputs zeroed -- zng_rocm_gunzip_members_dev reads
+ *        such a file
+ * The scan and the header kernel fetch aligned 16-byte lines: up to 15 bytes on either side of the file inside the same line
+ * are read (never used).  Synchronous.
+ *
+ * zng_rocm_bgzf_read_dev: MANY plaintext ranges [uoff, uoff + len) of the file in one set of launches, decoding only the
+ * members the ranges touch.  `members` is a HOST array: the rows of zng_rocm_bgzf_index_dev, zng_rocm_gunzip_members_dev or
+ * zng_rocm_bgzf_compress_dev for this file.  Before anything is launched the rows are checked -- src_off ascending and
+ * members not overlapping, every member inside src_len, dst_off contiguous from 0, bgzf == 1, 28 <= src_len <= 65536, out_len
+ * <= 65536 -- and every range for a null d_dst with a non-zero len; scratch_bytes is 0 (= 256 MiB) or 128 KiB .. 4 GiB.  Any
+ * violation is ZNG_ROCM_EINVAL with nothing launched and no range field or destination byte written.
+ * plain_len is the end of the last row, and a range is clipped to it: uoff >= plain_len gives status 1 with out_len 0, else
+ * out_len = min(len, plain_len - uoff) on success.  Members with out_len 0 are never decoded.
+ * What happens: for every range a binary search finds its first member.  A member that lies wholly inside the range is
+ * decoded straight to d_dst + (row.dst_off - uoff) with exactly row.out_len as capacity; a member the range only cuts (an
+ * edge: a range has at most two) is decoded into a 64 KiB slot of scratch, once per round however many ranges cut it, and
+ * each of those ranges gets a slice of it.  All members of a round go through ONE launch of the one-wavefront engine as gzip
+ * members (zng_rocm_uncompress_streams_dev, format 2), so header, payload, CRC-32 and ISIZE are verified on the device
+ * (inflate.c:556-700, :1105-1147); behind it on the same stream, with no host round trip, one kernel copies the slices, one
+ * workgroup each -- only from a member that ended with status 1, consumed exactly row.src_len and produced exactly
+ * row.out_len -- with 16-byte vector stores and byte steps at head and tail, for every pair of alignments.  One readback of
+ * the result rows and one synchronisation per round.  Ranges are taken in order until the edge slots of a round would pass
+ * scratch_bytes (or the round holds 2^22 members: its tables are bounded like its slots); a range is never split across rounds.
+ * Per range:
+ *   status 1    every member it touched verified; out_len = the clipped length, msg NULL
+ *   status -3   a member failed with a data or check error: msg is the engine's text for the first such member of the range
+ *               ("incorrect data check", "incorrect length check", "invalid distance too far back", ...), or "index row does
+ *               not match the file" when that member decoded cleanly but consumed or produced other than its row says
+ *   status -5   no member failed that way, but one was truncated or did not fit its row's out_len; msg NULL
+ *   on failure  out_len = the bytes of the range in front of the first failing member's part; those bytes, and the parts of
+ *               members behind it that verified, are in place; an edge member that failed has written nothing to d_dst
+ * Nothing outside [d_dst, d_dst + len) of any range is ever written, and one range's failure does not change another's
+ * result.  Returns 0, or the first device error.  Synchronous.  The three counters are thread-local, like the other last_*
+ * ones: members put through the engine, of those the members decoded straight into a destination, rounds.
+ *
+ * Virtual offsets, htslib's convention (host only; both work without a device): voff = src_off << 16 | (uoff - dst_off) of
+ * the member that holds uoff -- an offset at a member's end is offset 0 of the next non-empty member, and plain_len maps to
+ * the start of the last row (the end-of-file block of a complete file).  The inverse is uoff = dst_off + (voff & 0xffff) of
+ * the member at voff >> 16.  ZNG_ROCM_EINVAL: uoff > plain_len, src_off >= 2^48, voff >> 16 is no member's src_off, voff &
+ * 0xffff is above that member's out_len, an offset sixteen bits cannot say, an empty table, a null pointer. */
+typedef struct zng_rocm_bgzf_range {
+    uint64_t    uoff;      /* first plaintext byte */
+    uint64_t    len;       /* bytes wanted */
+    uint8_t    *d_dst;     /* device, any alignment, len bytes */
+    /* out */
+    int         status;    /* 1, -3, -5 */
+    uint64_t    out_len;
+    const char *msg;       /* static text on -3, else NULL */
+} zng_rocm_bgzf_range;
+int    zng_rocm_bgzf_index_dev(const uint8_t *d_src, size_t src_len, zng_rocm_gzip_member *members, size_t members_cap,
+                               size_t *nmembers, uint64_t *plain_len, size_t *in_used, void *stream);
+int    zng_rocm_bgzf_read_dev(const uint8_t *d_src, size_t src_len, const zng_rocm_gzip_member *members, size_t nmembers,
+                              zng_rocm_bgzf_range *ranges, size_t nranges, size_t scratch_bytes, void *stream);
+int    zng_rocm_bgzf_read_last_decoded(void);
+int    zng_rocm_bgzf_read_last_direct(void);
+int    zng_rocm_bgzf_read_last_rounds(void);
+int    zng_rocm_bgzf_voffset(const zng_rocm_gzip_member *members, size_t nmembers, uint64_t uoff, uint64_t *voff);
+int    zng_rocm_bgzf_uoffset(const zng_rocm_gzip_member *members, size_t nmembers, uint64_t voff, uint64_t *uoff);
+
 /* ONE raw stream with its host decode spread over `nthreads` threads (zng_rocm_inflate_tokens_decode_threads) and one
  * device pass; same results and status as zng_rocm_inflate_raw_window, which it falls back to for streams that
  * offer no block boundary to cut at or turn out irregular.  Synchronous. */

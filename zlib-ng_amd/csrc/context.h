@@ -89,6 +89,8 @@ enum ScratchSlot {
     kScrBgzf,               // device: state | member rows | member offsets | checks | payload sizes | the level-1 class's
                             //   results and its buffer per piece (zng_rocm_bgzf_compress_dev)
     kScrBgzfHost,           // pinned: the state on its way down
+    kScrBgzfRead,           // device: the engine's results | slices | the edge members' 64 KiB slots (zng_rocm_bgzf_read_dev)
+    kScrBgzfReadHost,       // pinned: the slices on their way up | the results on their way down
     kScrCount
 };
 

@@ -24,6 +24,7 @@
 #include "context.h"
 #include "framing_large.h"
 #include "framing_parse.h"
+#include "gzip_members_dev.h"
 #include "gzip_members_plan.h"
 
 namespace zr {
@@ -211,63 +212,24 @@ struct Call {
     }
 };
 
-// the candidates of the file and what their headers say: scan .. link.  Two readbacks: the candidates' number (4 bytes: it
-// sizes the tables and the header kernel's grid), then `rows`, once.  *too_many: more than kMembersMaxCandidates, no table.
+// the candidates of the file and what their headers say: scan .. link.  Two readbacks: the candidates' number (members_heads),
+// then `rows`, once.  *too_many: more than kMembersMaxCandidates, no table.
 int discover(Call &c, std::vector<CandRow> &rows, bool *too_many) {
     rows.clear();
     *too_many = false;
-    if (c.src_len < 4) return ZNG_ROCM_OK;
-    Context *cx = ctx();
-    const uint64_t head = (uintptr_t)c.d_src & 15u, nlines = (head + c.src_len + 15) >> 4;
-    const uint64_t ntiles64 = (nlines + kTileLines - 1) / kTileLines;
-    if (ntiles64 > 0x7fffffffull) {
-        set_error("zng_rocm_gunzip_members_dev: a file of %zu bytes is more than 2^31 tiles of 16 KiB", c.src_len);
-        return ZNG_ROCM_EINVAL;
-    }
-    const uint32_t ntiles = (uint32_t)ntiles64;
-    const size_t o_count = up16(nlines * sizeof(uint16_t)), o_off = o_count + up16((size_t)ntiles * sizeof(uint32_t));
-    uint8_t *d = nullptr, *h = nullptr;
-    {
-        std::lock_guard<std::mutex> use(c.ws->mu);
-        if (int rc = scratch_reserve(c.ws, kScrMembersScan, o_off + ((size_t)ntiles + 1) * sizeof(uint32_t), false, (void **)&d)) return rc;
-        if (int rc = scratch_reserve(c.ws, kScrMembersHost, 16, true, (void **)&h)) return rc;
-    }
-    uint16_t *d_bitmap = reinterpret_cast<uint16_t *>(d);
-    uint32_t *d_count = reinterpret_cast<uint32_t *>(d + o_count), *d_off = reinterpret_cast<uint32_t *>(d + o_off);
-    const uint32_t grid = ntiles < (uint32_t)cx->cus * 8u ? ntiles : (uint32_t)cx->cus * 8u;
-    hipLaunchKernelGGL(members_scan_kernel, dim3(grid), dim3(kScanThreads), 0, c.st, c.d_src, (uint64_t)c.src_len, d_bitmap, d_count, ntiles);
-    ZR_HIP(hipGetLastError());
-    hipLaunchKernelGGL(members_offsets_kernel, dim3(1), dim3(kScanThreads), 0, c.st, d_count, ntiles, d_off);
-    ZR_HIP(hipGetLastError());
-    ZR_HIP(hipMemcpyAsync(h, d_off + ntiles, sizeof(uint32_t), hipMemcpyDeviceToHost, c.st));
-    ZR_HIP(hipStreamSynchronize(c.st));
-    uint32_t n;
-    memcpy(&n, h, sizeof n);
-    if (n == kMembersTooMany) *too_many = true;
-    if (!n || *too_many) return ZNG_ROCM_OK;
-    const size_t o_jobs = up16((size_t)n * sizeof(uint64_t)), o_heads = o_jobs + up16((size_t)n * sizeof(HeadJob));
-    const size_t o_rows = o_heads + up16((size_t)n * sizeof(WrapperHead)), o_work = o_rows + up16((size_t)n * sizeof(CandRow));
-    uint8_t *tab = nullptr;
-    {
-        std::lock_guard<std::mutex> use(c.ws->mu);
-        if (int rc = scratch_reserve(c.ws, kScrMembersTab, o_work + header_rows_scratch(n), false, (void **)&tab)) return rc;
-        if (int rc = scratch_reserve(c.ws, kScrMembersHost, (size_t)n * sizeof(CandRow), true, (void **)&h)) return rc;
-    }
-    uint64_t *d_pos = reinterpret_cast<uint64_t *>(tab);
-    HeadJob *d_jobs = reinterpret_cast<HeadJob *>(tab + o_jobs);
-    WrapperHead *d_heads = reinterpret_cast<WrapperHead *>(tab + o_heads);
-    CandRow *d_rows = reinterpret_cast<CandRow *>(tab + o_rows);
-    hipLaunchKernelGGL(members_scatter_kernel, dim3(grid), dim3(kScanThreads), 0, c.st, c.d_src, (uint64_t)c.src_len, d_bitmap, d_off, ntiles,
-                       d_pos, d_jobs);
-    ZR_HIP(hipGetLastError());
-    if (int rc = header_rows_device(2, d_jobs, n, d_heads, tab + o_work, c.st)) return rc;
-    hipLaunchKernelGGL(members_link_kernel, dim3((n + 255u) / 256u), dim3(256), 0, c.st, c.d_src, (uint64_t)c.src_len, d_pos, d_heads, n,
+    MembersHeads m;
+    if (int rc = members_heads("zng_rocm_gunzip_members_dev", c.d_src, c.src_len, sizeof(CandRow), c.st, c.ws, &m)) return rc;
+    *too_many = m.too_many;
+    const uint32_t n = m.n;
+    if (!n) return ZNG_ROCM_OK;
+    CandRow *d_rows = reinterpret_cast<CandRow *>(m.d_rows);
+    hipLaunchKernelGGL(members_link_kernel, dim3((n + 255u) / 256u), dim3(256), 0, c.st, c.d_src, (uint64_t)c.src_len, m.d_pos, m.d_heads, n,
                        d_rows);
     ZR_HIP(hipGetLastError());
-    ZR_HIP(hipMemcpyAsync(h, d_rows, (size_t)n * sizeof(CandRow), hipMemcpyDeviceToHost, c.st));
+    ZR_HIP(hipMemcpyAsync(m.h_rows, d_rows, (size_t)n * sizeof(CandRow), hipMemcpyDeviceToHost, c.st));
     ZR_HIP(hipStreamSynchronize(c.st));
     rows.resize(n);
-    memcpy(rows.data(), h, (size_t)n * sizeof(CandRow));
+    memcpy(rows.data(), m.h_rows, (size_t)n * sizeof(CandRow));
     return ZNG_ROCM_OK;
 }
 
@@ -387,6 +349,58 @@ int gunzip_members(Call &c, uint64_t *out_len, size_t *in_used, size_t *nmembers
 }
 
 }  // namespace
+
+// scan, offsets, the candidates' number, scatter, headers (gzip_members_dev.h)
+int members_heads(const char *who, const uint8_t *d_src, size_t src_len, size_t row_bytes, hipStream_t st, Workspace *ws,
+                  MembersHeads *out) {
+    *out = MembersHeads{0u, false, nullptr, nullptr, nullptr, nullptr};
+    if (src_len < 4) return ZNG_ROCM_OK;
+    Context *cx = ctx();
+    const uint64_t head = (uintptr_t)d_src & 15u, nlines = (head + src_len + 15) >> 4;
+    const uint64_t ntiles64 = (nlines + kTileLines - 1) / kTileLines;
+    if (ntiles64 > 0x7fffffffull) {
+        set_error("%s: a file of %zu bytes is more than 2^31 tiles of 16 KiB", who, src_len);
+        return ZNG_ROCM_EINVAL;
+    }
+    const uint32_t ntiles = (uint32_t)ntiles64;
+    const size_t o_count = up16(nlines * sizeof(uint16_t)), o_off = o_count + up16((size_t)ntiles * sizeof(uint32_t));
+    uint8_t *d = nullptr, *h = nullptr;
+    {
+        std::lock_guard<std::mutex> use(ws->mu);
+        if (int rc = scratch_reserve(ws, kScrMembersScan, o_off + ((size_t)ntiles + 1) * sizeof(uint32_t), false, (void **)&d)) return rc;
+        if (int rc = scratch_reserve(ws, kScrMembersHost, 16, true, (void **)&h)) return rc;
+    }
+    uint16_t *d_bitmap = reinterpret_cast<uint16_t *>(d);
+    uint32_t *d_count = reinterpret_cast<uint32_t *>(d + o_count), *d_off = reinterpret_cast<uint32_t *>(d + o_off);
+    const uint32_t grid = ntiles < (uint32_t)cx->cus * 8u ? ntiles : (uint32_t)cx->cus * 8u;
+    hipLaunchKernelGGL(members_scan_kernel, dim3(grid), dim3(kScanThreads), 0, st, d_src, (uint64_t)src_len, d_bitmap, d_count, ntiles);
+    ZR_HIP(hipGetLastError());
+    hipLaunchKernelGGL(members_offsets_kernel, dim3(1), dim3(kScanThreads), 0, st, d_count, ntiles, d_off);
+    ZR_HIP(hipGetLastError());
+    ZR_HIP(hipMemcpyAsync(h, d_off + ntiles, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    ZR_HIP(hipStreamSynchronize(st));
+    uint32_t n;
+    memcpy(&n, h, sizeof n);
+    if (n == kMembersTooMany) out->too_many = true;
+    if (!n || out->too_many) return ZNG_ROCM_OK;
+    const size_t o_jobs = up16((size_t)n * sizeof(uint64_t)), o_heads = o_jobs + up16((size_t)n * sizeof(HeadJob));
+    const size_t o_rows = o_heads + up16((size_t)n * sizeof(WrapperHead)), o_work = o_rows + up16((size_t)n * row_bytes);
+    uint8_t *tab = nullptr;
+    {
+        std::lock_guard<std::mutex> use(ws->mu);
+        if (int rc = scratch_reserve(ws, kScrMembersTab, o_work + header_rows_scratch(n), false, (void **)&tab)) return rc;
+        if (int rc = scratch_reserve(ws, kScrMembersHost, (size_t)n * row_bytes, true, (void **)&h)) return rc;
+    }
+    uint64_t *d_pos = reinterpret_cast<uint64_t *>(tab);
+    HeadJob *d_jobs = reinterpret_cast<HeadJob *>(tab + o_jobs);
+    WrapperHead *d_heads = reinterpret_cast<WrapperHead *>(tab + o_heads);
+    hipLaunchKernelGGL(members_scatter_kernel, dim3(grid), dim3(kScanThreads), 0, st, d_src, (uint64_t)src_len, d_bitmap, d_off, ntiles,
+                       d_pos, d_jobs);
+    ZR_HIP(hipGetLastError());
+    if (int rc = header_rows_device(2, d_jobs, n, d_heads, tab + o_work, st)) return rc;
+    *out = MembersHeads{n, false, d_pos, d_heads, tab + o_rows, h};
+    return ZNG_ROCM_OK;
+}
 
 }  // namespace zr
 

@@ -440,3 +440,72 @@ def gunzip_members_dev(src_dev, dst, members_cap=None, stream=None, subblock=Fal
     counters = {"candidates": int(lib.zng_rocm_gunzip_last_candidates()), "replans": int(lib.zng_rocm_gunzip_last_replans()),
                 "small": int(lib.zng_rocm_gunzip_last_small()), "large": int(lib.zng_rocm_gunzip_last_large())}
     return st, int(out_len.value), int(in_used.value), rows, int(nmembers.value), counters
+
+
+class BgzfRange(C.Structure):
+    """zng_rocm_bgzf_range"""
+    _fields_ = [("uoff", C.c_uint64), ("len", C.c_uint64), ("d_dst", C.c_void_p), ("status", C.c_int), ("out_len", C.c_uint64),
+                ("msg", C.c_char_p)]
+
+
+def member_table(rows):
+    """[(src_off, src_len, dst_off, out_len, crc, bgzf)] -> a ctypes array of zng_rocm_gzip_member (host memory)"""
+    table = (GzipMember * max(len(rows), 1))()
+    for k, row in enumerate(rows):
+        table[k] = GzipMember(*(int(v) for v in row))
+    return table
+
+
+def bgzf_index_dev(src_dev, members_cap=None, stream=None):
+    """zng_rocm_bgzf_index_dev: the members table of a BGZF file in device memory (`src_dev`: uint8 CUDA tensor) without
+    decoding it.  `members_cap`: rows to take (None = all, reserved as in gunzip_members_dev).  Returns (status, members,
+    nmembers, plaintext bytes, file bytes used) with members = [(src_off, src_len, dst_off, out_len, crc, bgzf)]."""
+    import numpy as np
+    rocm._need_init()
+    lib = rocm.lib()
+    n = int(src_dev.numel())
+    cap = n // 28 + 1 if members_cap is None else int(members_cap)
+    table = np.empty(max(cap, 1) * C.sizeof(GzipMember), dtype=np.uint8)
+    nmembers, plain_len, in_used = C.c_size_t(0), C.c_uint64(0), C.c_size_t(0)
+    st = lib.zng_rocm_bgzf_index_dev(rocm._dev_ptr(src_dev) if n else None, n, C.c_void_p(table.ctypes.data) if cap else None, cap,
+                                     C.byref(nmembers), C.byref(plain_len), C.byref(in_used), rocm._stream_ptr(stream))
+    rows = [(int(m.src_off), int(m.src_len), int(m.dst_off), int(m.out_len), int(m.crc), int(m.bgzf))
+            for m in (GzipMember * min(cap, int(nmembers.value))).from_buffer(table)]
+    return st, rows, int(nmembers.value), int(plain_len.value), int(in_used.value)
+
+
+def bgzf_read_dev(src_dev, members, ranges, scratch_bytes=0, stream=None):
+    """zng_rocm_bgzf_read_dev: `ranges` = [(uoff, len, dst)] with dst a uint8 CUDA tensor of at least len bytes, a device
+    address or None, `members` the rows of bgzf_index_dev / gunzip_members_dev / bgzf_compress_dev for the file in `src_dev`, or a
+    member_table() of them.  Returns (return value, [(status, out_len, msg)] per range, counters) with counters = {"decoded",
+    "direct", "rounds"} (zng_rocm_bgzf_read_last_*)."""
+    rocm._need_init()
+    lib = rocm.lib()
+    n = int(src_dev.numel())
+    table, nm = (member_table(members), len(members)) if isinstance(members, (list, tuple)) else (members, len(members))
+    rs = (BgzfRange * max(len(ranges), 1))()
+    for k, (uoff, length, dst) in enumerate(ranges):
+        rs[k] = BgzfRange(int(uoff), int(length), None if dst is None else int(dst) if isinstance(dst, int) else dst.data_ptr(), 0, 0, None)
+    st = lib.zng_rocm_bgzf_read_dev(rocm._dev_ptr(src_dev) if n else None, n, C.cast(table, C.c_void_p), nm, C.cast(rs, C.c_void_p),
+                                    len(ranges), int(scratch_bytes), rocm._stream_ptr(stream))
+    out = [(int(r.status), int(r.out_len), None if r.msg is None else r.msg.decode()) for r in rs[:len(ranges)]]
+    counters = {"decoded": int(lib.zng_rocm_bgzf_read_last_decoded()), "direct": int(lib.zng_rocm_bgzf_read_last_direct()),
+                "rounds": int(lib.zng_rocm_bgzf_read_last_rounds())}
+    return st, out, counters
+
+
+def bgzf_voffset(members, uoff):
+    """zng_rocm_bgzf_voffset: the virtual offset of plaintext byte `uoff` (htslib's convention), or None when the call refuses;
+    needs no device"""
+    table = member_table(members) if isinstance(members, (list, tuple)) else members
+    voff = C.c_uint64(0)
+    st = rocm.lib().zng_rocm_bgzf_voffset(C.cast(table, C.c_void_p), len(members), int(uoff), C.byref(voff))
+    return int(voff.value) if st == 0 else None
+
+
+def bgzf_uoffset(members, voff):
+    """zng_rocm_bgzf_uoffset: the plaintext offset a virtual offset stands for, or None when the call refuses; needs no device"""
+    table = member_table(members) if isinstance(members, (list, tuple)) else members
+    uoff = C.c_uint64(0)
+    st = rocm.lib().zng_rocm_bgzf_uoffset(C.cast(table, C.c_void_p), len(members), int(voff), C.byref(uoff))
+    return int(uoff.value) if st == 0 else None
