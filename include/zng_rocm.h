@@ -836,6 +836,99 @@ int    zng_rocm_bgzf_read_last_rounds(void);
 int    zng_rocm_bgzf_voffset(const zng_rocm_gzip_member *members, size_t nmembers, uint64_t uoff, uint64_t *voff);
 int    zng_rocm_bgzf_uoffset(const zng_rocm_gzip_member *members, size_t nmembers, uint64_t voff, uint64_t *uoff);
 
+/* ---- random access into ONE plain stream: raw deflate, zlib or gzip (what zran.c and indexed_gzip do on a CPU) -------------
+ * A BGZF file offers random access by construction; every other stream -- a plain .gz, a zlib stream, raw deflate, what
+ * zng_rocm_compress2_dev or zng_rocm_deflate_dev write -- needs an INDEX: access points {in_bit, out_off, window_len}, each a
+ * block start (bit in_bit of the file), the plaintext offset of its first byte, and the window_len = min(32768, out_off)
+ * bytes in front of it, which the index keeps in device memory.  The SPAN of point k is the plaintext [out_off_k,
+ * out_off_(k+1)), the last span ends at plain_len; decoding can resume at any point with nothing but its window.
+ *
+ * zng_rocm_inflate_index_build_dev: zng_rocm_uncompress_large_dev(format, d_src, src_len, NULL, 0, d_dst, dst_cap, out_len,
+ * in_used, piece_bytes, flags, stream) plus an index (no preset dictionary).  The return value, *out_len, *in_used, the
+ * bytes at d_dst, the zng_rocm_last_error() text and the zng_rocm_inflate_large_last_* counters are that call's for the same
+ * arguments.  An index exists only on return value 1; on any other return (a zlib member with FDICT returns 2) *out = NULL.
+ * A multi-member gzip file is indexed up to the end of its first member (*in_used).  span_bytes: the least plaintext between
+ * two points, 0 (= 1 MiB) or 64 KiB .. 1 GiB; anything else, or out == NULL, is ZNG_ROCM_EINVAL with nothing launched and no
+ * device byte written.
+ * What happens: while the stream is decoded, the pieces loop notes the block starts it meets -- every part of a device pass
+ * that begins at a block start, every block start between two pieces, the block ends the sequential decoder delivers -- with
+ * their plaintext offsets.  Point 0 is always {8 * header_len, 0, 0}; walking the starts in stream order, one becomes a point
+ * when its out_off is at least span_bytes past the last point and in front of plain_len.  A stream only the sequential decoder
+ * handles (below 128 KiB compressed, for one) has point 0 alone: correct, and a read of it decodes from the start.  One
+ * kernel, one workgroup per point, then copies all windows out of d_dst into memory the index owns.  Synchronous.
+ * The index is immutable; zng_rocm_inflate_index_points copies up to `cap` points to `pts` (may be NULL) and returns their
+ * number; zng_rocm_inflate_index_destroy frees it (before zng_rocm_shutdown()).
+ *
+ * zng_rocm_inflate_index_read_dev: MANY plaintext ranges [uoff, uoff + len) in one set of launches, decoding only the spans
+ * the ranges touch.  d_src / src_len: the file the index was built from.  Checked before anything is launched: idx and the
+ * buffers are not null, every point of the index begins inside src_len (a file that ends in front of the last point is not
+ * the indexed one; a file that is merely cut behind it is read as far as it goes), no range has a null d_dst with a non-zero
+ * len, scratch_bytes is 0 (= 256 MiB) or 1 MiB .. 4 GiB.  Any violation is ZNG_ROCM_EINVAL with no range field or
+ * destination byte written.  A range is clipped to plain_len: uoff >= plain_len gives status 1 with out_len 0.
+ * What happens: a span that lies wholly inside a range is ONE job of the one-wavefront engine in its span form, decoded
+ * straight to d_dst + (out_off_k - uoff) with the span's length as capacity: it starts at bit in_bit & 7 of byte in_bit >> 3
+ * with in_len = min(src_len - (in_bit >> 3), 2^31 - 1), its history is the point's own window (a distance that reaches in
+ * front of it is "invalid distance too far back": a damaged file never reads outside a window), and it ends where its output
+ * reaches the capacity, at a block end or inside a block.  A span a range only cuts (an edge: a range has at most two) is
+ * decoded once per round into a scratch slot, however many ranges of the round cut it, and only as far as the furthest of
+ * them needs; behind the engine on the same stream one kernel copies each range's slice, one workgroup each -- only from a
+ * job that ended with status 1 and produced exactly its capacity -- with 16-byte vector stores and byte steps at head and
+ * tail, for every pair of alignments.  One launch of each kernel, one readback and one synchronisation per round.  Ranges
+ * are taken in order until the edge slots of a round would pass scratch_bytes; a range is never split, so a range whose own
+ * edge slots are larger is a round of its own.  A span of 2 GiB and more of plaintext is not this engine's: a range that
+ * touches one gets status -5 with msg "span too long for the one-wavefront engine".
+ * Per range (fields as zng_rocm_bgzf_range): status 1, out_len = the clipped length; status -3 with the engine's text for
+ * the FIRST failing span of the range ("invalid block type", "invalid distance too far back", ..., or "index does not match
+ * the stream" when the stream ended in front of the span's end); status -5 when that span was starved of input.  On failure
+ * out_len = the bytes of the range in front of the first failing span's part; an edge span that failed has written nothing
+ * to d_dst.  Nothing outside [d_dst, d_dst + len) of any range is ever written, and one range's failure does not change
+ * another's result.
+ * NO CHECK VALUE: a partial read has none to compare.  A read verifies the deflate structure of what it decodes and the
+ * length it produces, nothing else -- the build verified Adler-32 / CRC-32 and ISIZE of the whole member once.
+ * Returns 0, or the first device error.  Synchronous.  The three counters are thread-local: spans put through the engine, of
+ * those the spans decoded straight into a destination, rounds.
+ *
+ * zng_rocm_inflate_index_export / _import_dev: the index as one little-endian blob in HOST memory (one device-to-host copy of
+ * the windows, one copy back):
+ *   0   u32 magic "ZRIX"   4  u32 version (1)   8  u32 format   12  u32 0
+ *   16  u64 header_len     24 u64 src_end (*in_used of the build: the indexed member's end)   32  u64 plain_len
+ *   40  u64 span_bytes     48 u64 npoints
+ *   56  npoints rows of 24 bytes: u64 in_bit, u64 out_off, u32 window_len, u32 0
+ *   then the windows, point 0's first, each at its real length
+ * export: *need is always set; cap < *need returns -5 with nothing written.  import checks, before any allocation: magic and
+ * version, format, span_bytes, point 0 = {8 * header_len, 0, 0}, in_bit ascending, out_off ascending and below plain_len,
+ * window_len == min(32768, out_off), the reserved words, every point at or in front of src_end, and that the size is exactly
+ * header + rows + windows.  Anything else is ZNG_ROCM_EINVAL with *out = NULL. */
+typedef struct zng_rocm_inflate_index zng_rocm_inflate_index;        /* opaque; immutable once built */
+typedef struct zng_rocm_access_point {
+    uint64_t in_bit;         /* bit of the file where a deflate block begins */
+    uint64_t out_off;        /* plaintext offset of its first byte */
+    uint32_t window_len;     /* min(32768, out_off): bytes of history the index keeps for it */
+    uint32_t reserved;       /* 0 */
+} zng_rocm_access_point;
+typedef struct zng_rocm_inflate_range {           /* same fields and meaning as zng_rocm_bgzf_range */
+    uint64_t    uoff;
+    uint64_t    len;
+    uint8_t    *d_dst;
+    /* out */
+    int         status;
+    uint64_t    out_len;
+    const char *msg;
+} zng_rocm_inflate_range;
+int      zng_rocm_inflate_index_build_dev(int format, const uint8_t *d_src, size_t src_len, uint8_t *d_dst, size_t dst_cap,
+                                          uint64_t *out_len, size_t *in_used, uint64_t span_bytes, size_t piece_bytes,
+                                          uint32_t flags, zng_rocm_inflate_index **out, void *stream);
+int      zng_rocm_inflate_index_read_dev(const zng_rocm_inflate_index *idx, const uint8_t *d_src, size_t src_len,
+                                         zng_rocm_inflate_range *ranges, size_t nranges, size_t scratch_bytes, void *stream);
+size_t   zng_rocm_inflate_index_points(const zng_rocm_inflate_index *idx, zng_rocm_access_point *pts, size_t cap);
+uint64_t zng_rocm_inflate_index_plain_len(const zng_rocm_inflate_index *idx);
+int      zng_rocm_inflate_index_export(const zng_rocm_inflate_index *idx, uint8_t *buf, size_t cap, size_t *need, void *stream);
+int      zng_rocm_inflate_index_import_dev(const uint8_t *buf, size_t len, zng_rocm_inflate_index **out, void *stream);
+void     zng_rocm_inflate_index_destroy(zng_rocm_inflate_index *idx);
+int      zng_rocm_inflate_index_read_last_decoded(void);   /* thread-local: spans put through the engine */
+int      zng_rocm_inflate_index_read_last_direct(void);    /* of those, spans decoded straight into a destination */
+int      zng_rocm_inflate_index_read_last_rounds(void);
+
 /* ONE raw stream with its host decode spread over `nthreads` threads (zng_rocm_inflate_tokens_decode_threads) and one
  * device pass; same results and status as zng_rocm_inflate_raw_window, which it falls back to for streams that
  * offer no block boundary to cut at or turn out irregular.  Synchronous. */

@@ -91,6 +91,9 @@ enum ScratchSlot {
     kScrBgzfHost,           // pinned: the state on its way down
     kScrBgzfRead,           // device: the engine's results | slices | the edge members' 64 KiB slots (zng_rocm_bgzf_read_dev)
     kScrBgzfReadHost,       // pinned: the slices on their way up | the results on their way down
+    kScrIndexRead,          // device: the engine's results | jobs | span table | slices | the edge spans' slots
+                            //   (zng_rocm_inflate_index_read_dev); the window moves of zng_rocm_inflate_index_build_dev
+    kScrIndexReadHost,      // pinned: jobs | span table | slices on their way up | the results on their way down
     kScrCount
 };
 

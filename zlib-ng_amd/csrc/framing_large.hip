@@ -494,6 +494,7 @@ int uncompress_large(int format, zng_rocm_inflate_large_job *jobs, size_t njobs,
     if (single) {
         if (!inner.empty()) {
             zng_rocm_inflate_large_job &p = inner[0];
+            if (IndexSink *sink = inflate_index_sink()) sink->header_len = heads[inner_of[0]].header_len;
             p.status = zng_rocm_inflate_large_pieces_dev(p.d_src, p.src_len, p.d_window, p.window_len, p.d_dst, p.dst_cap, &p.out_len,
                                                          &p.in_used, bytes, flags, st);
             p.msg = nullptr;                             // the text of a data error is in zng_rocm_last_error() already

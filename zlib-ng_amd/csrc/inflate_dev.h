@@ -5,6 +5,9 @@
 #include "context.h"
 #include "inflate_dev_types.h"
 
+#include <utility>
+#include <vector>
+
 namespace zr {
 
 // one wavefront per job; d_jobs and d_results are device memory (results: 4 words per job)
@@ -12,6 +15,11 @@ int launch_inflate_streams_device(const InflateJobDev *d_jobs, size_t njobs, uin
 // the same with every job's dict_len bytes of history taken from ONE shared window: the bytes in front of d_hist_end
 // (zng_rocm_uncompress_streams_dict_dev: a job decodes with the whole window or, dict_len 0, with none)
 int launch_inflate_streams_dict_device(const InflateJobDev *d_jobs, size_t njobs, uint32_t *d_results, const uint8_t *d_hist_end,
+                                       hipStream_t stream);
+// the same with every job's dict_len bytes of history taken from ITS OWN window, the bytes in front of d_spans[job].hist_end,
+// the decode starting d_spans[job].start_bit bits into the job's first byte, and status 1 where the output reaches out_cap
+// (zng_rocm_inflate_index_read_dev: a job is one span of an indexed stream)
+int launch_inflate_streams_span_device(const InflateJobDev *d_jobs, size_t njobs, uint32_t *d_results, const InflateSpanDev *d_spans,
                                        hipStream_t stream);
 
 // the parts of ONE large stream, 16-bit symbols out (inflate_large.hip); results: 8 words per part; d_marks (or null):
@@ -54,6 +62,16 @@ int inflate_large_device_only(const uint8_t *d_src, size_t src_len, const uint8_
 int inflate_large_blocks_device_only(const uint8_t *d_src, size_t src_len, unsigned start_bit, const uint8_t *d_window,
                                      uint32_t window_len, uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, uint64_t *end_bit,
                                      int *final, hipStream_t st);
+// The block starts a pieces call meets, for zng_rocm_inflate_index_build_dev (inflate_index.hip): while the calling thread has
+// a sink set, inflate_pieces_call appends {bit of its d_src, offset in its output} of every genuine part that begins at a
+// block start and of every block start it establishes between pieces, and framing_large.hip notes the wrapper header's
+// length.  Null outside a build call: no other caller sees a difference.
+struct IndexSink {
+    std::vector<std::pair<uint64_t, uint64_t>> cands;
+    uint64_t header_len = 0;
+};
+IndexSink *inflate_index_sink();
+void inflate_index_sink_set(IndexSink *sink);
 void inflate_large_forget_parts();       // the part counters of the calling thread back to 0 ("the sequential decoder did it")
 void inflate_large_reset_counters();     // all of the calling thread's last_* counters: nothing ran
 

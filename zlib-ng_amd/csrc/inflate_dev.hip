@@ -664,8 +664,9 @@ template <int RING, bool PART, bool COMPACT = false, bool SUB = false>
 __global__ __launch_bounds__(64)
 void inflate_streams_kernel(const InflateJobDev *__restrict__ jobs, uint32_t njobs, uint32_t *__restrict__ results,
                             const unsigned long long *__restrict__ starts, uint32_t *__restrict__ marks) {
-    constexpr bool DICT = false;
+    constexpr bool DICT = false, SPAN = false;
     const uint8_t *const hist_end = nullptr;
+    const InflateSpanDev *const spans = nullptr;
 #include "inflate_streams_body.h"
 }
 
@@ -675,10 +676,35 @@ template <int RING>
 __global__ __launch_bounds__(64)
 void inflate_streams_dict_kernel(const InflateJobDev *__restrict__ jobs, uint32_t njobs, uint32_t *__restrict__ results,
                                  const uint8_t *__restrict__ hist_end) {
-    constexpr bool PART = false, COMPACT = false, SUB = false, DICT = true;
+    constexpr bool PART = false, COMPACT = false, SUB = false, DICT = true, SPAN = false;
     const unsigned long long *const starts = nullptr;
     uint32_t *const marks = nullptr;
+    const InflateSpanDev *const spans = nullptr;
 #include "inflate_streams_body.h"
+}
+
+// The span form (zng_rocm_inflate_index_read_dev): a job is one span of an indexed stream.  It starts spans[job].start_bit
+// bits into its first byte, its dict_len bytes of history are its OWN window, which ends at spans[job].hist_end (so the "too
+// far back" test holds a damaged file inside that window), and it ends with status 1 where its output reaches out_cap -- at
+// a block end or inside a block.
+template <int RING>
+__global__ __launch_bounds__(64)
+void inflate_streams_span_kernel(const InflateJobDev *__restrict__ jobs, uint32_t njobs, uint32_t *__restrict__ results,
+                                 const InflateSpanDev *__restrict__ spans) {
+    constexpr bool PART = false, COMPACT = false, SUB = false, DICT = false, SPAN = true;
+    const unsigned long long *const starts = nullptr;
+    uint32_t *const marks = nullptr;
+    const uint8_t *const hist_end = nullptr;
+#include "inflate_streams_body.h"
+}
+
+int launch_inflate_streams_span_device(const InflateJobDev *d_jobs, size_t njobs, uint32_t *d_results, const InflateSpanDev *d_spans,
+                                       hipStream_t st) {
+    if (!njobs) return ZNG_ROCM_OK;
+    ZR_LAUNCH_TRACED((inflate_streams_span_kernel<4096>), dim3((unsigned)njobs), dim3(64), st, d_jobs, (uint32_t)njobs, d_results,
+                     d_spans);
+    ZR_HIP(hipGetLastError());
+    return ZNG_ROCM_OK;
 }
 
 int launch_inflate_streams_dict_device(const InflateJobDev *d_jobs, size_t njobs, uint32_t *d_results, const uint8_t *d_hist_end,

@@ -14,6 +14,14 @@ struct InflateJobDev {
     uint32_t       flags;
 };
 
+// the span form's table, parallel to the jobs (inflate_streams_span_kernel): where the job's own window ends, and the bit of
+// its first byte the decode starts at
+struct InflateSpanDev {
+    const uint8_t *hist_end;
+    uint32_t       start_bit;      // 0..7
+    uint32_t       pad;
+};
+
 enum InflateMsg : uint32_t {
     kMsgNone = 0, kMsgBlockType, kMsgStoredLen, kMsgTooMany, kMsgCodeLengthsSet, kMsgBitRepeat, kMsgNoEob,
     kMsgLitLenSet, kMsgDistSet, kMsgLitLenCode, kMsgDistCode, kMsgTooFar, kMsgStarved, kMsgOutFull,

@@ -486,6 +486,9 @@ static thread_local int t_large_subparts = 0;           // of them, parts that b
 static thread_local int t_large_substarts = 0;          // SUBBLOCK: sub-starts placed (the sync kernel's boundaries, deduplicated)
 static thread_local int t_large_pieces = 0;             // pieces: device passes of the last call
 static thread_local uint64_t t_large_host_bytes = 0;    // pieces: compressed bytes the sequential decoder took
+static thread_local IndexSink *t_index_sink = nullptr;  // an index is being built (inflate_dev.h); null outside such a call
+// the last pass's candidates (walk_chain, Chain::record), in the pass's own positions: inflate_pieces_call moves them
+static thread_local std::vector<std::pair<unsigned long long, uint64_t>> t_pass_cands;
 #ifdef ZR_INFLATE_STATS
 static std::vector<unsigned long long> g_dbg_starts;     // diagnostic builds: the last call's part starts and result words
 static std::vector<uint32_t> g_dbg_res;
@@ -510,6 +513,9 @@ static int why_chain(const Chain &c, size_t np, const unsigned long long *starts
               (unsigned long long)jobs[cur].out_cap, (int)r[6]);
     return 0;
 }
+
+IndexSink *inflate_index_sink() { return t_index_sink; }
+void inflate_index_sink_set(IndexSink *sink) { t_index_sink = sink; }
 
 // the part counters of the calling thread back to 0 (a call begins; or "the sequential decoder did it": inflate_resolve.hip)
 void inflate_large_forget_parts() {
@@ -874,9 +880,11 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
     s.b0 = (uint16_t)n12[2];                              // (copied with the finder's counts when F1 + F2 ran)
     s.patterns_do = patterns_do;
     thin_starts(good, start_bit, src_len, s.starts, s.heavy);
+    s.chain.record = t_index_sink != nullptr;
     size_t taken = 0;
     int launches = 0;
     const int rc = pass_run(ws, ss, sub, blocks, pp, st, &taken, &launches);
+    if (t_index_sink) t_pass_cands.swap(s.chain.cands);
     t_large_substarts += (int)s.substarts;
 #ifdef ZR_INFLATE_STATS
     if (s.res) {
@@ -1079,6 +1087,8 @@ static int inflate_pieces_call(const uint8_t *d_src, size_t src_len, const uint8
                 ++passes;
                 parts += t_large_parts;
                 subparts += t_large_subparts;
+                if (t_index_sink)                         // the pass's block starts, moved by its base and by what lay in front
+                    for (const auto &c : t_pass_cands) t_index_sink->cands.emplace_back(c.first + 8 * base, produced + c.second);
                 produced += n;
                 if (!pp.stopped) {                        // the stream ended in this piece
                     *out_len = produced;
@@ -1091,6 +1101,7 @@ static int inflate_pieces_call(const uint8_t *d_src, size_t src_len, const uint8
                 if (key == 0) {
                     abit = bit;
                     aout = produced;
+                    if (t_index_sink) t_index_sink->cands.emplace_back(abit, aout);
                 }
                 p = piece_bytes;
                 continue;
@@ -1173,6 +1184,7 @@ static int inflate_pieces_call(const uint8_t *d_src, size_t src_len, const uint8
             fin = -1;
             abit = bit;
             aout = produced;
+            if (t_index_sink) t_index_sink->cands.emplace_back(abit, aout);
             p = piece_bytes;
             continue;
         }

@@ -262,6 +262,10 @@ struct Chain {
     unsigned long long end_bit = 0;
     bool final = false;                                   // the BFINAL block is among what was delivered
     size_t subparts = 0;                                  // of the parts, those that began inside a block
+    // `record` (an index is being built: inflate_index_plan.h): every genuine part that begins at a block start, as {its bit,
+    // the symbols produced in front of it} -- positions in the pass's own buffer and output
+    bool record = false;
+    std::vector<std::pair<unsigned long long, uint64_t>> cands;
     // a failed walk: why, and when it was a part's own result (message, no end), which part of the stream
     const char *reason = nullptr;
     size_t bad_part = ~(size_t)0;
@@ -332,6 +336,7 @@ inline bool walk_chain(const uint32_t *res, const uint32_t *side, const uint32_t
             return fail("a part's message, or no end");
         }
         if ((uint64_t)r[5] > c.produced + window_len) return fail("a distance reaches in front of the stream");
+        if (c.record && (!sub || keys[cur] == 0)) c.cands.emplace_back(starts[cur], c.produced);
         c.copies.push_back(PartCopy{slot_ptr[g], c.produced, 0, r[0], 0u});
         c.produced += r[0];
         c.end_bit = (unsigned long long)r[1] | ((unsigned long long)r[2] << 32);

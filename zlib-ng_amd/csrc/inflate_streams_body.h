@@ -3,7 +3,10 @@
 //   RING, PART, COMPACT, SUB   the template parameters described in front of inflate_streams_kernel
 //   DICT                       constexpr bool: the history of a job is the tail of one shared window that ends at hist_end
 //                              (inflate_streams_dict_kernel) instead of the bytes in front of its `out`
-//   jobs, njobs, results, starts, marks, hist_end   the kernel's arguments (null where a form has none)
+//   SPAN                       constexpr bool: the history of a job is ITS OWN window, which ends at spans[job].hist_end, the
+//                              decode starts spans[job].start_bit bits (0..7) into the first byte, and reaching out_cap is the
+//                              expected end (inflate_streams_span_kernel: one span of an indexed stream)
+//   jobs, njobs, results, starts, marks, hist_end, spans   the kernel's arguments (null where a form has none)
 // Textual sharing keeps every existing instantiation the very function it was: same arguments, same attributes, same code.
 // The fast loop leaves for any source in front of the stream (ZR_INFLATE_BEFORE_STREAM); the general copy path is the one
 // place that reads such a byte, and it reads hist_end[sp] instead of out[sp] in the dictionary form.
@@ -91,6 +94,13 @@
         cnt -= (uint32_t)(sb & 7ull);
     } else {
         seek(0);
+    }
+    const uint8_t *span_hist = nullptr;                  // SPAN: the end of this job's own window
+    if constexpr (SPAN) {
+        const InflateSpanDev S = spans[job];
+        span_hist = S.hist_end;
+        hold >>= S.start_bit & 7u;
+        cnt -= S.start_bit & 7u;
     }
 
     uint32_t op = 0, flushed = 0;
@@ -215,6 +225,15 @@
     };
     bool last = false;
     while (!last && msg == kMsgNone) {
+        if constexpr (SPAN) {
+            // a span that is complete at a block end stops in front of the next block: it never looks at bytes it does not need
+            // (the waiting literals go to the ring first, clipped at out_cap: service())
+            if (op >= out_cap) {
+                service();
+                if (msg == kMsgNone) msg = kMsgOutFull;
+                break;
+            }
+        }
         if constexpr (PART) {
             // a block starts here: everything in front of it is complete, if the bits it took are all input (the zero bits
             // behind a truncated stream decode to something too).  Stored once per block, so no register holds it.
@@ -544,7 +563,16 @@
             if (PART && dist > op && dist - op > reach) reach = dist - op;
             service();
             if (msg != kMsgNone) break;
-            if (len > out_cap - op) { msg = kMsgOutFull; break; }
+            [[maybe_unused]] bool span_full = false;
+            if constexpr (SPAN) {
+                // the span ends inside this copy: its front is copied, and that is the end
+                if (len > out_cap - op) {
+                    len = out_cap - op;
+                    span_full = true;
+                }
+            } else {
+                if (len > out_cap - op) { msg = kMsgOutFull; break; }
+            }
             wave_sync();                                                              // earlier literals are in the ring
             const int src0 = (int)op - (int)dist;
             if (dist <= kNear && dist <= op && dist >= len && len <= 64u) {
@@ -588,11 +616,15 @@
                     if (sp >= (int)flushed) v = L.ring[(a0 + (uint32_t)sp) & M];
                     else if (PART && sp < 0) v = (T)(256 + 32768 + sp);      // a byte of the 32 KiB in front of this part
                     else if (DICT && sp < 0) v = (T)hist_end[sp];            // a byte of the shared window
+                    else if (SPAN && sp < 0) v = (T)span_hist[sp];           // a byte of the job's own window
                     else v = out[sp];
                     L.ring[(a0 + op + i) & M] = v;
                 }
             }
             op += len;
+            if constexpr (SPAN) {
+                if (span_full) { msg = kMsgOutFull; break; }
+            }
         }
         if (SUB && handed) break;
         if (PART && !last && msg == kMsgNone && block_end_stop()) break;
@@ -631,6 +663,9 @@
             }
         }
         return;
+    }
+    if constexpr (SPAN) {
+        if (msg == kMsgOutFull) msg = kMsgNone;         // out_cap bytes are in place: the span's expected end, status 1
     }
     if (lane == 0) {
         const unsigned long long used = (bit_pos() + 7ull) >> 3;

@@ -494,6 +494,99 @@ def bgzf_read_dev(src_dev, members, ranges, scratch_bytes=0, stream=None):
     return st, out, counters
 
 
+
+class AccessPoint(C.Structure):
+    """zng_rocm_access_point"""
+    _fields_ = [("in_bit", C.c_uint64), ("out_off", C.c_uint64), ("window_len", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class InflateRange(BgzfRange):
+    """zng_rocm_inflate_range: the fields of zng_rocm_bgzf_range"""
+
+
+class InflateIndex:
+    """A zng_rocm_inflate_index: access points into ONE raw deflate (fmt 0), zlib (1) or gzip (2) stream in device memory.
+    Made by InflateIndex.build() or InflateIndex.load(); immutable; close() (or the garbage collector) frees it."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @classmethod
+    def build(cls, fmt, src_dev, dst, span_bytes=0, piece_bytes=0, stream=None, subblock=False, flags=None):
+        """zng_rocm_inflate_index_build_dev.  Returns (status, bytes produced, member bytes used, index or None): the first
+        three are uncompress_large_dev's for the same arguments (the last_* counters too); an index exists on status 1."""
+        rocm._need_init()
+        lib = rocm.lib()
+        out_len, in_used, h = C.c_uint64(0), C.c_size_t(0), C.c_void_p(None)
+        fl = (SUBBLOCK if subblock else 0) if flags is None else int(flags)
+        n, cap = int(src_dev.numel()), int(dst.numel())
+        st = lib.zng_rocm_inflate_index_build_dev(int(fmt), rocm._dev_ptr(src_dev) if n else None, n, rocm._dev_ptr(dst) if cap else None,
+                                                  cap, C.byref(out_len), C.byref(in_used), int(span_bytes), int(piece_bytes), fl,
+                                                  C.byref(h), rocm._stream_ptr(stream))
+        return st, int(out_len.value), int(in_used.value), cls(h.value) if h.value else None
+
+    @classmethod
+    def load(cls, blob, stream=None):
+        """zng_rocm_inflate_index_import_dev: (return value, index or None) from the bytes save() gave"""
+        rocm._need_init()
+        raw = bytes(blob)
+        h = C.c_void_p(None)
+        st = rocm.lib().zng_rocm_inflate_index_import_dev(raw, len(raw), C.byref(h), rocm._stream_ptr(stream))
+        return st, cls(h.value) if h.value else None
+
+    def save(self, stream=None):
+        """zng_rocm_inflate_index_export: the index as bytes"""
+        lib = rocm.lib()
+        need = C.c_size_t(0)
+        lib.zng_rocm_inflate_index_export(self._h, None, 0, C.byref(need), rocm._stream_ptr(stream))
+        buf = (C.c_uint8 * max(need.value, 1))()
+        rocm._check(lib.zng_rocm_inflate_index_export(self._h, buf, need.value, C.byref(need), rocm._stream_ptr(stream)),
+                    "zng_rocm_inflate_index_export")
+        return bytes(buf[:need.value])
+
+    def points(self):
+        """[(in_bit, out_off, window_len)]"""
+        lib = rocm.lib()
+        n = int(lib.zng_rocm_inflate_index_points(self._h, None, 0))
+        pts = (AccessPoint * max(n, 1))()
+        lib.zng_rocm_inflate_index_points(self._h, C.cast(pts, C.c_void_p), n)
+        return [(int(p.in_bit), int(p.out_off), int(p.window_len)) for p in pts[:n]]
+
+    @property
+    def plain_len(self):
+        return int(rocm.lib().zng_rocm_inflate_index_plain_len(self._h))
+
+    def read(self, src_dev, ranges, scratch_bytes=0, stream=None, src_len=None):
+        """zng_rocm_inflate_index_read_dev: `ranges` = [(uoff, len, dst)] with dst a uint8 CUDA tensor of at least len bytes, a
+        device address or None; `src_len`: the file's length when it is not all of `src_dev`.  Returns (return value,
+        [(status, out_len, msg)] per range, counters) with counters = {"decoded", "direct", "rounds"}."""
+        rocm._need_init()
+        lib = rocm.lib()
+        n = int(src_dev.numel()) if src_len is None else int(src_len)
+        rs = (InflateRange * max(len(ranges), 1))()
+        for k, (uoff, length, dst) in enumerate(ranges):
+            rs[k] = InflateRange(int(uoff), int(length), None if dst is None else int(dst) if isinstance(dst, int) else dst.data_ptr(),
+                                 0, 0, None)
+        st = lib.zng_rocm_inflate_index_read_dev(self._h, rocm._dev_ptr(src_dev) if n else None, n, C.cast(rs, C.c_void_p), len(ranges),
+                                                 int(scratch_bytes), rocm._stream_ptr(stream))
+        out = [(int(r.status), int(r.out_len), None if r.msg is None else r.msg.decode()) for r in rs[:len(ranges)]]
+        counters = {"decoded": int(lib.zng_rocm_inflate_index_read_last_decoded()),
+                    "direct": int(lib.zng_rocm_inflate_index_read_last_direct()),
+                    "rounds": int(lib.zng_rocm_inflate_index_read_last_rounds())}
+        return st, out, counters
+
+    def close(self):
+        if self._h:
+            rocm.lib().zng_rocm_inflate_index_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def bgzf_voffset(members, uoff):
     """zng_rocm_bgzf_voffset: the virtual offset of plaintext byte `uoff` (htslib's convention), or None when the call refuses;
     needs no device"""

@@ -169,6 +169,18 @@ _PROTOS = {
     "zng_rocm_bgzf_read_last_rounds": (C.c_int, []),
     "zng_rocm_bgzf_voffset": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, C.POINTER(C.c_uint64)]),
     "zng_rocm_bgzf_uoffset": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "zng_rocm_inflate_index_build_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64),
+                                                   C.POINTER(C.c_size_t), C.c_uint64, C.c_size_t, C.c_uint32,
+                                                   C.POINTER(C.c_void_p), C.c_void_p]),
+    "zng_rocm_inflate_index_read_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]),
+    "zng_rocm_inflate_index_points": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "zng_rocm_inflate_index_plain_len": (C.c_uint64, [C.c_void_p]),
+    "zng_rocm_inflate_index_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]),
+    "zng_rocm_inflate_index_import_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.c_void_p]),
+    "zng_rocm_inflate_index_destroy": (None, [C.c_void_p]),
+    "zng_rocm_inflate_index_read_last_decoded": (C.c_int, []),
+    "zng_rocm_inflate_index_read_last_direct": (C.c_int, []),
+    "zng_rocm_inflate_index_read_last_rounds": (C.c_int, []),
     "zng_rocm_wrapper_parse": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_char_p)]),
     "zng_rocm_workspace_bytes": (C.c_size_t, [C.c_void_p]),
     "zng_rocm_hook_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_size_t]),
