@@ -550,11 +550,52 @@ const char *zng_rocm_inflate_message(uint32_t id);
  *   counting header and trailer; message ids include "incorrect header check", "unknown compression method", "invalid
  *   window size", "header crc mismatch", "need dictionary", "incorrect data check", "incorrect length check".  This call
  *   holds no dictionary, so a zlib member with FDICT is "need dictionary" (-3; uncompr.c:70-75);
- *   zng_rocm_uncompress_streams_dict_dev below is the call that reads such members. */
+ *   zng_rocm_uncompress_streams_dict_dev below is the call that reads such members.
+ * Levels 0..9, every strategy and canonical wrappers for a batch: zng_rocm_compress_streams2_dev / _members_dev below. */
 size_t zng_rocm_compress_streams_bound(size_t source_len, int format);
 int  zng_rocm_compress_streams_dev(int format, const zng_rocm_stream_job *jobs, size_t njobs, uint32_t *d_results, void *stream);
 int  zng_rocm_uncompress_streams_dev(int format, const zng_rocm_inflate_dev_job *jobs, size_t njobs, uint32_t *d_results,
                                      void *stream);
+
+/* Many wrapped streams at EVERY level and strategy -- compress2 (compress.c:31-69) / deflateInit2 + deflate(Z_FINISH) over a whole
+ * batch, in place or as one file.  Asynchronous on `stream`: no host synchronisation and no device-to-host copy inside the
+ * calls; the result words are valid once the stream has got there.  (With more than one round the host waits, between rounds,
+ * for the upload of the round before's segment table -- an event, not the stream.)
+ *   format       0 raw, 1 zlib, 2 gzip
+ *   level        -1 (= 6, deflate.c:296) or 0..9
+ *   strategy     0..4 as zng_rocm_deflate_strategy_streams_dev
+ *   jobs         HOST array (copied internally); in / in_len / dict_len / flags as zng_rocm_deflate_block_dev; a wrapped format
+ *                takes neither dict_len nor flags; no alignment is asked of in or out
+ *   round_bytes  plaintext per round (one set of launches); 0 = 4 GiB; a job is never split, so a round has at least one job
+ * The members are canonical (no padding, unlike the 12-byte wrappers of zng_rocm_compress_streams_dev):
+ *   zlib   CMF FLG with FLEVEL as deflate.c:868-885 sets it (0 for strategy >= Z_HUFFMAN_ONLY or level < 2) | data | Adler-32,
+ *          most significant byte first (deflate.c:1098-1101)
+ *   gzip   the 10 bytes of deflate.c:902-913 -- no name, no extra field, mtime 0, XFL by the same rule (:911-912), OS 3 | data |
+ *          CRC-32, ISIZE, little endian (deflate.c:1091-1096)
+ *   data   levels 1..9: exactly the bytes zng_rocm_deflate_strategy_streams_dev writes for the same job list, level and
+ *          strategy (the segment size is chosen once from the call's whole plaintext); level 0: exactly the bytes
+ *          zng_rocm_deflate_strategy_block_dev writes per job at level 0 (deflate_stored.c:46-95: stored blocks of 65535 bytes)
+ * Check values: Adler-32 for formats 0 and 1, CRC-32 for format 2, of every plaintext in one many-message pass per round.
+ * Refused with ZNG_ROCM_EINVAL before anything is launched or written: format / level / strategy out of range, a null pointer,
+ * dict_len > 32768, flags other than ZNG_ROCM_BLOCK_*, dict_len or flags in a wrapped format, a job whose
+ * zng_rocm_compress_bound(in_len, format) does not fit 32 bits.  njobs == 0 returns 0.
+ *
+ * zng_rocm_compress_streams2_dev: member i goes to jobs[i].out, out_cap >= zng_rocm_compress_streams2_bound(in_len, format)
+ *   (= zng_rocm_compress_bound; a smaller one returns -5 with nothing launched).  d_results (device): 2 words per job {bytes
+ *   written, check value}, as zng_rocm_compress_streams_dev.
+ * zng_rocm_compress_members_dev: the members stand back to back in d_dst -- for gzip the multi-member file of RFC 1952 2.2 (what
+ *   `cat a.gz b.gz` makes and zng_rocm_gunzip_members_dev reads); out / out_cap of the jobs are not looked at.  d_offsets
+ *   (device, njobs + 1): d_offsets[i] = first byte of member i, d_offsets[njobs] = the file's length.  A length above dst_cap
+ *   means the file did not fit: then no byte at or behind d_dst + dst_cap is written and the bytes in front of it are those of
+ *   the file that fits.  d_checks (device, njobs, may be NULL): the check values.
+ * zng_rocm_compress_streams2_last_rounds: rounds of the calling thread's last call of either. */
+size_t zng_rocm_compress_streams2_bound(size_t source_len, int format);
+int    zng_rocm_compress_streams2_dev(int format, int level, int strategy, const zng_rocm_stream_job *jobs, size_t njobs,
+                                      size_t round_bytes, uint32_t *d_results, void *stream);
+int    zng_rocm_compress_members_dev(int format, int level, int strategy, const zng_rocm_stream_job *jobs, size_t njobs,
+                                     uint8_t *d_dst, size_t dst_cap, size_t round_bytes, uint64_t *d_offsets, uint32_t *d_checks,
+                                     void *stream);
+int    zng_rocm_compress_streams2_last_rounds(void);
 
 /* ---- one preset dictionary shared by many small device-resident streams -----------------------------------------------
  * deflateSetDictionary / inflateSetDictionary (deflate.c:456-512, inflate.c:1234-1260) for the many-stream calls above.  The
@@ -942,6 +983,7 @@ int  zng_rocm_inflate_raw_threads(const uint8_t *src, size_t src_len, const uint
  *                  -1 = 6, 0 = stored blocks, 1..9 as zng_rocm_deflate_dev, anything else Z_STREAM_ERROR (-2,
  *                  deflate.c:318-320); the zlib FLEVEL / gzip XFL hints are those of the requested level
  *                  (deflate.c:868-885, :913).  Returns Z_OK (0) / Z_BUF_ERROR (-5) / error.
+ *                  Many streams in one asynchronous call: zng_rocm_compress_streams2_dev / zng_rocm_compress_members_dev.
  * uncompress2_dev: src (HOST, the sequential bitstream stays on the host) -> d_dst (device).  On return *dst_len
  *                  = plaintext bytes, *src_len = input bytes consumed.  Z_OK, Z_BUF_ERROR (destination too small),
  *                  Z_DATA_ERROR with the reference's message text in zng_rocm_last_error() ("incorrect header

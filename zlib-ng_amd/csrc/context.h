@@ -94,6 +94,9 @@ enum ScratchSlot {
     kScrIndexRead,          // device: the engine's results | jobs | span table | slices | the edge spans' slots
                             //   (zng_rocm_inflate_index_read_dev); the window moves of zng_rocm_inflate_index_build_dev
     kScrIndexReadHost,      // pinned: jobs | span table | slices on their way up | the results on their way down
+    kScrCompressStreams,    // device: file offset | job table of the whole call | a round's check values
+                            //   (zng_rocm_compress_streams2_dev, zng_rocm_compress_members_dev)
+    kScrCompressStreamsHost, // pinned: the job table on its way up
     kScrCount
 };
 

@@ -1,6 +1,7 @@
 // deflate_blocks.h -- what the rows engine (deflate_dyn.hip: lz_rows_kernel, emit_dynamic_kernel, segments_scan_kernel) leaves
 // on the device for a caller that places the blocks itself instead of having gather_segments_kernel pack them into one buffer
-// per stream: the BGZF writer (bgzf.hip) moves every block from its slot straight to its byte in the file.
+// per stream: the BGZF writer (bgzf.hip) and the many-stream wrapped calls (compress_streams.hip) move every block from its slot
+// straight to its byte in the file or member.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -44,5 +45,13 @@ struct RowsBlocks {
 // Asynchronous on `st`; the caller holds ws->mu.
 int deflate_rows_enqueue_blocks(int level, const zng_rocm_stream_job *sjobs, size_t njobs, Workspace *ws, hipStream_t st,
                                 RowsBlocks *blocks);
+
+// The same for streams of any length and any strategy (0..4, as zng_rocm_deflate_strategy_streams_dev): every stream is cut into
+// segments of seg_bytes, and the blocks of all segments of a stream follow one another in the table, in_stream[] counting on
+// through the stream.  seg_bytes is what deflate_rows_segment_bytes() gives for the plaintext of the caller's WHOLE call, so that
+// the blocks are those zng_rocm_deflate_strategy_streams_dev writes for the same job list (compress_streams.hip).
+uint32_t deflate_rows_segment_bytes(size_t total_in);
+int deflate_rows_enqueue_streams(int level, int strategy, const zng_rocm_stream_job *sjobs, size_t njobs, uint32_t seg_bytes,
+                                 Workspace *ws, hipStream_t st, RowsBlocks *blocks);
 
 }  // namespace zr

@@ -984,6 +984,14 @@ int deflate_rows_enqueue_blocks(int level, const zng_rocm_stream_job *sjobs, siz
     return deflate_rows_enqueue(level, 0, sjobs, njobs, nullptr, kSegBytesMin, ws, st, &unused, nullptr, blocks);
 }
 
+uint32_t deflate_rows_segment_bytes(size_t total_in) { return segment_bytes(total_in, ctx()->cus); }
+
+int deflate_rows_enqueue_streams(int level, int strategy, const zng_rocm_stream_job *sjobs, size_t njobs, uint32_t seg_bytes,
+                                 Workspace *ws, hipStream_t st, RowsBlocks *blocks) {
+    unsigned long long *unused = nullptr;
+    return deflate_rows_enqueue(level, strategy, sjobs, njobs, nullptr, seg_bytes, ws, st, &unused, nullptr, blocks);
+}
+
 }  // namespace zr
 
 using namespace zr;

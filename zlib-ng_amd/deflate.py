@@ -255,3 +255,48 @@ def bgzf_compress_dev(src_dev, dst, level=-1, block_bytes=0, members_cap=None, r
             for m in (GzipMember * min(cap, int(nmembers.value))).from_buffer(table)]
     counters = {"rounds": int(lib.zng_rocm_bgzf_last_rounds()), "stored": int(lib.zng_rocm_bgzf_last_stored())}
     return st, int(out_len.value), rows, int(nmembers.value), counters
+
+
+def compress_streams2_bound(n, fmt):
+    return rocm.lib().zng_rocm_compress_streams2_bound(int(n), int(fmt))
+
+
+def stream_jobs(srcs, dsts=None, dict_len=None, flags=None):
+    """zng_rocm_stream_job[] for the two calls below: srcs[i] a uint8 CUDA tensor (a view at any address; its dict_len[i] bytes
+    of history lie in front of it in the same storage), dsts[i] the buffer of member i (None: out / out_cap stay 0, as
+    compress_members_dev wants them)."""
+    jobs = (StreamJob * max(len(srcs), 1))()
+    for i, s in enumerate(srcs):
+        jobs[i].in_ptr = s.data_ptr() if s.numel() else None
+        jobs[i].in_len = int(s.numel())
+        if dsts is not None:
+            jobs[i].out_ptr = dsts[i].data_ptr()
+            jobs[i].out_cap = int(dsts[i].numel())
+        jobs[i].dict_len = 0 if dict_len is None else int(dict_len[i])
+        jobs[i].flags = 0 if flags is None else int(flags[i])
+    return jobs
+
+
+def compress_streams2_dev(jobs, njobs, results, fmt, level=-1, strategy=0, round_bytes=0, stream=None):
+    """zng_rocm_compress_streams2_dev: every job deflated at `level` (-1 = 6, 0..9) and `strategy` (0..4) and wrapped (fmt 0 raw,
+    1 zlib, 2 gzip) into its own buffer; `results` an int32 CUDA tensor [njobs, 2] = {bytes written, check value}, valid once
+    `stream` has got there.  Returns the status (0, ZNG_ROCM_E*, -5)."""
+    rocm._need_init()
+    return rocm.lib().zng_rocm_compress_streams2_dev(int(fmt), int(level), int(strategy), C.byref(jobs), int(njobs), int(round_bytes),
+                                                     rocm._dev_ptr(results) if results is not None else None, rocm._stream_ptr(stream))
+
+
+def compress_members_dev(jobs, njobs, dst, offsets, fmt, level=-1, strategy=0, round_bytes=0, checks=None, stream=None):
+    """zng_rocm_compress_members_dev: the members back to back in the uint8 CUDA tensor `dst` (dst.numel() is dst_cap; None: no
+    destination); `offsets` an int64 CUDA tensor of njobs + 1 (member starts, then the file's length -- above dst_cap when the
+    file did not fit), `checks` an int32 CUDA tensor of njobs or None.  Returns the status."""
+    rocm._need_init()
+    cap = int(dst.numel()) if dst is not None else 0
+    return rocm.lib().zng_rocm_compress_members_dev(int(fmt), int(level), int(strategy), C.byref(jobs), int(njobs),
+                                                    rocm._dev_ptr(dst) if cap else None, cap, int(round_bytes),
+                                                    rocm._dev_ptr(offsets) if offsets is not None else None,
+                                                    rocm._dev_ptr(checks) if checks is not None else None, rocm._stream_ptr(stream))
+
+
+def compress_streams2_last_rounds():
+    return int(rocm.lib().zng_rocm_compress_streams2_last_rounds())

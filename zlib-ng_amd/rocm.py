@@ -106,6 +106,12 @@ _PROTOS = {
     "zng_rocm_compress_streams_bound": (C.c_size_t, [C.c_size_t, C.c_int]),
     "zng_rocm_compress_streams_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "zng_rocm_uncompress_streams_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "zng_rocm_compress_streams2_bound": (C.c_size_t, [C.c_size_t, C.c_int]),
+    "zng_rocm_compress_streams2_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p,
+                                                 C.c_void_p]),
+    "zng_rocm_compress_members_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "zng_rocm_compress_streams2_last_rounds": (C.c_int, []),
     "zng_rocm_dict_create_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "zng_rocm_dict_destroy": (None, [C.c_void_p]),
     "zng_rocm_dict_id": (C.c_uint32, [C.c_void_p]),
