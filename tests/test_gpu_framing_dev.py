@@ -8,6 +8,7 @@ zng_rocm_uncompress_streams_dev): every step on the device.
   * the reference's messages for damaged wrappers (inflate.c:509-555, :686-692, :1105-1147);
   * the reference's own .gz fixtures (tests/golden/ref_fixtures)."""
 import gzip
+import hashlib
 import importlib
 import io
 import struct
@@ -18,6 +19,7 @@ import pytest
 
 import ref_fixtures
 import synth
+import wrapper_cases
 from gpu_common import product, torch_mod
 
 pytestmark = pytest.mark.gpu
@@ -169,6 +171,42 @@ def test_damaged_wrappers_give_the_reference_messages(mods):
     bad = hdr + struct.pack("<H", (zlib.crc32(hdr) ^ 1) & 0xffff) + body + struct.pack("<II", zlib.crc32(p), len(p))
     rows, _ = _uncompress(inf, [bad], [len(p)], 2)
     assert (rows[0][0], rows[0][3]) == (-3, "header crc mismatch")
+
+
+def test_cut_and_damaged_headers_of_short_members(mods):
+    """one batch per format, members of at most a few hundred bytes into 64-byte outputs: a gzip member short of ten bytes is
+    starved whatever its bytes are, unknown flag bits are a header check failure, and a zlib header with FDICT needs a
+    dictionary even where the DICTID is cut short"""
+    zr, dfl, inf = mods
+    cases = wrapper_cases.cut_and_damaged_members()
+    for fmt in (1, 2):
+        sel = [c for c in cases if c[0] == fmt]
+        assert sel and max(len(c[1]) for c in sel) < 300
+        rows, _ = _uncompress(inf, [c[1] for c in sel], [64] * len(sel), fmt)
+        for c, r in zip(sel, rows):
+            assert r == (c[2], 0, 0, c[3]), (fmt, c[1].hex(), r)
+
+
+# sha256 of what zng_rocm_compress_streams_dev (the level-1 class; the call has no level) writes for wrapper_cases.PLAIN_4K,
+# recorded before the wrapper rules moved to framing_parse.h
+STREAMS_DIGEST = {
+    1: "cbb420e6cf44750337dc4283ba0ecca6b67bc5a1bbd2c62d8ff1d82e0fc77555",
+    2: "c08829cc0884f261267a1a5b52bafd47a0379fd2271b5fce50b2b5154cc0692c",
+}
+
+
+@pytest.mark.parametrize("fmt", [1, 2])
+def test_wrapped_bytes_are_the_recorded_ones(mods, fmt):
+    zr, dfl, inf = mods
+    torch = torch_mod()
+    p = wrapper_cases.PLAIN_4K
+    src = torch.from_numpy(np.frombuffer(p + b"\0" * 16, dtype=np.uint8).copy()).cuda()
+    wb = dfl.WrappedBatch(src, [0], [len(p)], fmt)
+    wb.run()
+    c = wb.compressed(0)
+    print("compress_streams_dev", fmt, hashlib.sha256(c).hexdigest())
+    assert zlib.decompressobj(15 if fmt == 1 else 31).decompress(c) == p
+    assert hashlib.sha256(c).hexdigest() == STREAMS_DIGEST[fmt]
 
 
 def test_reference_gz_fixtures(mods):

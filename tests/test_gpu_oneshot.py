@@ -1,6 +1,7 @@
 """GPU: compress2 / uncompress2 class front ends -- zlib and gzip framing with on-device trailer checksums.
 Cross-checked both ways against CPython's zlib/gzip (independent codec) and the reference's messages."""
 import gzip
+import hashlib
 import importlib
 import zlib
 
@@ -8,6 +9,7 @@ import numpy as np
 import pytest
 
 import synth
+import wrapper_cases
 from gpu_common import product, torch_mod
 
 pytestmark = pytest.mark.gpu
@@ -84,6 +86,41 @@ def test_uncompress2_errors_use_reference_messages(one):
     kat = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "inflate_kat.json")))["zlib_stream"]
     rc, produced, consumed, msg = one.uncompress2_dev(bytes.fromhex(kat["hex"]), dst, fmt=one.ZLIB)
     assert rc == 0 and dst[:produced].cpu().numpy().tobytes() == kat["plaintext"].encode()
+
+
+def test_cut_and_damaged_headers_of_short_members(one):
+    """the members of tests/wrapper_cases.py one by one: every one is Z_DATA_ERROR with this call's own text"""
+    torch = torch_mod()
+    dst = torch.zeros(64, dtype=torch.uint8, device="cuda")
+    for fmt, member, _, _, text in wrapper_cases.cut_and_damaged_members():
+        rc, _, _, msg = one.uncompress2_dev(member, dst, fmt=fmt)
+        assert (rc, msg) == (-3, text), (fmt, member.hex(), rc, msg)
+
+
+# sha256 of what zng_rocm_compress2_dev writes for wrapper_cases.PLAIN_4K, recorded before the wrapper rules moved to
+# framing_parse.h: (format, level)
+COMPRESS2_DIGEST = {
+    (1, 1): "5d05d5dc979d3b6f86cb94b99ea491fc216aa5bad58c5675298237bc618f09bd",
+    (1, 6): "beae34117ab74e470041a2282fdfc52728e41ee7608b359585835e27c40f79a0",
+    (1, 9): "907b2e6da6db33e927ec4e789747b3e4e91d27672a22207ecff045e7b44cffec",
+    (2, 1): "5c3e07e50e91ea1fca97d03b808b84ac8d9e223c8feef620984720213abed34e",
+    (2, 6): "f8c7f033e655a64db654e9d6cd046f26bc5be68c599d7d1bd25321e700042cd2",
+    (2, 9): "16069de5c76ffaed1251eb639794f1b50858002ef63633caac643839f08a2a24",
+}
+
+
+def test_compress2_bytes_are_the_recorded_ones(one):
+    torch = torch_mod()
+    p = wrapper_cases.PLAIN_4K
+    src = torch.from_numpy(np.frombuffer(p + b"\0" * 16, dtype=np.uint8).copy()).cuda()
+    got = {}
+    for (fmt, level) in COMPRESS2_DIGEST:
+        dst, clen = one.compress2_dev(src, level=level, fmt=fmt, length=len(p))
+        comp = dst[:clen].cpu().numpy().tobytes()
+        assert zlib.decompressobj(15 if fmt == 1 else 31).decompress(comp) == p
+        got[(fmt, level)] = hashlib.sha256(comp).hexdigest()
+        print("compress2_dev", fmt, level, got[(fmt, level)])
+    assert got == COMPRESS2_DIGEST
 
 
 def test_a_large_member_is_inflated_on_the_device(one):

@@ -5,7 +5,8 @@ out-of-line call marker tests/test_kernel_isa.py looks for.
                                deflate_quick_kernel, so eight workgroups per CU still fit
   inflate_streams_dict_kernel  the dictionary form of the stream inflater: no more LDS than the ring-4096 stream form
   dict_head_kernel             the primed head table (dict.hip)
-  frame_compress_dict_kernel, parse_header_dict_kernel, verify_trailer_dict_kernel   the 16-byte FDICT wrapper (framing_dev.hip)"""
+  frame_compress_kernel, parse_header_kernel, verify_trailer_kernel   the wrapper kernels, which write and judge the 16-byte
+                               FDICT wrapper as well (framing_dev.hip)"""
 import os
 import re
 import shutil
@@ -72,6 +73,6 @@ def test_head_table_and_framing_kernels():
     assert len(head) == 1, sorted(head)
     assert _one(head, "dict_head_kernel") == (0, 0, 0, 256)
     framing = _kernels("framing_dev.hip")
-    for name in ("frame_compress_dict_kernel", "parse_header_dict_kernel", "verify_trailer_dict_kernel"):
+    for name in ("frame_compress_kernel", "parse_header_kernel", "verify_trailer_kernel"):
         scratch, spills, lds, wg = _one(framing, name)
         assert (scratch, spills, lds, wg) == (0, 0, 0, 256), (name, scratch, spills, lds, wg)

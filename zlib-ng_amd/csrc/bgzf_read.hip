@@ -51,8 +51,8 @@ void bgzf_index_link_kernel(const uint8_t *__restrict__ src, uint64_t src_len, c
     BgzfIndexRow r = {p, end, bgzf ? (uint32_t)h.header_len : 0u, 0u, 0u, bgzf_index_flags(bgzf, h.status == -5, p, end, h.header_len, src_len)};
     if (r.flags & kIdxTrailer) {                         // (end <= src_len and end - 8 >= p: inside the file)
         const uint8_t *t = src + end - 8;
-        r.crc = t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
-        r.isize = t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) | ((uint32_t)t[7] << 24);
+        r.crc = wrapper_le32(t);
+        r.isize = wrapper_le32(t + 4);
     }
     if ((r.flags & kIdxInside) && src_len - end >= 2 && src[end] == 0x1fu && src[end + 1] == 0x8bu) r.flags |= kIdxNextMagic;
     rows[i] = r;

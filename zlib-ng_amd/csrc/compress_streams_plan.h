@@ -1,9 +1,9 @@
 // compress_streams_plan.h -- the rules of zng_rocm_compress_streams2_dev and zng_rocm_compress_members_dev (compress_streams.hip):
 // many device-resident streams deflated at any level and strategy and wrapped as raw / zlib / gzip members, each in its own
 // buffer or all back to back in one destination.  Plain C++ over integers, no HIP: the argument checks, the cut of the job list
-// into rounds, the header and trailer bytes by format, level and strategy, the stored (level 0) sizes and block headers, and
-// the bounds.  The rules the kernels apply as well are written once for host and device; tests/test_compress_streams_plan_cpu.py
-// drives them through tests/c/compress_streams_plan_driver.cpp without a GPU.
+// into rounds, the stored (level 0) sizes and block headers, and the bounds; the header and trailer bytes by format, level and
+// strategy are the canonical writer of framing_parse.h.  The rules the kernels apply as well are written once for host and
+// device; tests/test_compress_streams_plan_cpu.py drives them through tests/c/compress_streams_plan_driver.cpp without a GPU.
 //
 // A member is  header | raw deflate data | trailer:
 //   format 0 raw    nothing | data | nothing
@@ -14,6 +14,7 @@
 #include <stdint.h>
 
 #include "../../include/zng_rocm.h"
+#include "framing_parse.h"     // the wrapper's rules
 #include "gf2.h"      // ZR_HD
 
 namespace zr {
@@ -33,31 +34,13 @@ ZR_HD bool cs_format_ok(int format) { return format >= 0 && format <= 2; }
 ZR_HD bool cs_strategy_ok(int strategy) { return strategy >= 0 && strategy <= 4; }
 
 // ---- the wrapper --------------------------------------------------------------------------------------------------------
-ZR_HD uint32_t cs_head_bytes(int format) { return format == 1 ? 2u : format == 2 ? 10u : 0u; }
-ZR_HD uint32_t cs_tail_bytes(int format) { return format == 1 ? 4u : format == 2 ? 8u : 0u; }
-
-// FLEVEL of the zlib header (deflate.c:873-880) and XFL of the gzip header (deflate.c:911-912); level is 0 .. 9
-ZR_HD uint32_t cs_zlib_flevel(int level, int strategy) {
-    return (strategy >= 2 || level < 2) ? 0u : level < 6 ? 1u : level == 6 ? 2u : 3u;
-}
-ZR_HD uint32_t cs_gzip_xfl(int level, int strategy) { return level == 9 ? 2u : (strategy >= 2 || level < 2) ? 4u : 0u; }
-
-// byte k (0 .. cs_head_bytes - 1) of the header
-ZR_HD uint8_t cs_header_byte(int format, int level, int strategy, uint32_t k) {
-    if (format == 1) {
-        uint32_t header = ((8u + (7u << 4)) << 8) | (cs_zlib_flevel(level, strategy) << 6);     // Z_DEFLATED, w_bits 15
-        header += 31u - header % 31u;
-        return (uint8_t)(header >> (k == 0u ? 8 : 0));
-    }
-    // gzip: ID1 ID2 CM FLG | MTIME x 4 | XFL OS
-    return k == 0u ? (uint8_t)0x1fu : k == 1u ? (uint8_t)0x8bu : k == 2u ? (uint8_t)8u : k == 8u ? (uint8_t)cs_gzip_xfl(level, strategy)
-         : k == 9u ? (uint8_t)3u : (uint8_t)0u;
-}
-// byte k (0 .. cs_tail_bytes - 1) of the trailer around n plaintext bytes whose check value (Adler-32; gzip: CRC-32) is `check`
-ZR_HD uint8_t cs_trailer_byte(int format, uint32_t k, uint32_t check, uint32_t n) {
-    if (format == 1) return (uint8_t)(check >> (8u * (3u - k)));
-    return (uint8_t)((k < 4u ? check : n) >> (8u * (k & 3u)));
-}
+// the canonical writer of framing_parse.h under this plan's names: no rule is restated here
+ZR_HD uint32_t cs_head_bytes(int format) { return wrapper_head_bytes(format); }
+ZR_HD uint32_t cs_tail_bytes(int format) { return wrapper_tail_bytes(format); }
+ZR_HD uint32_t cs_zlib_flevel(int level, int strategy) { return wrapper_zlib_flevel(level, strategy); }
+ZR_HD uint32_t cs_gzip_xfl(int level, int strategy) { return wrapper_gzip_xfl(level, strategy); }
+ZR_HD uint8_t cs_header_byte(int format, int level, int strategy, uint32_t k) { return wrapper_header_byte(format, level, strategy, k); }
+ZR_HD uint8_t cs_trailer_byte(int format, uint32_t k, uint32_t check, uint32_t n) { return wrapper_trailer_byte(format, k, check, n); }
 
 // ---- level 0 ------------------------------------------------------------------------------------------------------------
 // deflate_stored for a complete input and an output that holds everything (deflate_stored.c:46-95): blocks of 65535 bytes, an

@@ -13,6 +13,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "framing_parse.h"
 #include "gf2.h"      // ZR_HD
 #include "inflate_dev_types.h"
 
@@ -57,10 +58,10 @@ ZR_HD void dict_put_header(uint8_t *out, uint32_t dictid) {
     for (uint32_t k = 0; k < kDictWrapHead; ++k) out[k] = dict_header_byte(k, dictid);
 }
 // the trailer: Adler-32 of the plaintext, most significant byte first (deflate.c:1098-1101)
-ZR_HD uint8_t dict_trailer_byte(uint32_t k, uint32_t adler) { return (uint8_t)(adler >> (8u * (3u - k))); }
+ZR_HD uint8_t dict_trailer_byte(uint32_t k, uint32_t adler) { return wrapper_trailer_byte(1, k, adler, 0u); }
 
 // What the reader makes of the first bytes of a zlib member (inflate.c:509-555 with windowBits 15, :702-715 DICTID) when it
-// holds the dictionary whose id is `dictid`:
+// holds the dictionary whose id is `dictid` -- wrapper_parse_rules (framing_parse.h) with the dictionary's judgement on top:
 //   msg      kMsgNone: decode from byte `pos` on; kDictMismatch: FDICT names another dictionary (pos = 6); else the header's
 //            fault as zng_rocm_uncompress_streams_dev reports it -- a header that ends inside the DICTID is a short header
 //   history  1: FDICT set and the ids agree, the payload is decoded with the dictionary; 0: FDICT clear, no history
@@ -68,24 +69,13 @@ struct DictHeader {
     uint32_t pos, msg, history;
 };
 ZR_HD DictHeader dict_parse_header(const uint8_t *in, uint64_t n, uint32_t dictid) {
-    DictHeader r = {0u, kMsgNone, 0u};
-    if (n < 2u) {
-        r.msg = kMsgStarved;
-        return r;
-    }
-    const uint32_t cmf = in[0], flg = in[1];
-    r.pos = 2u;
-    if (((cmf << 8) | flg) % 31u) r.msg = kMsgHeaderCheck;
-    else if ((cmf & 15u) != 8u) r.msg = kMsgMethod;
-    else if ((cmf >> 4) + 8u > 15u) r.msg = kMsgWindow;
-    else if (flg & 0x20u) {
-        if (n < kDictHeadParsed) {
-            r.msg = kMsgStarved;
-            return r;
-        }
-        const uint32_t id = ((uint32_t)in[2] << 24) | ((uint32_t)in[3] << 16) | ((uint32_t)in[4] << 8) | in[5];
+    const WrapperHead h = wrapper_parse_rules(1, LaneBytes{in}, n);         // the order of the checks lives there
+    DictHeader r = {n < 2u ? 0u : 2u, kMsgNone, 0u};
+    if (h.status == -5) r.msg = kMsgStarved;                                // inside CMF / FLG or inside the DICTID
+    else if (h.status == -3) r.msg = wrapper_inflate_msg(h.msg);
+    else if (h.fdict) {
         r.pos = kDictHeadParsed;
-        if (id == dictid) r.history = 1u;
+        if (h.dictid == dictid) r.history = 1u;
         else r.msg = kDictMismatch;
     }
     return r;

@@ -15,8 +15,11 @@
 //
 // The *_dict calls are the same two pipelines for raw and zlib streams that share ONE preset dictionary (zng_rocm_dict,
 // dict.hip; deflateSetDictionary / inflateSetDictionary, deflate.c:456-512, inflate.c:1234-1260): the level-1 class and the
-// inflater in their dictionary forms, and a 16-byte zlib wrapper with FDICT and the DICTID (dict_plan.h) -- the kernels
-// frame_compress_dict_kernel, parse_header_dict_kernel and verify_trailer_dict_kernel below.
+// inflater in their dictionary forms, and a 16-byte zlib wrapper with FDICT and the DICTID (dict_plan.h).  The same three
+// wrapper kernels and the same two host bodies serve both; with a dictionary the header is judged by dict_parse_header.
+//
+// The rules of the wrappers -- the order of the header checks, the FHCRC, the trailer's compare order, the trailer bytes -- are
+// framing_parse.h's; nothing of them is restated here.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -25,6 +28,7 @@
 #include "checksum_args.h"
 #include "context.h"
 #include "dict_dev.h"
+#include "framing_parse.h"
 #include "gf2.h"
 #include "inflate_dev.h"
 
@@ -35,196 +39,57 @@ extern "C" int zng_rocm_checksums_dev(int which, const zng_rocm_check_job *jobs,
 namespace zr {
 
 constexpr uint32_t kWrapHead = 12;                       // both wrapped formats (see above)
-__host__ __device__ inline uint32_t wrap_tail(int format) { return format == 1 ? 4u : format == 2 ? 8u : 0u; }
 
 struct FrameJob {
     uint8_t *out;
     uint64_t in_len;
 };
 
+// has_dict: the 16-byte head with FDICT and `dictid` (zlib; dict_plan.h) in place of the 12-byte one
 __global__ __launch_bounds__(256)
-void frame_compress_kernel(const FrameJob *__restrict__ jobs, uint32_t njobs, int format, const uint32_t *__restrict__ quick,
-                           const uint32_t *__restrict__ checks, uint32_t *__restrict__ results) {
+void frame_compress_kernel(const FrameJob *__restrict__ jobs, uint32_t njobs, int format, uint32_t dictid, int has_dict,
+                           const uint32_t *__restrict__ quick, const uint32_t *__restrict__ checks, uint32_t *__restrict__ results) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= njobs) return;
     uint8_t *out = jobs[i].out;
     const uint32_t clen = quick[2 * i], adler = quick[2 * i + 1];
     if (format == 0) {
         results[2 * i] = clen;
-        results[2 * i + 1] = adler;
+        results[2 * i + 1] = adler;                      // of the plaintext alone: a dictionary is in no check value
         return;
     }
     static const uint8_t zhead[12] = {0x78, 0x01, 0x00, 0x00, 0x00, 0xff, 0xff, 0x00, 0x00, 0x00, 0xff, 0xff};
     // ID1 ID2 CM=8 FLG=FEXTRA MTIME=0 XFL=4 (fastest, deflate.c:913-914) OS=3 (Unix) XLEN=0
     static const uint8_t ghead[12] = {0x1f, 0x8b, 0x08, 0x04, 0x00, 0x00, 0x00, 0x00, 0x04, 0x03, 0x00, 0x00};
-    for (int k = 0; k < 12; ++k) out[k] = format == 1 ? zhead[k] : ghead[k];
-    uint8_t *t = out + kWrapHead + clen;
-    if (format == 1) {                                   // Adler-32, most significant byte first (deflate.c:1098-1101)
-        t[0] = (uint8_t)(adler >> 24); t[1] = (uint8_t)(adler >> 16); t[2] = (uint8_t)(adler >> 8); t[3] = (uint8_t)adler;
-        results[2 * i + 1] = adler;
-    } else {                                             // CRC-32 and ISIZE, least significant byte first (deflate.c:1091-1096)
-        const uint32_t crc = checks[2 * i + 1], isize = (uint32_t)jobs[i].in_len;
-        for (int k = 0; k < 4; ++k) { t[k] = (uint8_t)(crc >> (8 * k)); t[4 + k] = (uint8_t)(isize >> (8 * k)); }
-        results[2 * i + 1] = crc;
-    }
-    results[2 * i] = kWrapHead + clen + wrap_tail(format);
+    if (has_dict) dict_put_header(out, dictid);
+    else for (int k = 0; k < 12; ++k) out[k] = format == 1 ? zhead[k] : ghead[k];
+    const uint32_t head = has_dict ? kDictWrapHead : kWrapHead, tail = wrapper_tail_bytes(format);
+    const uint32_t check = format == 1 ? adler : checks[2 * i + 1];
+    uint8_t *t = out + head + clen;
+    for (uint32_t k = 0; k < tail; ++k) t[k] = wrapper_trailer_byte(format, k, check, (uint32_t)jobs[i].in_len);
+    results[2 * i] = head + clen + tail;
+    results[2 * i + 1] = check;
 }
 
 // ---- uncompress side ---------------------------------------------------------------------------------------------------
+// without a dictionary: wrapper_parse_whole's verdict per member.  has_dict (raw and zlib): format 0 -- every job decodes with
+// the W bytes of the window as history; format 1 -- dict_parse_header's verdict: FDICT with `dictid` gives the history, with
+// another id kDictMismatch, and FDICT clear no history
 __global__ __launch_bounds__(256)
-void parse_header_kernel(const InflateJobDev *__restrict__ given, uint32_t njobs, int format,
-                         const DeviceTables *__restrict__ tabs, InflateJobDev *__restrict__ patched,
-                         uint32_t *__restrict__ head /* 2 per job: header bytes, message id */) {
+void parse_header_kernel(const InflateJobDev *__restrict__ given, uint32_t njobs, int format, uint32_t dictid, uint32_t W,
+                         int has_dict, const DeviceTables *__restrict__ tabs, InflateJobDev *__restrict__ patched,
+                         uint32_t *__restrict__ head /* 2 per job: header bytes, verdict */) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= njobs) return;
     const InflateJobDev j = given[i];
-    const uint8_t *in = j.in;
-    const uint64_t n = j.in_len;
-    uint64_t pos = 0;
-    uint32_t msg = kMsgNone;
-    if (format == 1) {                                   // inflate.c:509-555 with windowBits 15
-        if (n < 2) {
-            msg = kMsgStarved;
-        } else {
-            const uint32_t cmf = in[0], flg = in[1];
-            if (((cmf << 8) | flg) % 31u) msg = kMsgHeaderCheck;
-            else if ((cmf & 15u) != 8u) msg = kMsgMethod;
-            else if ((cmf >> 4) + 8u > 15u) msg = kMsgWindow;
-            else if (flg & 0x20u) msg = kMsgNeedDict;    // a preset dictionary: Z_DATA_ERROR for the one-shot caller (uncompr.c:70-75);
-                                                         // zng_rocm_uncompress_streams_dict_dev is the call that holds one
-            pos = 2;
-        }
-    } else if (format == 2) {                            // inflate.c:556-700
-        if (n < 10) {
-            msg = kMsgStarved;
-        } else if (in[0] != 0x1f || in[1] != 0x8b) {
-            msg = kMsgHeaderCheck;
-        } else if (in[2] != 8) {
-            msg = kMsgMethod;
-        } else if (in[3] & 0xe0u) {
-            msg = kMsgHeaderCheck;                       // "unknown header flags set": reported as a header check failure
-        } else {
-            const uint32_t flags = in[3];
-            pos = 10;
-            if (flags & 4u) {                            // FEXTRA
-                if (pos + 2 > n) msg = kMsgStarved;
-                else pos += 2u + (in[pos] | ((uint32_t)in[pos + 1] << 8));
-            }
-            for (uint32_t bit = 8; bit <= 16 && msg == kMsgNone; bit <<= 1) {      // FNAME, FCOMMENT: zero-terminated
-                if (!(flags & bit)) continue;
-                while (pos < n && in[pos]) ++pos;
-                if (pos >= n) msg = kMsgStarved;
-                else ++pos;
-            }
-            if (msg == kMsgNone && (flags & 2u)) {       // FHCRC: the low 16 bits of the CRC-32 of the header so far
-                if (pos + 2 > n) {
-                    msg = kMsgStarved;
-                } else {
-                    uint32_t c = 0xffffffffu;
-                    for (uint64_t k = 0; k < pos; ++k) c = tabs->byte_tab[(c ^ in[k]) & 0xffu] ^ (c >> 8);
-                    c = ~c;
-                    if ((c & 0xffffu) != (in[pos] | ((uint32_t)in[pos + 1] << 8))) msg = kMsgHeaderCrc;
-                    pos += 2;
-                }
-            }
-            if (msg == kMsgNone && pos > n) msg = kMsgStarved;
-        }
-    }
-    InflateJobDev p = j;
-    p.dict_len = 0;
-    if (msg != kMsgNone) {                               // nothing to decode: an empty job costs the inflater nothing
-        p.in_len = 0;
-        p.out_cap = 0;
+    DictHeader h = {0u, kMsgNone, has_dict ? 1u : 0u};
+    if (has_dict) {
+        if (format == 1) h = dict_parse_header(j.in, j.in_len, dictid);
     } else {
-        p.in = in + pos;
-        p.in_len = n - pos;
+        const WholeHead w = wrapper_parse_whole(format, LaneBytes{j.in}, j.in_len, tabs->byte_tab);
+        h.pos = (uint32_t)w.header_len;
+        h.msg = w.msg;
     }
-    patched[i] = p;
-    head[2 * i] = (uint32_t)pos;
-    head[2 * i + 1] = msg;
-}
-
-// the checksum descriptors of the inflated streams, as checksum.hip's host code builds them -- but from lengths that
-// only exist on the device
-__global__ __launch_bounds__(256)
-void fill_check_args_kernel(const InflateJobDev *__restrict__ jobs, const uint32_t *__restrict__ inflated, uint32_t njobs,
-                            const DeviceTables *__restrict__ tabs, int do_adler, int do_crc, StreamArgs *__restrict__ sa,
-                            FinalArgs *__restrict__ fa) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= njobs) return;
-    const uint64_t len = (int32_t)inflated[4 * i + 2] == 1 ? inflated[4 * i] : 0u;
-    fill_check_descriptor(jobs[i].out, len, tabs, do_adler, do_crc, sa + i, fa + i);
-}
-
-__global__ __launch_bounds__(256)
-void verify_trailer_kernel(const InflateJobDev *__restrict__ given, const uint32_t *__restrict__ head,
-                           const uint32_t *__restrict__ checks, uint32_t njobs, int format, uint32_t *__restrict__ results) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= njobs) return;
-    uint32_t out_len = results[4 * i], used = results[4 * i + 1], status = results[4 * i + 2], msg = results[4 * i + 3];
-    const uint32_t hdr = head[2 * i], hmsg = head[2 * i + 1];
-    if (hmsg != kMsgNone) {
-        out_len = 0;
-        used = 0;
-        msg = hmsg;
-        status = hmsg == kMsgStarved ? (uint32_t)-5 : (uint32_t)-3;
-    } else if ((int32_t)status == 1) {
-        const uint32_t tail = wrap_tail(format);
-        const uint64_t at = (uint64_t)hdr + used;
-        if (at + tail > given[i].in_len) {               // the stream ends before its trailer
-            status = (uint32_t)-5;
-            msg = kMsgStarved;
-            used = (uint32_t)given[i].in_len;
-        } else {
-            const uint8_t *t = given[i].in + at;
-            if (format == 1) {
-                const uint32_t stored = ((uint32_t)t[0] << 24) | ((uint32_t)t[1] << 16) | ((uint32_t)t[2] << 8) | t[3];
-                if (stored != checks[2 * i]) { status = (uint32_t)-3; msg = kMsgDataCheck; }
-            } else if (format == 2) {
-                const uint32_t crc = t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
-                const uint32_t isize = t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) | ((uint32_t)t[7] << 24);
-                if (crc != checks[2 * i + 1]) { status = (uint32_t)-3; msg = kMsgDataCheck; }
-                else if (isize != out_len) { status = (uint32_t)-3; msg = kMsgLengthCheck; }
-            }
-            used = (uint32_t)(at + tail);
-        }
-    } else {
-        used += hdr;
-    }
-    results[4 * i] = out_len;
-    results[4 * i + 1] = used;
-    results[4 * i + 2] = status;
-    results[4 * i + 3] = msg;
-}
-
-// ---- the same with a shared preset dictionary (raw and zlib) --------------------------------------------------------------
-__global__ __launch_bounds__(256)
-void frame_compress_dict_kernel(const FrameJob *__restrict__ jobs, uint32_t njobs, int format, uint32_t dictid,
-                                const uint32_t *__restrict__ quick, uint32_t *__restrict__ results) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= njobs) return;
-    const uint32_t clen = quick[2 * i], adler = quick[2 * i + 1];
-    results[2 * i + 1] = adler;                          // of the plaintext alone: the dictionary is in no check value
-    if (format == 0) {
-        results[2 * i] = clen;
-        return;
-    }
-    uint8_t *out = jobs[i].out;
-    dict_put_header(out, dictid);
-    uint8_t *t = out + kDictWrapHead + clen;
-    for (uint32_t k = 0; k < 4u; ++k) t[k] = dict_trailer_byte(k, adler);
-    results[2 * i] = kDictWrapHead + clen + 4u;
-}
-
-// format 0: every job decodes with the W bytes of the window as history.  format 1: dict_parse_header's verdict per member
-__global__ __launch_bounds__(256)
-void parse_header_dict_kernel(const InflateJobDev *__restrict__ given, uint32_t njobs, int format, uint32_t dictid, uint32_t W,
-                              InflateJobDev *__restrict__ patched, uint32_t *__restrict__ head /* 2 per job: header bytes, verdict */) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= njobs) return;
-    const InflateJobDev j = given[i];
-    DictHeader h = {0u, kMsgNone, 1u};
-    if (format == 1) h = dict_parse_header(j.in, j.in_len, dictid);
     InflateJobDev p = j;
     p.dict_len = h.history ? W : 0u;
     if (h.msg != kMsgNone) {                             // nothing to decode: an empty job costs the inflater nothing
@@ -239,9 +104,22 @@ void parse_header_dict_kernel(const InflateJobDev *__restrict__ given, uint32_t 
     head[2 * i + 1] = h.msg;
 }
 
+// the checksum descriptors of the inflated streams, as checksum.hip's host code builds them -- but from lengths that
+// only exist on the device
 __global__ __launch_bounds__(256)
-void verify_trailer_dict_kernel(const InflateJobDev *__restrict__ given, const uint32_t *__restrict__ head,
-                                const uint32_t *__restrict__ checks, uint32_t njobs, int format, uint32_t *__restrict__ results) {
+void fill_check_args_kernel(const InflateJobDev *__restrict__ jobs, const uint32_t *__restrict__ inflated, uint32_t njobs,
+                            const DeviceTables *__restrict__ tabs, int do_adler, int do_crc, StreamArgs *__restrict__ sa,
+                            FinalArgs *__restrict__ fa) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= njobs) return;
+    const uint64_t len = (int32_t)inflated[4 * i + 2] == 1 ? inflated[4 * i] : 0u;
+    fill_check_descriptor(jobs[i].out, len, tabs, do_adler, do_crc, sa + i, fa + i);
+}
+
+// (kDictMismatch is a verdict of dict_parse_header alone: without a dictionary no head row carries it)
+__global__ __launch_bounds__(256)
+void verify_trailer_kernel(const InflateJobDev *__restrict__ given, const uint32_t *__restrict__ head,
+                           const uint32_t *__restrict__ checks, uint32_t njobs, int format, uint32_t *__restrict__ results) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= njobs) return;
     uint32_t out_len = results[4 * i], used = results[4 * i + 1], status = results[4 * i + 2], msg = results[4 * i + 3];
@@ -257,18 +135,16 @@ void verify_trailer_dict_kernel(const InflateJobDev *__restrict__ given, const u
         msg = hmsg;
         status = hmsg == kMsgStarved ? (uint32_t)-5 : (uint32_t)-3;
     } else if ((int32_t)status == 1) {
-        const uint32_t tail = wrap_tail(format);
+        const uint32_t tail = wrapper_tail_bytes(format);
         const uint64_t at = (uint64_t)hdr + used;
         if (at + tail > given[i].in_len) {               // the stream ends before its trailer
             status = (uint32_t)-5;
             msg = kMsgStarved;
             used = (uint32_t)given[i].in_len;
         } else {
-            if (format == 1) {
-                const uint8_t *t = given[i].in + at;
-                const uint32_t stored = ((uint32_t)t[0] << 24) | ((uint32_t)t[1] << 16) | ((uint32_t)t[2] << 8) | t[3];
-                if (stored != checks[2 * i]) { status = (uint32_t)-3; msg = kMsgDataCheck; }
-            }
+            const uint32_t adler = format == 1 ? checks[2 * i] : 0u, crc = format == 2 ? checks[2 * i + 1] : 0u;
+            const uint32_t verdict = wrapper_trailer_verdict(format, given[i].in + at, adler, crc, out_len);
+            if (verdict != kWrapNone) { status = (uint32_t)-3; msg = wrapper_inflate_msg(verdict); }
             used = (uint32_t)(at + tail);
         }
     } else {
@@ -280,28 +156,18 @@ void verify_trailer_dict_kernel(const InflateJobDev *__restrict__ given, const u
     results[4 * i + 3] = msg;
 }
 
-}  // namespace zr
-
-using namespace zr;
-
-extern "C" {
-
-size_t zng_rocm_compress_streams_bound(size_t source_len, int format) {
-    return zng_rocm_deflate_quick_bound(source_len) + (format ? kWrapHead + wrap_tail(format) + 4 : 0);
+// ---- the host bodies: one for the two compress calls, one for the two uncompress calls; dict = null: the plain call ---------
+static size_t frame_bound(size_t source_len, int format, bool has_dict) {
+    const uint32_t head = has_dict ? kDictWrapHead : kWrapHead;
+    return zng_rocm_deflate_quick_bound(source_len) + (format ? head + wrapper_tail_bytes(format) + 4 : 0);
 }
 
-int zng_rocm_compress_streams_dev(int format, const zng_rocm_stream_job *jobs, size_t njobs, uint32_t *d_results, void *stream) {
-    if (!ctx()) {
-        set_error("zng_rocm_init() has not succeeded");
-        return ZNG_ROCM_ENODEV;
-    }
-    if (!njobs) return ZNG_ROCM_OK;
-    if (!jobs || !d_results || format < 0 || format > 2 || njobs > 0x7fffffffull) return ZNG_ROCM_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
+static int compress_streams_body(int format, const zng_rocm_dict *dict, const zng_rocm_stream_job *jobs, size_t njobs,
+                                 uint32_t *d_results, hipStream_t st) {
     DeviceGuard dev;
     Workspace *ws = workspace_for(st);
     if (!ws) return ZNG_ROCM_ENOMEM;
-    const uint32_t head = format ? kWrapHead : 0u, tail = wrap_tail(format);
+    const uint32_t head = format ? (dict ? kDictWrapHead : kWrapHead) : 0u, tail = wrapper_tail_bytes(format);
     uint32_t *d_quick = nullptr, *d_checks = nullptr;
     FrameJob *d_fj = nullptr, *h_fj = nullptr;
     std::vector<zng_rocm_stream_job> inner(njobs);
@@ -315,10 +181,15 @@ int zng_rocm_compress_streams_dev(int format, const zng_rocm_stream_job *jobs, s
         if (int rc = scratch_reserve(ws, kScrFrameJobsHost, njobs * sizeof(FrameJob), true, (void **)&h_fj)) return rc;
         for (size_t i = 0; i < njobs; ++i) {
             const zng_rocm_stream_job &j = jobs[i];
-            if (!j.out || ((uintptr_t)j.out & 3) || j.out_cap < zng_rocm_compress_streams_bound(j.in_len, format) ||
-                (format && (j.dict_len || j.flags))) {
-                set_error("job %zu: out must be 4-byte aligned with out_cap >= zng_rocm_compress_streams_bound(); a wrapped "
-                          "stream takes neither a dictionary nor block flags", i);
+            const bool fits = j.out && !((uintptr_t)j.out & 3) && j.out_cap >= frame_bound(j.in_len, format, dict != nullptr);
+            const bool taken = dict ? (!j.in_len || j.in) && !j.dict_len && !(format && j.flags) &&
+                                          !(j.flags & ~(uint32_t)(ZNG_ROCM_BLOCK_NOT_FINAL | ZNG_ROCM_BLOCK_SYNC_FLUSH))
+                                    : !(format && (j.dict_len || j.flags));
+            if (!fits || !taken) {
+                set_error(dict ? "job %zu: out must be 4-byte aligned with out_cap >= zng_rocm_compress_streams_dict_bound(); the job's "
+                                 "dict_len must be 0 (the history is the dictionary object's) and a zlib stream takes no block flags"
+                               : "job %zu: out must be 4-byte aligned with out_cap >= zng_rocm_compress_streams_bound(); a wrapped "
+                                 "stream takes neither a dictionary nor block flags", i);
                 return ZNG_ROCM_EINVAL;
             }
             inner[i] = j;
@@ -330,26 +201,21 @@ int zng_rocm_compress_streams_dev(int format, const zng_rocm_stream_job *jobs, s
         ZR_HIP(hipMemcpyAsync(d_fj, h_fj, njobs * sizeof(FrameJob), hipMemcpyHostToDevice, st));
         if (int rc = host_tables_release(ws, st)) return rc;
     }
-    // the two passes take the stream's workspace themselves
-    if (int rc = zng_rocm_deflate_quick_dev(inner.data(), njobs, d_quick, st)) return rc;
+    // the passes take the stream's workspace themselves
+    if (int rc = dict ? launch_deflate_quick_dict(inner.data(), njobs, d_quick, dict, st)
+                      : zng_rocm_deflate_quick_dev(inner.data(), njobs, d_quick, st))
+        return rc;
     if (format == 2)
         if (int rc = zng_rocm_checksums_dev(2, cj.data(), njobs, d_checks, st)) return rc;
     hipLaunchKernelGGL(frame_compress_kernel, dim3((unsigned)((njobs + 255) / 256)), dim3(256), 0, st, d_fj, (uint32_t)njobs,
-                       format, d_quick, d_checks, d_results);
+                       format, dict ? dict->id : 0u, dict ? 1 : 0, d_quick, d_checks, d_results);
     ZR_HIP(hipGetLastError());
     return ZNG_ROCM_OK;
 }
 
-int zng_rocm_uncompress_streams_dev(int format, const zng_rocm_inflate_dev_job *jobs, size_t njobs, uint32_t *d_results,
-                                    void *stream) {
+static int uncompress_streams_body(int format, const zng_rocm_dict *dict, const zng_rocm_inflate_dev_job *jobs, size_t njobs,
+                                   uint32_t *d_results, hipStream_t st) {
     Context *c = ctx();
-    if (!c) {
-        set_error("zng_rocm_init() has not succeeded");
-        return ZNG_ROCM_ENODEV;
-    }
-    if (!njobs) return ZNG_ROCM_OK;
-    if (!jobs || !d_results || format < 0 || format > 2 || njobs > 0x7fffffffull) return ZNG_ROCM_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
     DeviceGuard dev;
     Workspace *ws = workspace_for(st);
     if (!ws) return ZNG_ROCM_ENOMEM;
@@ -370,8 +236,10 @@ int zng_rocm_uncompress_streams_dev(int format, const zng_rocm_inflate_dev_job *
         const zng_rocm_inflate_dev_job &j = jobs[i];
         if ((j.in_len && !j.in) || (j.out_cap && !j.out) || j.in_len > 0x7fffffffull || j.out_cap > 0x7fffffffull ||
             j.dict_len || j.flags) {
-            set_error("job %zu: null buffer, a stream or output of 2 GiB and more, or dict_len / flags (raw streams only: "
-                      "zng_rocm_inflate_streams_dev)", i);
+            set_error(dict ? "job %zu: null buffer, a stream or output of 2 GiB and more, or dict_len / flags (the history is the "
+                             "dictionary object's)"
+                           : "job %zu: null buffer, a stream or output of 2 GiB and more, or dict_len / flags (raw streams only: "
+                             "zng_rocm_inflate_streams_dev)", i);
             return ZNG_ROCM_EINVAL;
         }
         h_given[i] = InflateJobDev{(const uint8_t *)j.in, (uint8_t *)j.out, j.in_len, j.out_cap, 0u, 0u};
@@ -379,9 +247,12 @@ int zng_rocm_uncompress_streams_dev(int format, const zng_rocm_inflate_dev_job *
     ZR_HIP(hipMemcpyAsync(d_given, h_given, njobs * sizeof(InflateJobDev), hipMemcpyHostToDevice, st));
     if (int rc = host_tables_release(ws, st)) return rc;
     const dim3 grid((unsigned)((njobs + 255) / 256)), block(256);
-    hipLaunchKernelGGL(parse_header_kernel, grid, block, 0, st, d_given, (uint32_t)njobs, format, c->tables, d_patched, d_head);
+    hipLaunchKernelGGL(parse_header_kernel, grid, block, 0, st, d_given, (uint32_t)njobs, format, dict ? dict->id : 0u,
+                       dict ? dict->window : 0u, dict ? 1 : 0, c->tables, d_patched, d_head);
     ZR_HIP(hipGetLastError());
-    if (int rc = launch_inflate_streams_device(d_patched, njobs, d_results, st)) return rc;
+    if (int rc = dict ? launch_inflate_streams_dict_device(d_patched, njobs, d_results, dict->d_window + dict->window, st)
+                      : launch_inflate_streams_device(d_patched, njobs, d_results, st))
+        return rc;
     if (format) {
         StreamArgs *d_sa = reinterpret_cast<StreamArgs *>(d_msg);
         FinalArgs *d_fa = reinterpret_cast<FinalArgs *>(d_msg + njobs * sizeof(StreamArgs));
@@ -396,9 +267,38 @@ int zng_rocm_uncompress_streams_dev(int format, const zng_rocm_inflate_dev_job *
     return ZNG_ROCM_OK;
 }
 
+}  // namespace zr
+
+using namespace zr;
+
+extern "C" {
+
+size_t zng_rocm_compress_streams_bound(size_t source_len, int format) { return frame_bound(source_len, format, false); }
+
+int zng_rocm_compress_streams_dev(int format, const zng_rocm_stream_job *jobs, size_t njobs, uint32_t *d_results, void *stream) {
+    if (!ctx()) {
+        set_error("zng_rocm_init() has not succeeded");
+        return ZNG_ROCM_ENODEV;
+    }
+    if (!njobs) return ZNG_ROCM_OK;
+    if (!jobs || !d_results || format < 0 || format > 2 || njobs > 0x7fffffffull) return ZNG_ROCM_EINVAL;
+    return compress_streams_body(format, nullptr, jobs, njobs, d_results, (hipStream_t)stream);
+}
+
+int zng_rocm_uncompress_streams_dev(int format, const zng_rocm_inflate_dev_job *jobs, size_t njobs, uint32_t *d_results,
+                                    void *stream) {
+    if (!ctx()) {
+        set_error("zng_rocm_init() has not succeeded");
+        return ZNG_ROCM_ENODEV;
+    }
+    if (!njobs) return ZNG_ROCM_OK;
+    if (!jobs || !d_results || format < 0 || format > 2 || njobs > 0x7fffffffull) return ZNG_ROCM_EINVAL;
+    return uncompress_streams_body(format, nullptr, jobs, njobs, d_results, (hipStream_t)stream);
+}
+
 size_t zng_rocm_compress_streams_dict_bound(size_t source_len, int format) {
     if (format != 0 && format != 1) return 0;
-    return zng_rocm_deflate_quick_bound(source_len) + (format ? kDictWrapHead + wrap_tail(format) + 4 : 0);
+    return frame_bound(source_len, format, true);
 }
 
 int zng_rocm_compress_streams_dict_dev(int format, const zng_rocm_dict *dict, const zng_rocm_stream_job *jobs, size_t njobs,
@@ -410,42 +310,7 @@ int zng_rocm_compress_streams_dict_dev(int format, const zng_rocm_dict *dict, co
     }
     if (!njobs) return ZNG_ROCM_OK;
     if (!jobs || !d_results || njobs > 0x7fffffffull) return ZNG_ROCM_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    DeviceGuard dev;
-    Workspace *ws = workspace_for(st);
-    if (!ws) return ZNG_ROCM_ENOMEM;
-    const uint32_t head = format ? kDictWrapHead : 0u, tail = wrap_tail(format);
-    uint32_t *d_quick = nullptr;
-    FrameJob *d_fj = nullptr, *h_fj = nullptr;
-    std::vector<zng_rocm_stream_job> inner(njobs);
-    {
-        std::lock_guard<std::mutex> use(ws->mu);
-        if (int rc = scratch_reserve(ws, kScrFrameWords, njobs * 4 * sizeof(uint32_t), false, (void **)&d_quick)) return rc;
-        if (int rc = scratch_reserve(ws, kScrFrameJobs, njobs * sizeof(FrameJob), false, (void **)&d_fj)) return rc;
-        if (int rc = host_tables_acquire(ws)) return rc;
-        if (int rc = scratch_reserve(ws, kScrFrameJobsHost, njobs * sizeof(FrameJob), true, (void **)&h_fj)) return rc;
-        for (size_t i = 0; i < njobs; ++i) {
-            const zng_rocm_stream_job &j = jobs[i];
-            if (!j.out || ((uintptr_t)j.out & 3) || (j.in_len && !j.in) ||
-                j.out_cap < zng_rocm_compress_streams_dict_bound(j.in_len, format) || j.dict_len || (format && j.flags) ||
-                (j.flags & ~(uint32_t)(ZNG_ROCM_BLOCK_NOT_FINAL | ZNG_ROCM_BLOCK_SYNC_FLUSH))) {
-                set_error("job %zu: out must be 4-byte aligned with out_cap >= zng_rocm_compress_streams_dict_bound(); the job's "
-                          "dict_len must be 0 (the history is the dictionary object's) and a zlib stream takes no block flags", i);
-                return ZNG_ROCM_EINVAL;
-            }
-            inner[i] = j;
-            inner[i].out = (uint8_t *)j.out + head;
-            inner[i].out_cap = j.out_cap - head - tail;
-            h_fj[i] = FrameJob{(uint8_t *)j.out, j.in_len};
-        }
-        ZR_HIP(hipMemcpyAsync(d_fj, h_fj, njobs * sizeof(FrameJob), hipMemcpyHostToDevice, st));
-        if (int rc = host_tables_release(ws, st)) return rc;
-    }
-    if (int rc = launch_deflate_quick_dict(inner.data(), njobs, d_quick, dict, st)) return rc;      // takes the workspace itself
-    hipLaunchKernelGGL(frame_compress_dict_kernel, dim3((unsigned)((njobs + 255) / 256)), dim3(256), 0, st, d_fj, (uint32_t)njobs,
-                       format, dict->id, d_quick, d_results);
-    ZR_HIP(hipGetLastError());
-    return ZNG_ROCM_OK;
+    return compress_streams_body(format, dict, jobs, njobs, d_results, (hipStream_t)stream);
 }
 
 int zng_rocm_uncompress_streams_dict_dev(int format, const zng_rocm_dict *dict, const zng_rocm_inflate_dev_job *jobs,
@@ -455,54 +320,9 @@ int zng_rocm_uncompress_streams_dict_dev(int format, const zng_rocm_dict *dict, 
         set_error("a dictionary object and format 0 (raw) or 1 (zlib): gzip has no preset dictionary");
         return ZNG_ROCM_EINVAL;
     }
-    Context *c = ctx();
     if (!njobs) return ZNG_ROCM_OK;
     if (!jobs || !d_results || njobs > 0x7fffffffull) return ZNG_ROCM_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    DeviceGuard dev;
-    Workspace *ws = workspace_for(st);
-    if (!ws) return ZNG_ROCM_ENOMEM;
-    std::lock_guard<std::mutex> use(ws->mu);
-    InflateJobDev *d_given = nullptr, *h_given = nullptr, *d_patched = nullptr;
-    uint32_t *d_words = nullptr;
-    uint8_t *d_msg = nullptr;
-    Partial *d_part = nullptr;
-    if (int rc = scratch_reserve(ws, kScrInflateDevJobs, 2 * njobs * sizeof(InflateJobDev), false, (void **)&d_given)) return rc;
-    d_patched = d_given + njobs;
-    if (int rc = scratch_reserve(ws, kScrFrameWords, njobs * 4 * sizeof(uint32_t), false, (void **)&d_words)) return rc;
-    uint32_t *d_head = d_words, *d_checks = d_words + 2 * njobs;
-    if (int rc = scratch_reserve(ws, kScrCheckMessages, njobs * (sizeof(StreamArgs) + sizeof(FinalArgs)), false, (void **)&d_msg)) return rc;
-    if (int rc = scratch_reserve(ws, kScrCheckPartials, njobs * sizeof(Partial), false, (void **)&d_part)) return rc;
-    if (int rc = host_tables_acquire(ws)) return rc;
-    if (int rc = scratch_reserve(ws, kScrInflateDevJobsHost, njobs * sizeof(InflateJobDev), true, (void **)&h_given)) return rc;
-    for (size_t i = 0; i < njobs; ++i) {
-        const zng_rocm_inflate_dev_job &j = jobs[i];
-        if ((j.in_len && !j.in) || (j.out_cap && !j.out) || j.in_len > 0x7fffffffull || j.out_cap > 0x7fffffffull ||
-            j.dict_len || j.flags) {
-            set_error("job %zu: null buffer, a stream or output of 2 GiB and more, or dict_len / flags (the history is the "
-                      "dictionary object's)", i);
-            return ZNG_ROCM_EINVAL;
-        }
-        h_given[i] = InflateJobDev{(const uint8_t *)j.in, (uint8_t *)j.out, j.in_len, j.out_cap, 0u, 0u};
-    }
-    ZR_HIP(hipMemcpyAsync(d_given, h_given, njobs * sizeof(InflateJobDev), hipMemcpyHostToDevice, st));
-    if (int rc = host_tables_release(ws, st)) return rc;
-    const dim3 grid((unsigned)((njobs + 255) / 256)), block(256);
-    hipLaunchKernelGGL(parse_header_dict_kernel, grid, block, 0, st, d_given, (uint32_t)njobs, format, dict->id, dict->window,
-                       d_patched, d_head);
-    ZR_HIP(hipGetLastError());
-    if (int rc = launch_inflate_streams_dict_device(d_patched, njobs, d_results, dict->d_window + dict->window, st)) return rc;
-    if (format) {
-        StreamArgs *d_sa = reinterpret_cast<StreamArgs *>(d_msg);
-        FinalArgs *d_fa = reinterpret_cast<FinalArgs *>(d_msg + njobs * sizeof(StreamArgs));
-        hipLaunchKernelGGL(fill_check_args_kernel, grid, block, 0, st, d_patched, d_results, (uint32_t)njobs, c->tables, 1, 0,
-                           d_sa, d_fa);
-        ZR_HIP(hipGetLastError());
-        if (int rc = launch_checksum_batch_device(true, false, d_sa, d_fa, d_part, njobs, d_checks, st)) return rc;
-    }
-    hipLaunchKernelGGL(verify_trailer_dict_kernel, grid, block, 0, st, d_given, d_head, d_checks, (uint32_t)njobs, format, d_results);
-    ZR_HIP(hipGetLastError());
-    return ZNG_ROCM_OK;
+    return uncompress_streams_body(format, dict, jobs, njobs, d_results, (hipStream_t)stream);
 }
 
 }  // extern "C"

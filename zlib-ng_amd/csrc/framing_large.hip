@@ -205,44 +205,27 @@ void large_fold_kernel(const uint32_t *__restrict__ sub2, const uint32_t *__rest
     }
 }
 
-// inflate.c:1105-1147: the check value (zlib most significant byte first, gzip least) and gzip's ISIZE
+// inflate.c:1105-1147: the check value and gzip's ISIZE (wrapper_trailer_verdict)
 __global__ __launch_bounds__(256)
 void large_trailer_kernel(const TrailJob *__restrict__ jobs, const uint32_t *__restrict__ checks2, uint32_t njobs, int format,
                           TrailRow *__restrict__ rows) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= njobs) return;
     const TrailJob j = jobs[i];
-    const uint32_t tail = format == 1 ? 4u : 8u;
+    const uint32_t tail = wrapper_tail_bytes(format);
     TrailRow r = {j.at + tail, 1, kWrapNone};
     if (j.at + tail > j.src_len) {                       // the member ends inside its trailer
         r.status = -5;
         r.in_used = j.src_len;
     } else {
-        const uint8_t *t = j.src + j.at;
-        if (format == 1) {
-            const uint32_t stored = ((uint32_t)t[0] << 24) | ((uint32_t)t[1] << 16) | ((uint32_t)t[2] << 8) | t[3];
-            if (stored != checks2[2 * i]) { r.status = -3; r.msg = kWrapDataCheck; }
-        } else {
-            const uint32_t crc = t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
-            const uint32_t isize = t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) | ((uint32_t)t[7] << 24);
-            if (crc != checks2[2 * i + 1]) { r.status = -3; r.msg = kWrapDataCheck; }
-            else if (isize != (uint32_t)j.out_len) { r.status = -3; r.msg = kWrapLengthCheck; }
-        }
+        const uint32_t adler = format == 1 ? checks2[2 * i] : 0u, crc = format == 2 ? checks2[2 * i + 1] : 0u;
+        r.msg = wrapper_trailer_verdict(format, j.src + j.at, adler, crc, j.out_len);
+        if (r.msg != kWrapNone) r.status = -3;
     }
     rows[i] = r;
 }
 
 namespace {
-
-// the member's bytes in host memory
-struct HostBytes {
-    const uint8_t *src;
-    uint32_t byte(uint64_t pos) const { return src[pos]; }
-    uint64_t find_zero(uint64_t from, uint64_t n) const {
-        const void *z = from < n ? memchr(src + from, 0, (size_t)(n - from)) : nullptr;
-        return z ? (uint64_t)((const uint8_t *)z - src) : n;
-    }
-};
 
 // CRC-32 of a gzip header on the host, without the device context (zng_rocm_wrapper_parse works before zng_rocm_init)
 uint32_t host_crc32(const uint8_t *p, size_t n) {

@@ -177,8 +177,8 @@ void members_link_kernel(const uint8_t *__restrict__ src, uint64_t src_len, cons
     const uint64_t end = r.next < n ? pos[r.next] : src_len;
     if (h.status == 0 && end >= p + h.header_len + 8) {  // inflate.c:1105-1147: CRC-32 and ISIZE, least significant byte first
         const uint8_t *t = src + end - 8;
-        r.crc = t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
-        r.isize = t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) | ((uint32_t)t[7] << 24);
+        r.crc = wrapper_le32(t);
+        r.isize = wrapper_le32(t + 4);
         r.flags |= kCandTrailer;
     }
     rows[i] = r;
@@ -251,7 +251,7 @@ int decode_alone(Call &c, uint32_t bgzf, int *status, uint64_t *out_len, size_t 
     if (c.nm < c.members_cap)
         if (int rc = peek(c, c.at + *in_used - 8, 4, t)) return rc;
     ++g_large;
-    c.add(c.at, *in_used, *out_len, t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24), bgzf);
+    c.add(c.at, *in_used, *out_len, wrapper_le32(t), bgzf);
     return ZNG_ROCM_OK;
 }
 

@@ -18,6 +18,7 @@
 
 #include <vector>
 
+#include "framing_parse.h"
 #include "gf2.h"
 
 namespace zr {
@@ -53,8 +54,7 @@ ZR_HD uint64_t member_header_look(uint64_t src_len, uint64_t p) {
 inline void scan_candidates(const uint8_t *src, uint64_t n, std::vector<uint64_t> &pos) {
     pos.clear();
     for (uint64_t p = 0; p + 4 <= n; ++p)
-        if (member_candidate(src[p] | ((uint32_t)src[p + 1] << 8) | ((uint32_t)src[p + 2] << 16) | ((uint32_t)src[p + 3] << 24)))
-            pos.push_back(p);
+        if (member_candidate(wrapper_le32(src + p))) pos.push_back(p);
 }
 
 // One row per candidate, as the link kernel writes it and the host reads it back.
