@@ -610,6 +610,9 @@ int    zng_rocm_compress_streams2_last_rounds(void);
  *   - builds the primed head table of the level-1 class: for every bucket the last position p with p + 4 <= W whose four
  *     bytes hash there, + 1 (the last 3 positions are left out, deflate.c:494-501) -- one atomic max per position, so the
  *     table is what entering the positions in order leaves, whatever the scheduling;
+ *   - builds the primed row tables of the rows engine (levels 1..9 of zng_rocm_compress_streams2_dict_dev below): what its
+ *     priming leaves behind the positions [0, T), T the largest multiple of 1024 with T + 3 <= W -- one workgroup, the
+ *     matcher's own ordered insert;
  *   - synchronises `stream` once, to bring the DICTID to the host.
  * The object is immutable afterwards and may be used from any thread and any HIP stream of the device it was made on.  After
  * zng_rocm_shutdown() every call with it returns ZNG_ROCM_ENODEV (also under a later zng_rocm_init()); zng_rocm_dict_destroy
@@ -644,6 +647,36 @@ int      zng_rocm_compress_streams_dict_dev(int format, const zng_rocm_dict *dic
                                             size_t njobs, uint32_t *d_results, void *stream);
 int      zng_rocm_uncompress_streams_dict_dev(int format, const zng_rocm_dict *dict, const zng_rocm_inflate_dev_job *jobs,
                                               size_t njobs, uint32_t *d_results, void *stream);
+
+/* The shared preset dictionary at EVERY level: zng_rocm_compress_streams2_dev / zng_rocm_compress_members_dev with the object's
+ * window as every stream's history.  They behave as those two calls in every respect -- rounds, asynchrony, result words, the
+ * offsets table, the does-not-fit rule, zng_rocm_compress_streams2_last_rounds -- except:
+ *   format    0 raw (deflateSetDictionary on a raw stream) or 1 zlib; 2 (gzip has no dictionary, deflate.c:467) or a NULL dict
+ *             is ZNG_ROCM_EINVAL with nothing launched
+ *   zlib      the header is the canonical 6 bytes: CMF FLG with FLEVEL as above, FDICT set and FCHECK making the pair a multiple
+ *             of 31 (deflate.c:868-888), then the DICTID, most significant byte first (:889-892) -- no padding, unlike the
+ *             16-byte wrapper of zng_rocm_compress_streams_dict_dev; the trailer is the Adler-32 of the plaintext alone.
+ *             zng_rocm_uncompress_streams_dict_dev and inflateSetDictionary read these members.
+ *   bound     zng_rocm_compress_streams2_dict_bound = zng_rocm_compress_streams2_bound, + 4 for format 1; 0 for a refused format
+ *   level     -1, 1..9 with strategy 0, 1 or 4 (Z_FIXED): the dictionary form of the rows matcher (Z_FIXED with the static-only
+ *             emitter behind it).  zng_rocm_dict_create_dev has built, once, the row tables the matcher's priming leaves behind
+ *             the whole 1 KiB batches inside the window; a stream's first segment loads them (about 88 KiB) and the window into
+ *             LDS instead of entering up to 32 batches of history, and every stream's bytes are EXACTLY those the plain call
+ *             writes for the same plaintext with the W window bytes copied in front of it and dict_len = W -- matches that
+ *             begin in the window and run on into the plaintext included.  Level 0 writes stored blocks behind the FDICT header
+ *             and reads no dictionary byte.
+ *   strategy  2 (Z_HUFFMAN_ONLY) and 3 (Z_RLE) are ZNG_ROCM_EINVAL here: their front end is another kernel, and at most one
+ *             byte of history is not worth a dictionary form
+ *   jobs      a job's own dict_len must be 0; flags (ZNG_ROCM_BLOCK_*) in format 0 only
+ * A dictionary made before a zng_rocm_shutdown() gives ZNG_ROCM_ENODEV, as in the dictionary calls above; argument refusals
+ * come first. */
+size_t zng_rocm_compress_streams2_dict_bound(size_t source_len, int format);
+int    zng_rocm_compress_streams2_dict_dev(int format, int level, int strategy, const zng_rocm_dict *dict,
+                                           const zng_rocm_stream_job *jobs, size_t njobs, size_t round_bytes,
+                                           uint32_t *d_results, void *stream);
+int    zng_rocm_compress_members_dict_dev(int format, int level, int strategy, const zng_rocm_dict *dict,
+                                          const zng_rocm_stream_job *jobs, size_t njobs, uint8_t *d_dst, size_t dst_cap,
+                                          size_t round_bytes, uint64_t *d_offsets, uint32_t *d_checks, void *stream);
 
 /* zlib (format 1) / gzip (format 2) members around the LARGE device inflaters: zng_rocm_inflate_large_streams_dev (the
  * batch) and zng_rocm_inflate_large_pieces_dev (one member of any length) for wrapped streams that already sit in device

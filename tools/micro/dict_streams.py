@@ -12,17 +12,23 @@ message is its own stream, so repeating a record changes nothing a stream does).
             b  zng_rocm_inflate_streams_dev over the streams of deflate c, the dictionary copied in front of EVERY output
             c  zng_rocm_uncompress_streams_dict_dev, format 0, over the same streams
 
+  level 6   a  zng_rocm_compress_streams2_dev, format 0, level 6: no dictionary
+            b  the same call with the dictionary copied in front of EVERY message and dict_len = W (the way before)
+            c  zng_rocm_compress_streams2_dict_dev, format 0, level 6: the dictionary object
+            (b and c write the same bytes: every result row is compared, and every 1024th stream)
+
 Every leg is warmed (one untimed call: it allocates the scratch), then the legs take turns until each has been timed for
 --window-s (1.0) seconds in total and at least --min-reps (5) times.  A timing is the device time between two events
 recorded around the call on its stream.  Per leg: median, min, max and quartiles in ms, spread = (p75 - p25) / median, GB/s of
 plaintext, and for deflate the compressed total and its ratio.  Before the timings every 1024th stream of deflate c is read
 back by CPython with zdict= and every output of inflate c is compared with the plaintext on the device.
 
---parent-lib FILE adds the `streams` workload of bench.py (4096 x 1 MiB of the six-class mix, zng_rocm_deflate_quick_dev)
-through the library at FILE and through this tree's, alternating in the same process: the existing kernel is meant to be the
-same code in both, and this is where that is looked at.
+--parent-lib FILE adds the `streams` workload of bench.py (4096 x 1 MiB of the six-class mix, zng_rocm_deflate_quick_dev) and
+its `deflate_lvl6` workload (one 256 MiB stream, zng_rocm_deflate_dev at level 6) through the library at FILE and through this
+tree's, alternating in the same process: the existing kernels are meant to be the same code in both, and this is where that
+is looked at.
 
---only LEG (deflate_a .. inflate_c, or all) runs that leg --min-reps + 1 times behind the checks and writes no report: the
+--only LEG (deflate_a .. level6_c, level6 for the three level-6 legs, or all) runs that leg --min-reps + 1 times behind the checks and writes no report: the
 form a profiler is pointed at.
 
     python tools/micro/dict_streams.py [--messages 65536] [--window-s 1.0] [--parent-lib FILE] [--only LEG] [--out FILE.json]
@@ -42,7 +48,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-LEGS = ("deflate_a", "deflate_b", "deflate_c", "inflate_a", "inflate_b", "inflate_c")
+LEGS = ("deflate_a", "deflate_b", "deflate_c", "inflate_a", "inflate_b", "inflate_c", "level6_a", "level6_b", "level6_c")
 
 
 def records(count, lo, hi, seed):
@@ -102,8 +108,8 @@ def main():
     ap.add_argument("--window-s", type=float, default=1.0)
     ap.add_argument("--min-reps", type=int, default=5)
     ap.add_argument("--parent-lib", default=None)
-    ap.add_argument("--only", default=None, choices=LEGS + ("all",))
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dict_streams_rate_v1.json"))
+    ap.add_argument("--only", default=None, choices=LEGS + ("level6", "all"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dict_streams_rate_v2.json"))
     a = ap.parse_args()
     import torch
     zr = importlib.import_module("zlib-ng_amd")
@@ -180,9 +186,12 @@ def main():
 
         legs = {"deflate_a": lambda: wa.run(st), "deflate_b": lambda: wb.run(st), "deflate_c": lambda: wc.run_dict(dic, st),
                 "inflate_a": lambda: ia.run_wrapped(0, st), "inflate_b": lambda: ib.run(st), "inflate_c": lambda: ic.run_dict(0, dic, st)}
+        l6_legs, l6_sizes = level6_legs(torch, st, dfl, lib, dic, D, pool, plain, front, in_off, front_off, lens)
+        legs.update(l6_legs)
         if a.only:
+            pick = LEGS if a.only == "all" else tuple(l6_legs) if a.only == "level6" else (a.only,)
             for _ in range(a.min_reps + 1):
-                for k in (LEGS if a.only == "all" else (a.only,)):
+                for k in pick:
                     legs[k]()
             st.synchronize()
             return 0
@@ -190,13 +199,19 @@ def main():
                "distinct_messages": len(pool), "message_bytes": [min(lens), max(lens)], "plaintext_bytes": total, "dictionary_bytes": W,
                "figure": "device time between two events around the call; median over the reps of a window of at least "
                          "%.1f s per leg, legs alternating; spread = (p75 - p25) / median; GB/s of plaintext" % a.window_s}
-        for side in ("deflate", "inflate"):
+        for side in ("deflate", "inflate", "level6"):
             per = alternate(torch, st, {k: v for k, v in legs.items() if k.startswith(side)}, a.window_s, a.min_reps)
             for k, v in per.items():
                 out[k] = summary(v, total)
         for k, c in (("deflate_a", ca), ("deflate_b", cb), ("deflate_c", cc)):
             out[k].update(compressed_bytes=sum(c), ratio=round(total / sum(c), 4))
         out["dictionary_gain"] = round(1.0 - sum(cc) / sum(ca), 4)
+        for k, c in l6_sizes.items():
+            out[k].update(compressed_bytes=c, ratio=round(total / c, 4))
+        out["level6_dictionary_gain"] = round(1.0 - l6_sizes["level6_c"] / l6_sizes["level6_a"], 4)
+        b, c = out["level6_b"], out["level6_c"]
+        out["level6_c_over_b"] = round(b["ms"] / c["ms"], 4)
+        out["level6_c_faster_than_b"] = bool(c["p75_ms"] < b["p25_ms"])
         b, c = out["deflate_b"], out["deflate_c"]
         out["deflate_c_within_b_spread"] = bool(c["ms"] <= b["ms"] + (b["p75_ms"] - b["p25_ms"]))
         b, c = out["inflate_b"], out["inflate_c"]
@@ -205,8 +220,9 @@ def main():
             print(k, json.dumps(out[k]), flush=True)
 
         if a.parent_lib:
-            out["streams_parent_vs_new"] = parent_leg(a, torch, st, sp, lib)
+            out["streams_parent_vs_new"], out["deflate_lvl6_parent_vs_new"] = parent_leg(a, torch, st, sp, lib)
             print("streams", json.dumps(out["streams_parent_vs_new"]), flush=True)
+            print("deflate_lvl6", json.dumps(out["deflate_lvl6_parent_vs_new"]), flush=True)
     dic.close()
     with open(a.out, "w") as f:
         json.dump(out, f, indent=1)
@@ -214,8 +230,44 @@ def main():
     return 0
 
 
+def level6_legs(torch, st, dfl, lib, dic, D, pool, plain, front, in_off, front_off, lens):
+    """the three level-6 legs over one shared set of output slots (the legs run one behind the other on one stream), checked
+    once: the object's streams are read by CPython with zdict=, and the in-front call writes the same rows and bytes"""
+    n, W = len(lens), len(D)
+    out_off, pos = [], 0
+    for v in lens:
+        out_off.append(pos)
+        pos += (lib.zng_rocm_compress_streams2_bound(v, 0) + 15) & ~15
+    dst = torch.zeros(pos + 16, dtype=torch.uint8, device="cuda")
+
+    def table(src, offs, dict_len):
+        jobs = (dfl.StreamJob * n)()
+        for i in range(n):
+            jobs[i].in_ptr, jobs[i].in_len, jobs[i].dict_len = src.data_ptr() + offs[i], lens[i], dict_len
+            jobs[i].out_ptr, jobs[i].out_cap = dst.data_ptr() + out_off[i], lib.zng_rocm_compress_streams2_bound(lens[i], 0)
+        return jobs
+    ja, jb, jc = table(plain, in_off, 0), table(front, front_off, W), table(plain, in_off, 0)
+    res = {k: torch.zeros((n, 2), dtype=torch.int32, device="cuda") for k in "abc"}
+
+    def ok(rc):
+        assert rc == 0, rc
+    legs = {"level6_a": lambda: ok(dfl.compress_streams2_dev(ja, n, res["a"], 0, 6, 0, 0, st)),
+            "level6_b": lambda: ok(dfl.compress_streams2_dev(jb, n, res["b"], 0, 6, 0, 0, st)),
+            "level6_c": lambda: ok(dfl.compress_streams2_dict_dev(dic, jc, n, res["c"], 0, 6, 0, 0, st))}
+    samples = {}
+    for k in ("c", "b", "a"):
+        legs["level6_" + k]()
+        st.synchronize()
+        size = res[k].cpu().numpy()[:, 0]
+        samples[k] = [dst[out_off[i]:out_off[i] + int(size[i])].cpu().numpy().tobytes() for i in range(0, n, 1024)]
+    for i, c in zip(range(0, n, 1024), samples["c"]):
+        assert zlib.decompressobj(-15, zdict=D).decompress(c) == pool[i % len(pool)], i
+    assert torch.equal(res["b"], res["c"]) and samples["b"] == samples["c"]
+    return legs, {"level6_" + k: int(res[k].cpu().numpy()[:, 0].astype(np.int64).sum()) for k in "abc"}
+
+
 def parent_leg(a, torch, st, sp, lib):
-    """bench.py's `streams` workload through two builds of the library in one process"""
+    """bench.py's `streams` and `deflate_lvl6` workloads through two builds of the library in one process"""
     import synth
     dfl = importlib.import_module("zlib-ng_amd.deflate")
     old = C.CDLL(os.path.abspath(a.parent_lib))
@@ -243,8 +295,29 @@ def parent_leg(a, torch, st, sp, lib):
     row = {k: summary(v, count * each) for k, v in per.items()}
     p = row["parent"]
     row["new_within_parent_spread"] = bool(p["min_ms"] <= row["new"]["ms"] <= p["max_ms"])
+    del batch, src, res_old
+
+    # deflate_lvl6: one 256 MiB stream, level 6, the synchronous call (its host synchronisation inside the timing)
+    nbytes = 256 << 20
+    one = torch.from_numpy(synth.silesia_like(nbytes, seed=0x5EED0003)).cuda()
+    cap = lib.zng_rocm_deflate_bound(nbytes)
+    outs = {"parent": torch.zeros(cap, dtype=torch.uint8, device="cuda"), "new": torch.zeros(cap, dtype=torch.uint8, device="cuda")}
+    lens = {"parent": C.c_size_t(0), "new": C.c_size_t(0)}
+    for h in (old, lib):
+        h.zng_rocm_deflate_dev.restype = C.c_int
+        h.zng_rocm_deflate_dev.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
+
+    def lvl6(h, k):
+        return lambda: h.zng_rocm_deflate_dev(6, C.c_void_p(one.data_ptr()), nbytes, C.c_void_p(outs[k].data_ptr()), cap, C.byref(lens[k]), sp)
+    per = alternate(torch, st, {"parent": lvl6(old, "parent"), "new": lvl6(lib, "new")}, a.window_s, a.min_reps)
+    st.synchronize()
+    assert lens["parent"].value == lens["new"].value and torch.equal(outs["parent"][:lens["new"].value], outs["new"][:lens["new"].value])
+    row6 = {k: summary(v, nbytes) for k, v in per.items()}
+    p = row6["parent"]
+    row6["compressed_bytes"] = int(lens["new"].value)
+    row6["new_within_parent_spread"] = bool(p["min_ms"] <= row6["new"]["ms"] <= p["max_ms"])
     old.zng_rocm_shutdown()
-    return row
+    return row, row6
 
 
 if __name__ == "__main__":

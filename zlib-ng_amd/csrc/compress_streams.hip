@@ -19,6 +19,10 @@
 //
 // Every store of the frame kernel is bounded by the member's capacity: out_cap, or dst_cap for the file, which is cut at the
 // buffer's end while the scan goes on counting, so d_offsets[njobs] is the size the file needs.
+//
+// zng_rocm_compress_streams2_dict_dev / zng_rocm_compress_members_dict_dev are the same calls with one shared preset dictionary
+// (dict.hip) as every stream's history: the rows engine runs its dictionary form (lz_rows_dict_kernel), and the zlib member
+// begins with the 6-byte FDICT header -- CMF FLG, the DICTID -- instead of the 2-byte one.
 #include "checksum_args.h"
 #include "context.h"
 
@@ -26,6 +30,7 @@
 #include "compress_streams_plan.h"
 #include "deflate_blocks.h"
 #include "deflate_dev.h"
+#include "dict_dev.h"
 
 #include <mutex>
 
@@ -51,7 +56,14 @@ struct CsRound {                        // the arguments the kernels of a round 
     unsigned long long *offsets;        // members: d_offsets
     uint32_t      *checks;              // members: d_checks or null
     uint32_t      *results;             // streams2: d_results
+    uint32_t       dict, dictid;        // 1: the calls with a shared preset dictionary, whose zlib header carries FDICT and this DICTID
 };
+
+// bytes of the member's header, and byte k of it
+__device__ __forceinline__ uint32_t cs_round_head(const CsRound &r) { return r.dict ? cs_dict_head_bytes(r.format) : cs_head_bytes(r.format); }
+__device__ __forceinline__ uint8_t cs_round_header_byte(const CsRound &r, uint32_t k) {
+    return r.dict ? cs_dict_header_byte(r.level, r.strategy, r.dictid, k) : cs_header_byte(r.format, r.level, r.strategy, k);
+}
 
 __device__ __forceinline__ uint32_t cs_check_of(const CsRound &r, uint32_t i) { return r.check2[2 * i + (r.format == 2 ? 1 : 0)]; }
 
@@ -87,7 +99,7 @@ void cs_scan_kernel(CsRound r, unsigned long long *__restrict__ file_off) {
     __shared__ unsigned long long wave_sum[16];
     __shared__ unsigned long long carry;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const uint32_t wrap = cs_head_bytes(r.format) + cs_tail_bytes(r.format);
+    const uint32_t wrap = cs_round_head(r) + cs_tail_bytes(r.format);
     if (!r.members) {                                    // every member in its own buffer: nothing to place
         for (uint32_t i = (uint32_t)t; i < r.nj; i += 1024u) {
             const unsigned long long g = r.first + i;
@@ -136,7 +148,7 @@ __global__ __launch_bounds__(256)
 void cs_frame_kernel(CsRound r, const BlkJob *__restrict__ blk, const uint32_t *__restrict__ seg_len,
                      const unsigned long long *__restrict__ in_stream, unsigned long long nblk) {
     const int t = threadIdx.x;
-    const uint32_t head = cs_head_bytes(r.format), tail = cs_tail_bytes(r.format);
+    const uint32_t head = cs_round_head(r), tail = cs_tail_bytes(r.format);
     const unsigned long long items = (unsigned long long)r.nj + nblk;
     for (unsigned long long w = blockIdx.x; w < items; w += gridDim.x) {
         if (w < r.nj) {
@@ -145,7 +157,7 @@ void cs_frame_kernel(CsRound r, const BlkJob *__restrict__ blk, const uint32_t *
             const CsJob j = r.jobs[g];
             const CsPlace p = cs_place(r, g, j);
             const unsigned long long body = cs_stream_bytes(r, i, j);
-            if (t < (int)head) cs_put(p, p.at + t, cs_header_byte(r.format, r.level, r.strategy, (uint32_t)t));
+            if (t < (int)head) cs_put(p, p.at + t, cs_round_header_byte(r, (uint32_t)t));
             else if (t >= 32 && t < 32 + (int)tail)
                 cs_put(p, p.at + head + body + (t - 32), cs_trailer_byte(r.format, (uint32_t)t - 32u, cs_check_of(r, i), j.in_len));
             else if (r.level == 0 && cs_stored_marker(j.flags) && t >= 64 && t < 64 + (int)kCsStoredHead)
@@ -180,19 +192,30 @@ void cs_frame_kernel(CsRound r, const BlkJob *__restrict__ blk, const uint32_t *
 
 static thread_local int t_cs_rounds = 0;
 
+// with_dict: the calls with a shared preset dictionary (`dict` is every stream's history), else dict is null
 static int compress_streams_run(const char *who, bool members, int format, int level, int strategy, const zng_rocm_stream_job *jobs,
                                 size_t njobs, uint8_t *d_dst, size_t dst_cap, size_t round_bytes, uint64_t *d_offsets,
-                                uint32_t *d_checks, uint32_t *d_results, void *stream) {
+                                uint32_t *d_checks, uint32_t *d_results, void *stream, bool with_dict = false,
+                                const zng_rocm_dict *dict = nullptr) {
     t_cs_rounds = 0;
-    int rc = cs_call_check(format, level, strategy, jobs, njobs, members ? (const void *)d_offsets : (const void *)d_results);
+    const void *res = members ? (const void *)d_offsets : (const void *)d_results;
+    int rc = with_dict ? cs_dict_call_check(format, level, strategy, dict, jobs, njobs, res)
+                       : cs_call_check(format, level, strategy, jobs, njobs, res);
     if (!rc && members) rc = cs_file_check(d_dst, dst_cap);
     if (rc) {
-        set_error("%s: format outside 0..2, level outside -1..9, strategy outside 0..4, or a null pointer", who);
+        if (with_dict)
+            set_error("%s: no dictionary object, format outside 0..1 (gzip has no preset dictionary), level outside -1..9, strategy "
+                      "other than 0, 1 or 4, or a null pointer", who);
+        else set_error("%s: format outside 0..2, level outside -1..9, strategy outside 0..4, or a null pointer", who);
         return rc;
     }
     uint64_t bad = 0;
-    if ((rc = cs_jobs_check(format, jobs, njobs, !members, &bad))) {
-        if (rc == kCsBufError) set_error("%s: job %llu: out_cap below zng_rocm_compress_streams2_bound()", who, (unsigned long long)bad);
+    if ((rc = with_dict ? cs_dict_jobs_check(format, jobs, njobs, !members, &bad) : cs_jobs_check(format, jobs, njobs, !members, &bad))) {
+        if (rc == kCsBufError)
+            set_error("%s: job %llu: out_cap below zng_rocm_compress_streams2%s_bound()", who, (unsigned long long)bad, with_dict ? "_dict" : "");
+        else if (with_dict)
+            set_error("%s: job %llu: null buffer, a dict_len of its own, unknown flags, flags in a wrapped format, or a bound that "
+                      "does not fit 32 bits", who, (unsigned long long)bad);
         else
             set_error("%s: job %llu: null buffer, dict_len above 32768, unknown flags, dict_len or flags in a wrapped format, or a "
                       "bound that does not fit 32 bits", who, (unsigned long long)bad);
@@ -203,6 +226,8 @@ static int compress_streams_run(const char *who, bool members, int format, int l
         set_error("zng_rocm_init() has not succeeded");
         return ZNG_ROCM_ENODEV;
     }
+    if (with_dict)
+        if ((rc = dict_usable(dict))) return rc;
     level = cs_level(level);
     size_t total_in = 0, np_max = 0;
     for (size_t first = 0; first < njobs;) {
@@ -273,13 +298,16 @@ static int compress_streams_run(const char *who, bool members, int format, int l
         r.offsets = reinterpret_cast<unsigned long long *>(d_offsets);
         r.checks = d_checks;
         r.results = d_results;
+        r.dict = with_dict ? 1u : 0u;
+        r.dictid = with_dict ? dict->id : 0u;
         hipLaunchKernelGGL(cs_check_args_kernel, dim3((r.nj + 255u) / 256u), dim3(256), 0, st, r, ctx()->tables, d_sa, d_fa);
         ZR_HIP(hipGetLastError());
         if ((rc = launch_checksum_batch_device(format != 2, format == 2, d_sa, d_fa, d_part, r.nj, d_chk, st))) return rc;
         RowsBlocks blocks = {nullptr, nullptr, nullptr, nullptr, 0};
         unsigned long long nblk = h_jobs[last - 1].blk0 + cs_stored_blocks(jobs[last - 1].in_len) - h_jobs[first].blk0;
         if (level) {
-            if ((rc = deflate_rows_enqueue_streams(level, strategy, jobs + first, r.nj, seg_bytes, ws, st, &blocks))) {
+            if ((rc = with_dict ? deflate_rows_enqueue_streams_dict(level, strategy, dict, jobs + first, r.nj, seg_bytes, ws, st, &blocks)
+                                : deflate_rows_enqueue_streams(level, strategy, jobs + first, r.nj, seg_bytes, ws, st, &blocks))) {
                 (void)host_tables_release(ws, st);
                 return rc;
             }
@@ -318,6 +346,21 @@ int zng_rocm_compress_members_dev(int format, int level, int strategy, const zng
                                   size_t dst_cap, size_t round_bytes, uint64_t *d_offsets, uint32_t *d_checks, void *stream) {
     return compress_streams_run("zng_rocm_compress_members_dev", true, format, level, strategy, jobs, njobs, d_dst, dst_cap,
                                 round_bytes, d_offsets, d_checks, nullptr, stream);
+}
+
+size_t zng_rocm_compress_streams2_dict_bound(size_t source_len, int format) { return (size_t)cs_dict_bound(source_len, format); }
+
+int zng_rocm_compress_streams2_dict_dev(int format, int level, int strategy, const zng_rocm_dict *dict, const zng_rocm_stream_job *jobs,
+                                        size_t njobs, size_t round_bytes, uint32_t *d_results, void *stream) {
+    return compress_streams_run("zng_rocm_compress_streams2_dict_dev", false, format, level, strategy, jobs, njobs, nullptr, 0,
+                                round_bytes, nullptr, nullptr, d_results, stream, true, dict);
+}
+
+int zng_rocm_compress_members_dict_dev(int format, int level, int strategy, const zng_rocm_dict *dict, const zng_rocm_stream_job *jobs,
+                                       size_t njobs, uint8_t *d_dst, size_t dst_cap, size_t round_bytes, uint64_t *d_offsets,
+                                       uint32_t *d_checks, void *stream) {
+    return compress_streams_run("zng_rocm_compress_members_dict_dev", true, format, level, strategy, jobs, njobs, d_dst, dst_cap,
+                                round_bytes, d_offsets, d_checks, nullptr, stream, true, dict);
 }
 
 }  // extern "C"

@@ -106,6 +106,50 @@ inline int cs_jobs_check(int format, const zng_rocm_stream_job *jobs, uint64_t n
     return ZNG_ROCM_OK;
 }
 
+// ---- the shared preset dictionary (zng_rocm_compress_streams2_dict_dev, zng_rocm_compress_members_dict_dev) --------------
+// The same members with one dictionary object as every stream's history: format 0 raw (deflateSetDictionary on a raw stream),
+// format 1 zlib with the 6-byte FDICT header of framing_parse.h and the Adler-32 of the plaintext alone as the trailer; gzip has
+// no dictionary.  Levels 1..9 go through the dictionary form of the rows matcher, level 0 reads no dictionary byte.  Z_HUFFMAN_ONLY
+// and Z_RLE have another front end (deflate_rle.h) and at most one byte of history to gain: they are refused here.
+ZR_HD bool cs_dict_format_ok(int format) { return format == 0 || format == 1; }
+ZR_HD bool cs_dict_strategy_ok(int strategy) { return strategy == 0 || strategy == 1 || strategy == 4; }
+ZR_HD uint32_t cs_dict_head_bytes(int format) { return wrapper_dict_head_bytes(format); }
+ZR_HD uint8_t cs_dict_header_byte(int level, int strategy, uint32_t dictid, uint32_t k) {
+    return wrapper_dict_header_byte(level, strategy, dictid, k);
+}
+// zng_rocm_compress_streams2_dict_bound: the DICTID's four bytes on top of the plain bound; 0 for a refused format
+inline uint64_t cs_dict_bound(uint64_t n, int format) {
+    return cs_dict_format_ok(format) ? cs_bound(n, format) + (format == 1 ? 4u : 0u) : 0u;
+}
+// the call itself; `dict` is looked at only for being null
+inline int cs_dict_call_check(int format, int level, int strategy, const void *dict, const void *jobs, uint64_t njobs,
+                              const void *results) {
+    if (!dict || !cs_dict_format_ok(format) || cs_level(level) == kCsLevelRefused || !cs_dict_strategy_ok(strategy)) return ZNG_ROCM_EINVAL;
+    if (njobs && (!jobs || !results)) return ZNG_ROCM_EINVAL;
+    return ZNG_ROCM_OK;
+}
+// one job: as cs_job_check, but the history is the object's -- a dict_len of the job's own is refused -- and the bound is
+// cs_dict_bound
+inline int cs_dict_job_check(int format, const zng_rocm_stream_job &j, bool per_job_out) {
+    if (j.in_len && !j.in) return ZNG_ROCM_EINVAL;
+    if (j.dict_len || (j.flags & ~kCsBlockFlags)) return ZNG_ROCM_EINVAL;
+    if (format != 0 && j.flags) return ZNG_ROCM_EINVAL;
+    if (cs_dict_bound(j.in_len, format) > 0xffffffffull) return ZNG_ROCM_EINVAL;
+    if (per_job_out) {
+        if (!j.out) return ZNG_ROCM_EINVAL;
+        if (j.out_cap < cs_dict_bound(j.in_len, format)) return kCsBufError;
+    }
+    return ZNG_ROCM_OK;
+}
+inline int cs_dict_jobs_check(int format, const zng_rocm_stream_job *jobs, uint64_t njobs, bool per_job_out, uint64_t *bad) {
+    for (uint64_t i = 0; i < njobs; ++i)
+        if (int rc = cs_dict_job_check(format, jobs[i], per_job_out)) {
+            if (bad) *bad = i;
+            return rc;
+        }
+    return ZNG_ROCM_OK;
+}
+
 // ---- the rounds ---------------------------------------------------------------------------------------------------------
 // the round that begins at job `first` ends in front of the job returned: jobs are taken while their plaintext stays within
 // round_bytes (0 = 4 GiB); a job is never split, so a round has at least one job, however long

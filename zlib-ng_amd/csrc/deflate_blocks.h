@@ -53,5 +53,10 @@ int deflate_rows_enqueue_blocks(int level, const zng_rocm_stream_job *sjobs, siz
 uint32_t deflate_rows_segment_bytes(size_t total_in);
 int deflate_rows_enqueue_streams(int level, int strategy, const zng_rocm_stream_job *sjobs, size_t njobs, uint32_t seg_bytes,
                                  Workspace *ws, hipStream_t st, RowsBlocks *blocks);
+// The same behind ONE shared preset dictionary (dict_dev.h): every stream's history is the object's window, through the
+// dictionary form of the matcher -- strategies 0, 1 and 4; no job has a dict_len of its own.  The bytes are those of the call
+// above over the window copied in front of every plaintext with dict_len = W.
+int deflate_rows_enqueue_streams_dict(int level, int strategy, const zng_rocm_dict *dict, const zng_rocm_stream_job *sjobs,
+                                      size_t njobs, uint32_t seg_bytes, Workspace *ws, hipStream_t st, RowsBlocks *blocks);
 
 }  // namespace zr

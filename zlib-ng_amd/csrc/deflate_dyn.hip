@@ -12,6 +12,9 @@
 //        Output per segment: a bitmap of token starts (1 bit per position; a token's length is the distance to the next
 //        start), the distance of every match (u16 per 4 positions: matches are >= 4 long, so two never share a slot) --
 //        0.625 bytes of scratch per input byte (round 2: a 32-bit selector per byte) -- and the symbol histogram.
+//        lz_rows_dict_kernel is the same body (deflate_rows_body.h) behind ONE shared preset dictionary: a stream's first
+//        segment loads the window and the row tables its priming leaves from the dictionary object (rows_dict_table_kernel
+//        builds them once) instead of entering up to 32 batches of history that lie in front of the plaintext.
 //   K2 emit_dynamic_kernel one workgroup per segment = one dynamic-Huffman block: Huffman code lengths from K1's
 //        histogram (rank sort + two-queue merge, depth limit by frequency halving), canonical codes, the RLE-coded
 //        length header (trees.c send_all_trees equivalent), then the body bits assembled in an LDS tile.  Each segment
@@ -28,6 +31,7 @@
 #include "deflate_blocks.h"
 #include "deflate_dev.h"
 #include "deflate_rows.h"
+#include "dict_dev.h"
 
 #include <mutex>
 
@@ -61,6 +65,9 @@ static uint32_t segment_bytes(size_t in_len, int cus) {
 }
 constexpr uint32_t kPrime = 32768u;            // dictionary primed from the previous segment
 constexpr int      kHistWords = 320;           // 288 literal/length + 32 distance counts
+static_assert(kDictRowBatch == (uint32_t)kRowBatch && kDictRowsPosBytes == sizeof(RowShared::pos) &&
+              kDictRowsTagBytes == sizeof(RowShared::tag) && kDictRowsCntBytes == sizeof(RowShared::cnt) && kDictWindowMax == kPrime,
+              "dict_plan.h describes the tables of deflate_rows.h");
 // A segment is written as several BLOCKS, one per kSubBytes of positions (counted from the segment's first batch): zlib's
 // blocks hold about as much (lit_bufsize 16384 symbols), the codes follow the data more closely, a block may be stored
 // (<= 65535 bytes), and -- what it was done for -- every block start is a place where a parallel inflater can cut the
@@ -81,150 +88,49 @@ __global__ __launch_bounds__(kRowBatch)
 void lz_rows_kernel(const SegJob *__restrict__ jobs, unsigned long long *__restrict__ bm_base, uint16_t *__restrict__ d16_base,
                     uint32_t *__restrict__ hist_out, uint32_t max_cand, unsigned long long *__restrict__ stamp_out) {
     __shared__ RowShared sh;
+    constexpr bool DICT = false;
+    constexpr const uint8_t *dwin = nullptr;
+    constexpr const uint4 *dtab = nullptr;
+    constexpr uint32_t dW = 0u;
+#include "deflate_rows_body.h"
+}
 
-    const SegJob job = jobs[blockIdx.x];
-    const uint8_t *in = job.in;
-    const uint32_t n = job.seg_end;                 // matches never run past the segment
-    const int t = threadIdx.x, lane = t & 63;
+// The dictionary form (zng_rocm_compress_streams2_dict_dev): one shared window and the row tables its priming leaves, loaded
+// from the dictionary object, instead of a history in front of every stream (deflate_rows_body.h).
+__global__ __launch_bounds__(kRowBatch)
+void lz_rows_dict_kernel(const SegJob *__restrict__ jobs, unsigned long long *__restrict__ bm_base, uint16_t *__restrict__ d16_base,
+                         uint32_t *__restrict__ hist_out, uint32_t max_cand, unsigned long long *__restrict__ stamp_out,
+                         const uint8_t *__restrict__ dwin, const uint4 *__restrict__ dtab, uint32_t dW) {
+    __shared__ __attribute__((aligned(16))) RowShared sh;
+    constexpr bool DICT = true;
+#include "deflate_rows_body.h"
+}
 
+// The tables of a dictionary object: what lz_rows_kernel's priming loop leaves in pos / tag / cnt behind the positions
+// [0, T) of the window, T = dict_rows_primed(W) -- the same rows_insert turns (its counter carry included) by one workgroup,
+// once per dictionary.  Every string of these positions lies inside the window, so the tables do not depend on any plaintext.
+// tab: kDictRowsBytes, pos | tag | cnt, 16-byte aligned.
+__global__ __launch_bounds__(kRowBatch)
+void rows_dict_table_kernel(const uint8_t *__restrict__ window, uint32_t W, uint4 *__restrict__ tab) {
+    __shared__ __attribute__((aligned(16))) RowShared sh;
+    const int t = threadIdx.x;
     for (int i = t; i < kRows * kRowEnt / 2; i += kRowBatch) reinterpret_cast<uint32_t *>(sh.pos)[i] = 0;
     for (int i = t; i < kRows * kRowEnt / 4; i += kRowBatch) reinterpret_cast<uint32_t *>(sh.tag)[i] = 0;
     for (int i = t; i < kRows / 4; i += kRowBatch) sh.cnt[i] = 0;
-    if (t < 288) {
-        sh.hist_l[t] = 0;
-        // before the segment has tokens of its own: 8 bits per literal, 7 per length symbol, 5 per distance symbol
-        sh.cost_l[t] = (uint16_t)((t < 256 ? 8u : 7u) * kCostBit);
-    } else if (t < 320) {
-        sh.hist_d[t - 288] = 0;
-        sh.cost_d[t - 288] = (uint16_t)(5u * kCostBit);
-    }
-    if (t == 0) {
-        sh.cover = job.seg_start;
-        sh.tot_l = sh.tot_d = 0;
-    }
-
-    uint32_t P0 = job.seg_start > kPrime ? job.seg_start - kPrime : 0u;
-    P0 -= P0 % kRowBatch;
-    const uint32_t first = job.seg_start - job.seg_start % kRowBatch;   // batch holding the segment's first byte
-    unsigned long long *bm = bm_base + job.bm_off;
-    uint16_t *d16 = d16_base + job.d16_off;
-
-    // chunk [F, F + 1024) of the plaintext, one dword per lane of the first four waves; bytes at or beyond n read 0
-    auto fetch = [&](uint32_t F) -> uint32_t {
-        const uint32_t q = F + 4u * (uint32_t)t;
-        if (t >= 256 || q >= n) return 0u;
-        if (q + 4u <= n) return load_u32(in + q);
-        uint32_t v = 0;
-        for (uint32_t j = 0; q + j < n; ++j) v |= (uint32_t)load_u8(in + q + j) << (8u * j);
-        return v;
-    };
-    auto put = [&](uint32_t F, uint32_t v) {
-        if (t < 256) {
-            const uint32_t idx = (F + 4u * (uint32_t)t) & (kRingBytes - 1u);
-            *reinterpret_cast<uint32_t *>(sh.ring + idx) = v;
-            if (idx < kRingMirror) *reinterpret_cast<uint32_t *>(sh.ring + kRingBytes + idx) = v;
-        }
-    };
-    put(P0, fetch(P0));
-    put(P0 + 1024u, fetch(P0 + 1024u));
-    uint32_t chunk = fetch(P0 + 2048u);              // stored at the top of the FIRST batch: [P0 + 2048, P0 + 3072)
     __syncthreads();
-
-    // the tokens of a finished batch: bitmap word, distances, histogram
-    auto emit_tokens = [&](uint32_t Pb, const RowsToken &r, unsigned long long starts) __attribute__((always_inline)) {
-        const uint32_t p = Pb + (uint32_t)t;
-        const unsigned long long matches = __ballot(r.kind == 2u);
-        if (lane == 0) {
-            bm[(Pb - first) / 64u + (uint32_t)(t >> 6)] = starts;
-            const uint32_t nt = (uint32_t)__popcll(starts), nm = (uint32_t)__popcll(matches);
-            if (nt) atomicAdd(&sh.tot_l, nt);
-            if (nm) atomicAdd(&sh.tot_d, nm);
-        }
-        if (r.kind == 2u) {
-            uint32_t sy, eb;
-            rows_len_symbol(r.len, sy, eb);
-            atomicAdd(&sh.hist_l[sy], 1u);
-            rows_dist_symbol(r.dist, sy, eb);
-            atomicAdd(&sh.hist_d[sy], 1u);
-            d16[(p - first) >> 2] = (uint16_t)(r.dist - 1u);
-        } else if (r.kind == 1u) {
-            atomicAdd(&sh.hist_l[sh.ring[p & (kRingBytes - 1u)]], 1u);
-        }
-    };
-
-    // Two batches in flight: the compares of batch P (LDS-bound) run beside the parse of the batch before it (VALU-bound);
-    // waves 4-7 and 12-15 take the two in the opposite order, so every SIMD has both kinds of work at any time.
     const int wave_id = __builtin_amdgcn_readfirstlane(t >> 6);
-    const bool parse_first = ((wave_id >> 2) & 1) != 0;
-    int since_refresh = 0, snap_due = -1;            // a histogram snapshot (sub-block index) to write once every wave's counts are in
-    uint32_t *hist_seg = hist_out + (size_t)blockIdx.x * kMaxSub * kHistWords;
-    bool have_prev = false;
-    uint32_t P_prev = 0;
-    RowsMatch prev;
-    prev.L = prev.dist = prev.val = 0;
-    for (uint32_t P = P0;; P += kRowBatch) {
-        const bool live = P < n;                    // one more round after the last batch: its parse
-        if (!live && !have_prev) break;
-        if (live) {
-            put(P + kRingAhead, chunk);             // [P + 2048, P + 3072): what the NEXT batch reads beyond its own positions
-            chunk = fetch(P + kRingAhead + 1024u);
-        }
-        const uint32_t p = P + (uint32_t)t;
-        if (live && P < first) {                    // priming: enter the positions, nothing else
-            const bool can = p + kLzMinMatch <= n;
-            uint32_t row, tag;
-            row_key(ring_u32(sh.ring, p & (kRingBytes - 1u)), row, tag);
-            rows_insert(&sh, can, row, tag, p, wave_id);
-            continue;
-        }
-        RowsFront f;
-        uint32_t cover_in;
-        if (live) {
-            const bool refresh = since_refresh >= kRefreshBatches;
-            since_refresh = refresh ? 1 : since_refresh + 1;
-            rows_front(n, P, &sh, t, refresh, f, &cover_in);
-        } else {
-            rows_barrier();
-            cover_in = sh.cover;
-        }
-        if (snap_due >= 0) {                        // the barriers above are behind the last batch's histogram updates
-            if (t < kHistWords) hist_seg[(size_t)snap_due * kHistWords + t] = t < 288 ? sh.hist_l[t] : sh.hist_d[t - 288];
-            snap_due = -1;
-        }
-        RowsMatch cur;
-        cur.L = cur.dist = cur.val = 0;
-        uint32_t CH = 1u;
-#pragma nounroll
-        for (int ph = 0; ph < 2; ++ph) {            // ONE copy of each piece in the code, the order a run-time matter
-            if ((ph == 0) == parse_first) {
-                if (have_prev) CH = rows_parse(n, P_prev, &sh, t, prev);
-            } else if (live) {
-                cur = rows_compare(n, P, P0, &sh, t, max_cand, f);
-            }
-        }
-        if (have_prev) {
-            unsigned long long starts;
-            const RowsToken r = rows_finish(n, P_prev, &sh, t, CH, prev.dist, cover_in, &starts);
-            emit_tokens(P_prev, r, starts);
-            const uint32_t done_batches = (P_prev - first) / kRowBatch + 1u;
-            if (done_batches % kSubBatches == 0) snap_due = (int)(done_batches / kSubBatches) - 1;
-        }
-#ifdef ZR_ROWS_STAMPS
-        if (lane == 0) sh.stamps[t >> 6][8] = __builtin_amdgcn_s_memtime();
-        if (blockIdx.x == 3 && stamp_out && lane < 9 && live && P >= first + 64u * kRowBatch && P < first + 96u * kRowBatch)
-            stamp_out[(((P - first) / kRowBatch - 64u) * kRowWaves + (uint32_t)(t >> 6)) * 9u + (uint32_t)lane] = sh.stamps[t >> 6][lane];
-#endif
-        if (!live) break;
-        prev = cur;
-        P_prev = P;
-        have_prev = true;
+    const uint32_t T = dict_rows_primed(W);
+    for (uint32_t P = 0; P < T; P += kRowBatch) {
+        const uint32_t p = P + (uint32_t)t;                   // p + 4 <= T + 3 <= W
+        uint32_t row, tag;
+        row_key(load_u32(window + p), row, tag);
+        rows_insert(&sh, true, row, tag, p, wave_id);         // (every turn ends at a barrier)
     }
-    __syncthreads();
-    {                                                // the totals: the last sub-block's snapshot
-        const uint32_t span = n - first;
-        const uint32_t nsub = span ? (span + kSubBytes - 1) / kSubBytes : 1u;
-        if (t < kHistWords) hist_seg[(size_t)(nsub - 1u) * kHistWords + t] = t < 288 ? sh.hist_l[t] : sh.hist_d[t - 288];
-    }
+    for (int i = t; i < (int)(kDictRowsPosBytes / 16u); i += kRowBatch) tab[i] = reinterpret_cast<const uint4 *>(sh.pos)[i];
+    tab += kDictRowsPosBytes / 16u;
+    for (int i = t; i < (int)(kDictRowsTagBytes / 16u); i += kRowBatch) tab[i] = reinterpret_cast<const uint4 *>(sh.tag)[i];
+    tab += kDictRowsTagBytes / 16u;
+    for (int i = t; i < (int)(kDictRowsCntBytes / 16u); i += kRowBatch) tab[i] = reinterpret_cast<const uint4 *>(sh.cnt)[i];
 }
 
 // ---- dynamic Huffman ---------------------------------------------------------------------------------------
@@ -854,7 +760,8 @@ constexpr int kZHuffmanOnly = 2, kZRle = 3, kZFixed = 4;
 // the blocks are, and no job's out / out_cap is looked at.
 static int deflate_rows_enqueue(int level, int strategy, const zng_rocm_stream_job *sjobs, size_t njobs, const size_t *cap_override,
                                 uint32_t seg_bytes, Workspace *ws, hipStream_t st, unsigned long long **results,
-                                unsigned long long *d_results_copy = nullptr, RowsBlocks *keep = nullptr) {
+                                unsigned long long *d_results_copy = nullptr, RowsBlocks *keep = nullptr,
+                                const zng_rocm_dict *dobj = nullptr) {
     size_t nseg = 0;
     for (size_t s = 0; s < njobs; ++s) nseg += sjobs[s].in_len ? ((size_t)sjobs[s].in_len + seg_bytes - 1) / seg_bytes : 1;
     const size_t max_blk = nseg * kMaxSub;
@@ -880,7 +787,7 @@ static int deflate_rows_enqueue(int level, int strategy, const zng_rocm_stream_j
     size_t slot_total = 0, bm_total = 0, d16_total = 0, k = 0, nb = 0;
     for (size_t s = 0; s < njobs; ++s) {
         const zng_rocm_stream_job &j = sjobs[s];
-        const uint32_t dict = j.dict_len;
+        const uint32_t dict = dobj ? dobj->window : j.dict_len;      // (the shared window: no job has a dict_len of its own)
         const bool final_block = (j.flags & ZNG_ROCM_BLOCK_NOT_FINAL) == 0;
         const size_t n = j.in_len ? ((size_t)j.in_len + seg_bytes - 1) / seg_bytes : 1;
         const size_t b0 = nb;
@@ -888,7 +795,7 @@ static int deflate_rows_enqueue(int level, int strategy, const zng_rocm_stream_j
             // positions count from the first dictionary byte: the segments' own 32 KiB priming reaches into it
             const uint32_t a = dict + (uint32_t)(i * seg_bytes);
             const uint32_t b = dict + (uint32_t)((i + 1) * (size_t)seg_bytes < j.in_len ? (i + 1) * (size_t)seg_bytes : j.in_len);
-            jobs[k].in = (const uint8_t *)j.in - dict;
+            jobs[k].in = (const uint8_t *)((uintptr_t)j.in - dict);   // behind a shared window: never read below in + dict
             jobs[k].out = nullptr;
             jobs[k].dst = (uint8_t *)j.out;
             jobs[k].dst_cap = 0;
@@ -953,6 +860,9 @@ static int deflate_rows_enqueue(int level, int strategy, const zng_rocm_stream_j
         ZR_LAUNCH_TRACED(rle_rows_kernel<true>, dim3((unsigned)nseg), dim3(kRleThreads), st, d_jobs, d_bm, d_d16, d_hist);
     else if (strategy == kZRle)
         ZR_LAUNCH_TRACED(rle_rows_kernel<false>, dim3((unsigned)nseg), dim3(kRleThreads), st, d_jobs, d_bm, d_d16, d_hist);
+    else if (dobj)
+        ZR_LAUNCH_TRACED(lz_rows_dict_kernel, dim3((unsigned)nseg), dim3(kRowBatch), st, d_jobs, d_bm, d_d16, d_hist, kLevelCand[level],
+                         g_rows_stamps, (const uint8_t *)dobj->d_window, (const uint4 *)dobj->d_rows, dobj->window);
     else
         ZR_LAUNCH_TRACED(lz_rows_kernel, dim3((unsigned)nseg), dim3(kRowBatch), st, d_jobs, d_bm, d_d16, d_hist, kLevelCand[level], g_rows_stamps);
     ZR_HIP(hipGetLastError());
@@ -990,6 +900,20 @@ int deflate_rows_enqueue_streams(int level, int strategy, const zng_rocm_stream_
                                  Workspace *ws, hipStream_t st, RowsBlocks *blocks) {
     unsigned long long *unused = nullptr;
     return deflate_rows_enqueue(level, strategy, sjobs, njobs, nullptr, seg_bytes, ws, st, &unused, nullptr, blocks);
+}
+
+// the shared window of `dict` is every stream's history (strategies 0, 1 and 4: the matcher's dictionary form); a job's own
+// dict_len is 0
+int deflate_rows_enqueue_streams_dict(int level, int strategy, const zng_rocm_dict *dict, const zng_rocm_stream_job *sjobs,
+                                      size_t njobs, uint32_t seg_bytes, Workspace *ws, hipStream_t st, RowsBlocks *blocks) {
+    unsigned long long *unused = nullptr;
+    return deflate_rows_enqueue(level, strategy, sjobs, njobs, nullptr, seg_bytes, ws, st, &unused, nullptr, blocks, dict);
+}
+
+int launch_rows_dict_table(const uint8_t *d_window, uint32_t W, void *d_tab, hipStream_t st) {
+    hipLaunchKernelGGL(rows_dict_table_kernel, dim3(1), dim3(kRowBatch), 0, st, d_window, W, (uint4 *)d_tab);
+    ZR_HIP(hipGetLastError());
+    return ZNG_ROCM_OK;
 }
 
 }  // namespace zr

@@ -6,8 +6,10 @@
 //                  and zero padded so that the matcher's 16-byte probes stay inside
 //   the head table of the level-1 class, primed: for every bucket the LAST entered position + 1 (dict_plan.h).  One atomic
 //                  max per position: the result is that of entering the positions in order, whatever the scheduling.
+//   the row tables of the rows engine (levels 1..9 of zng_rocm_compress_streams2_dict_dev), primed: what lz_rows_kernel's
+//                  priming leaves behind the whole batches inside the window (rows_dict_table_kernel, deflate_dyn.hip).
 // The object is immutable afterwards: zng_rocm_compress_streams_dict_dev / zng_rocm_uncompress_streams_dict_dev
-// (framing_dev.hip) only read it, from any thread and any HIP stream of its device.
+// (framing_dev.hip) and zng_rocm_compress_streams2_dict_dev / zng_rocm_compress_members_dict_dev (compress_streams.hip) only read it, from any thread and any HIP stream of its device.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -34,8 +36,9 @@ int dict_usable(const zng_rocm_dict *d) {
     return ZNG_ROCM_OK;
 }
 
-// one allocation: head table | the DICTID on its way to the host (16 bytes) | window | padding
-constexpr size_t kDictIdAt = kDictHeadSlots * sizeof(uint32_t), kDictWindowAt = kDictIdAt + 16;
+// one allocation: head table | the DICTID on its way to the host (16 bytes) | row tables | window | padding
+constexpr size_t kDictIdAt = kDictHeadSlots * sizeof(uint32_t), kDictRowsAt = kDictIdAt + 16, kDictWindowAt = kDictRowsAt + kDictRowsBytes;
+static_assert(kDictRowsAt % 16 == 0 && kDictWindowAt % 16 == 0, "the matchers load tables and window in 16-byte pieces");
 
 static int dict_fill(zng_rocm_dict *d, const uint8_t *d_dict, size_t dict_len, hipStream_t st) {
     const uint32_t W = d->window;
@@ -47,6 +50,9 @@ static int dict_fill(zng_rocm_dict *d, const uint8_t *d_dict, size_t dict_len, h
                            (const uint8_t *)d->d_window, W, d->d_head);
         ZR_HIP(hipGetLastError());
     }
+    // (no primed position: the tables are the zeroes already there)
+    if (dict_rows_primed(W))
+        if (int rc = launch_rows_dict_table(d->d_window, W, d->d_rows, st)) return rc;
     uint32_t *d_id = reinterpret_cast<uint32_t *>(base + kDictIdAt);
     if (int rc = launch_checksum(true, false, 1u, 0u, d_dict, nullptr, dict_len, d_id, nullptr, st)) return rc;
     ZR_HIP(hipMemcpyAsync(&d->id, d_id, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -82,6 +88,7 @@ int zng_rocm_dict_create_dev(const uint8_t *d_dict, size_t dict_len, zng_rocm_di
     }
     d->d_head = reinterpret_cast<uint32_t *>(base);
     d->d_window = reinterpret_cast<uint8_t *>(base) + kDictWindowAt;
+    d->d_rows = reinterpret_cast<uint8_t *>(base) + kDictRowsAt;
     if (int rc = dict_fill(d, d_dict, dict_len, (hipStream_t)stream)) {
         (void)hipFree(base);
         delete d;

@@ -47,6 +47,16 @@ inline void dict_head_table(const uint8_t *window, uint32_t W, uint32_t *head) {
     for (uint32_t p = 0; p < dict_positions(W); ++p) head[dict_hash(dict_first4(window + p))] = p + 1u;
 }
 
+// ---- the rows engine (levels 1..9 of zng_rocm_compress_streams2_dict_dev, deflate_dyn.hip) ------------------------------------
+// Its search state -- the three LDS arrays pos / tag / cnt of RowShared (deflate_rows.h) -- as lz_rows_kernel's priming loop
+// leaves it behind the positions [0, T) of the window, built once per dictionary and stored in this order in the object.
+constexpr uint32_t kDictRowBatch = 1024u;         // kRowBatch: positions the engine enters per batch
+constexpr uint32_t kDictRowsPosBytes = 3584u * 8u * 2u, kDictRowsTagBytes = 3584u * 8u, kDictRowsCntBytes = 3584u;
+constexpr uint32_t kDictRowsBytes = kDictRowsPosBytes + kDictRowsTagBytes + kDictRowsCntBytes;      // 89 600
+// T: the primed positions are the whole batches whose every 4-byte string lies inside the window -- the largest multiple of
+// the batch with T + 3 <= W.  The positions from T on are entered per stream, with the plaintext their strings reach into.
+ZR_HD uint32_t dict_rows_primed(uint32_t W) { return W < 3u ? 0u : (W - 3u) / kDictRowBatch * kDictRowBatch; }
+
 // byte k (0 .. 15) of the wrapper's head
 ZR_HD uint8_t dict_header_byte(uint32_t k, uint32_t dictid) {
     if (k < 2u) return k ? (uint8_t)0x3f : (uint8_t)0x78;

@@ -13,6 +13,7 @@
 //                            walk, and the two places where these callers answer differently from the rules
 //   wrapper_trailer_verdict  check value and ISIZE: the one place where the compare order lives
 //   wrapper_header_byte, wrapper_trailer_byte   the canonical header and trailer of the writers, by format, level and strategy
+//   wrapper_dict_head_bytes, wrapper_dict_header_byte   the 6-byte zlib header with FDICT and the DICTID
 //   wrapper_le32, wrapper_be32, wrapper_head_bytes, wrapper_tail_bytes   the 32-bit fields and the canonical sizes
 #pragma once
 #include <stdint.h>
@@ -53,6 +54,17 @@ ZR_HD uint8_t wrapper_header_byte(int format, int level, int strategy, uint32_t 
     // gzip: ID1 ID2 CM FLG | MTIME x 4 | XFL OS
     return k == 0u ? (uint8_t)0x1fu : k == 1u ? (uint8_t)0x8bu : k == 2u ? (uint8_t)8u : k == 8u ? (uint8_t)wrapper_gzip_xfl(level, strategy)
          : k == 9u ? (uint8_t)3u : (uint8_t)0u;
+}
+// The zlib header of a stream with a preset dictionary (deflate.c:868-892): CMF FLG as above with FDICT set -- FCHECK makes
+// the pair a multiple of 31 with the bit in it --, then the DICTID, most significant byte first.  Formats without a dictionary
+// (raw: deflateSetDictionary leaves no trace in the stream; gzip has none, deflate.c:467) have no such header.
+ZR_HD uint32_t wrapper_dict_head_bytes(int format) { return format == 1 ? 6u : 0u; }
+// byte k (0 .. 5) of it
+ZR_HD uint8_t wrapper_dict_header_byte(int level, int strategy, uint32_t dictid, uint32_t k) {
+    if (k >= 2u) return (uint8_t)(dictid >> (8u * (5u - k)));
+    uint32_t header = ((8u + (7u << 4)) << 8) | (wrapper_zlib_flevel(level, strategy) << 6) | 0x20u;     // PRESET_DICT
+    header += 31u - header % 31u;
+    return (uint8_t)(header >> (k == 0u ? 8 : 0));
 }
 // byte k (0 .. wrapper_tail_bytes - 1) of the trailer around n plaintext bytes whose check value (Adler-32; gzip: CRC-32) is
 // `check`: zlib most significant byte first (deflate.c:1098-1101), gzip CRC-32 then ISIZE, least significant first (:1091-1096)

@@ -73,8 +73,8 @@ class QuickBatch:
 
 
 class Dictionary:
-    """zng_rocm_dict: one preset dictionary prepared once on the device (DICTID, window, primed head table) and shared by
-    every stream of WrappedBatch.run_dict / InflateDevBatch.run_dict.  `data`: uint8 CUDA tensor (or bytes, copied to the
+    """zng_rocm_dict: one preset dictionary prepared once on the device (DICTID, window, the primed tables of the level-1 class and
+    of the rows engine) and shared by every stream of WrappedBatch.run_dict / InflateDevBatch.run_dict / compress_streams2_dict_dev.  `data`: uint8 CUDA tensor (or bytes, copied to the
     device first).  .id = Adler-32 of all of it, .window = min(len, 32768).  close() frees the object."""
 
     def __init__(self, data, stream=None):
@@ -296,6 +296,30 @@ def compress_members_dev(jobs, njobs, dst, offsets, fmt, level=-1, strategy=0, r
                                                     rocm._dev_ptr(dst) if cap else None, cap, int(round_bytes),
                                                     rocm._dev_ptr(offsets) if offsets is not None else None,
                                                     rocm._dev_ptr(checks) if checks is not None else None, rocm._stream_ptr(stream))
+
+
+def compress_streams2_dict_bound(n, fmt):
+    return rocm.lib().zng_rocm_compress_streams2_dict_bound(int(n), int(fmt))
+
+
+def compress_streams2_dict_dev(dictionary, jobs, njobs, results, fmt, level=-1, strategy=0, round_bytes=0, stream=None):
+    """zng_rocm_compress_streams2_dict_dev: compress_streams2_dev with the Dictionary's window as every stream's history (fmt 0
+    raw, 1 zlib with the 6-byte FDICT header; strategy 0, 1 or 4; a job has no dict_len of its own).  `dictionary` may be None
+    (the call refuses it).  Returns the status."""
+    rocm._need_init()
+    return rocm.lib().zng_rocm_compress_streams2_dict_dev(int(fmt), int(level), int(strategy), dictionary.h if dictionary is not None else None,
+                                                          C.byref(jobs), int(njobs), int(round_bytes),
+                                                          rocm._dev_ptr(results) if results is not None else None, rocm._stream_ptr(stream))
+
+
+def compress_members_dict_dev(dictionary, jobs, njobs, dst, offsets, fmt, level=-1, strategy=0, round_bytes=0, checks=None, stream=None):
+    """zng_rocm_compress_members_dict_dev: compress_members_dev with the Dictionary's window as every stream's history."""
+    rocm._need_init()
+    cap = int(dst.numel()) if dst is not None else 0
+    return rocm.lib().zng_rocm_compress_members_dict_dev(int(fmt), int(level), int(strategy), dictionary.h if dictionary is not None else None,
+                                                         C.byref(jobs), int(njobs), rocm._dev_ptr(dst) if cap else None, cap, int(round_bytes),
+                                                         rocm._dev_ptr(offsets) if offsets is not None else None,
+                                                         rocm._dev_ptr(checks) if checks is not None else None, rocm._stream_ptr(stream))
 
 
 def compress_streams2_last_rounds():

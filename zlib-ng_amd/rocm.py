@@ -119,6 +119,11 @@ _PROTOS = {
     "zng_rocm_compress_streams_dict_bound": (C.c_size_t, [C.c_size_t, C.c_int]),
     "zng_rocm_compress_streams_dict_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "zng_rocm_uncompress_streams_dict_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "zng_rocm_compress_streams2_dict_bound": (C.c_size_t, [C.c_size_t, C.c_int]),
+    "zng_rocm_compress_streams2_dict_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                                      C.c_void_p, C.c_void_p]),
+    "zng_rocm_compress_members_dict_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                     C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "zng_rocm_inflate_message": (C.c_char_p, [C.c_uint32]),
     "zng_rocm_inflate_tokens_free": (None, [C.c_void_p]),
     "zng_rocm_inflate_resolve_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
