@@ -9,6 +9,12 @@
  *                                        update_hash / quick_insert_string / insert_string
  *   match_tpl.h:26-280 (non-SLOW, OPTIMAL_CMP < 32 instantiation = longest_match_c,
  *                       arch/generic/compare256_c.c:49-52)    -> oracle_longest_match
+ *
+ * longest_match_c is match_tpl.h instantiated with the build host's OPTIMAL_CMP, so it is not one function: an
+ * x86-64 default build gives it 8-byte probes (:141-166), which skip candidates the byte-pair form (:167-173)
+ * evaluates, and below level 5 an evaluated candidate that does not improve ends the search.  This file follows the
+ * byte-pair form, and every function here is pinned bit for bit to the reference compiled with NO_UNALIGNED
+ * (OPTIMAL_CMP 8): oracle/_ref/libzng_ref_prims.so, tests/test_oracle_ref_prims.py.
  */
 #include <string.h>
 #include "zng_oracle.h"

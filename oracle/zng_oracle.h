@@ -9,8 +9,14 @@
  * 2.2.2); the reference file:line it follows is cited at each definition.
  * Parity pinning (see oracle/README.md): the reference's own known-answer
  * vectors (tests/golden/, extracted from test/test_adler32.cc,
- * test/test_crc32.cc, test/infcover.c ...) plus oracle/_ref (the reference's
- * arch/generic/crc32_braid_c.c compiled from its own sources).
+ * test/test_crc32.cc, test/infcover.c ...) plus oracle/_ref: the reference's
+ * arch/generic/crc32_braid_c.c compiled from its own sources, and -- for the
+ * deflate-side primitives and chunkmemset_safe, which have no vectors -- the
+ * reference itself built out of tree with NO_UNALIGNED behind ref_shim.c
+ * (libzng_ref_prims.so; tests/test_oracle_ref_prims.py holds every oracle_*
+ * function of those sections against it, bit for bit).  longest_match_c depends
+ * on the reference's build (OPTIMAL_CMP); oracle and product follow the
+ * byte-pair form a NO_UNALIGNED build has.
  */
 #ifndef ZNG_ORACLE_H
 #define ZNG_ORACLE_H

@@ -96,6 +96,40 @@ def load_ref_crc32():
     return fn
 
 
+_REF_PRIMS = {}
+
+
+def load_ref_prims(variant="bytecmp"):
+    """The reference's own deflate/inflate primitives behind oracle/ref_shim.c (oracle/_ref, built by
+    `make -C oracle` where the reference tree is present).  variant "bytecmp": the reference compiled with
+    NO_UNALIGNED (OPTIMAL_CMP 8, the byte-pair probes of match_tpl.h), the one every parity test pins against;
+    "native": the build host's default OPTIMAL_CMP, for measurements only.  The ref_* functions take the oracle's
+    argument types.  A missing library is an error: build() produces it and it travels with the working tree."""
+    if variant in _REF_PRIMS:
+        return _REF_PRIMS[variant]
+    name = {"bytecmp": "libzng_ref_prims.so", "native": "libzng_ref_prims_native.so"}[variant]
+    path = os.path.join(ORACLE_DIR, "_ref", name)
+    if not os.path.exists(path):
+        raise FileNotFoundError("%s is missing: `make -C oracle` builds it where the reference tree is present" % path)
+    lib = C.CDLL(path)
+    vp, u32, st = C.c_void_p, C.c_uint32, C.POINTER(DeflateState)
+    _sig(lib, "ref_slide_hash", None, [st])
+    _sig(lib, "ref_compare256", u32, [vp, vp])
+    _sig(lib, "ref_update_hash", u32, [u32, u32])
+    _sig(lib, "ref_quick_insert_string", C.c_uint16, [st, u32])
+    _sig(lib, "ref_insert_string", None, [st, u32, u32])
+    _sig(lib, "ref_update_hash_roll", u32, [u32, u32])
+    _sig(lib, "ref_quick_insert_string_roll", C.c_uint16, [st, u32])
+    _sig(lib, "ref_insert_string_roll", None, [st, u32, u32])
+    _sig(lib, "ref_longest_match", u32, [st, C.c_uint16])
+    _sig(lib, "ref_longest_match_slow", u32, [st, C.c_uint16])
+    _sig(lib, "ref_chunksize", u32, [])
+    _sig(lib, "ref_chunkmemset_safe", vp, [vp, vp, C.c_uint, C.c_uint])
+    _sig(lib, "ref_optimal_cmp", C.c_int, [])
+    _REF_PRIMS[variant] = lib
+    return lib
+
+
 def np_ptr(arr):
     """address of a numpy array's first byte (array must stay alive)"""
     return arr.ctypes.data

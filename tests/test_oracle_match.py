@@ -1,9 +1,11 @@
-"""Pin the oracle's deflate-side / inflate-side primitives.
+"""Independent models of the oracle's deflate-side / inflate-side primitives.
 
 The reference has direct tests only for compare256 (test/test_compare256.cc:25-51, a property test re-run
-here).  slide_hash / insert_string / longest_match / chunkmemset_safe have NO reference vectors (SURVEY.md
-section 4): they are checked against the values SURVEY.md 9.1 recorded from the real reference and against
-independent pure-Python models of the documented semantics -- "parity unpinned" beyond that.
+here).  slide_hash / insert_string / longest_match / chunkmemset_safe have no reference vectors (SURVEY.md
+section 4).  They are pinned bit for bit to the reference's own functions, compiled with NO_UNALIGNED, in
+tests/test_oracle_ref_prims.py (longest_match_c depends on the reference's build; oracle and product follow
+the byte-pair form of that build).  This file stays as a second opinion: the values SURVEY.md 9.1 recorded
+from the real reference and independent pure-Python models of the documented semantics.
 """
 import ctypes as C
 
@@ -149,8 +151,8 @@ def test_chunkmemset_safe_is_lz77_copy(oracle):
 
 
 def test_rolling_hash_variants(oracle):
-    """insert_string_roll.c (level 9).  The reference holds no vectors for it -> "parity unpinned"; checked against
-    an independent Python model of the template and against the closed form the device kernel uses (after three
+    """insert_string_roll.c (level 9).  The reference holds no vectors for it (it is pinned to the reference's
+    binary in test_oracle_ref_prims.py); checked here against an independent Python model of the template and against the closed form the device kernel uses (after three
     bytes the key holds exactly those three: (b0 << 10 ^ b1 << 5 ^ b2) & 32767)."""
     assert oracle.oracle_update_hash_roll(0, 0x61) == 0x61
     assert oracle.oracle_update_hash_roll(0x7fff, 0x1ff) == ((0x7fff << 5) ^ 0xff) & 32767   # only the low byte counts
