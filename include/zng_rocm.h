@@ -678,6 +678,47 @@ int    zng_rocm_compress_members_dict_dev(int format, int level, int strategy, c
                                           const zng_rocm_stream_job *jobs, size_t njobs, uint8_t *d_dst, size_t dst_cap,
                                           size_t round_bytes, uint64_t *d_offsets, uint32_t *d_checks, void *stream);
 
+/* Many small device-resident streams whose plaintext lengths nobody handed over: the read side of
+ * zng_rocm_compress_members_dev.  Raw deflate and zlib members do not record their length; these two calls find it on the
+ * device.  Both are asynchronous on `stream`, with no host synchronisation and no device-to-host copy inside; results are
+ * valid once the stream has got there.
+ *   format    0 raw, 1 zlib, 2 gzip; another value is ZNG_ROCM_EINVAL
+ *   dict      NULL, or a zng_rocm_dict for format 0 and 1 (format 2 with one: ZNG_ROCM_EINVAL, as in the *_dict calls)
+ *   jobs      HOST array, copied internally.  in / in_len: the whole member with its wrapper, as
+ *             zng_rocm_uncompress_streams_dev takes them, in_len below 2 GiB; out and out_cap are not looked at; flags 0
+ *   refusals  ZNG_ROCM_EINVAL before anything is launched or written: the format, a null buffer with a length, in_len of 2 GiB
+ *             and more, flags, a dict_len above 32768 or beside `dict` or a wrapped format, a null d_results with njobs > 0.  A
+ *             dictionary made before a zng_rocm_shutdown(): ZNG_ROCM_ENODEV, after the argument checks
+ *
+ * zng_rocm_inflate_sizes_dev: d_results (device, 4 words per job) = {plaintext bytes, input bytes consumed, status, message
+ *   id}: the row zng_rocm_inflate_streams_dev (format 0) or zng_rocm_uncompress_streams_dev / _dict_dev (1, 2) would write for
+ *   the job with out_cap = 0x7fffffff and its history in place -- every header refusal, "need dictionary", the DICTID mismatch
+ *   (-3, message 0), every data error with its message and its count of bytes consumed, truncation (-5) -- except that the
+ *   trailer's check value and ISIZE are not compared: there is no plaintext to check.  Status 1 for a wrapped member: header
+ *   accepted, payload decoded to its final block, the 4 / 8 trailer bytes present and counted (input that ends inside the
+ *   trailer: -5).  No output and no history byte is touched; of the history only the LENGTH matters: jobs[i].dict_len (format 0
+ *   without `dict`: the bytes the caller will place in front of `out`) or the object's window as the header's verdict gives
+ *   it.  A plaintext that does not fit 0x7fffffff bytes: {0x7fffffff, ., -5, "output buffer too small"}.  One field is NOT the
+ *   decode's: the plaintext count of a stream that runs out of input (-5, "input ended ...") is the bytes of the symbols whose
+ *   bits were all input -- what inflate() delivers for that input -- where the decode's partial count also holds what the
+ *   zero bits behind the input decoded to.  njobs == 0 returns 0.
+ *
+ * zng_rocm_uncompress_packed_dev: sizes, places, decode and verification in one enqueue sequence.  A job whose sizing row has
+ *   status 1 gets its size in bytes of d_dst, every other job none; job i starts at d_offsets[i] = the end of the bytes in front
+ *   of it, rounded up to `align` (0 or 1: back to back; else a power of two up to 4096, anything else ZNG_ROCM_EINVAL);
+ *   d_offsets (device, njobs + 1, required) [njobs] = the end of the last job's bytes: the room the batch needs.  Padding is never
+ *   written.  A job that ends at or before dst_cap is decoded by the existing engine and verified (check value and ISIZE
+ *   compared: "incorrect data check" / "incorrect length check" appear here, out_len the decoded count); a job that does not fit
+ *   gets {0, 0, -5, "output buffer too small"} and nothing is stored at or behind d_dst + dst_cap -- d_offsets still describes
+ *   the whole layout, so a caller allocates d_offsets[njobs] bytes and calls again; a job whose sizing row was not status 1 gets
+ *   {0, the sizing row's in_used, its status, its message}.  Complete streams only: for the bytes in front of a fault decode
+ *   that stream alone.  Refused on top: jobs[i].dict_len != 0, a null d_dst with dst_cap > 0, a null d_offsets or d_results. */
+int    zng_rocm_inflate_sizes_dev(int format, const zng_rocm_dict *dict, const zng_rocm_inflate_dev_job *jobs, size_t njobs,
+                                  uint32_t *d_results, void *stream);
+int    zng_rocm_uncompress_packed_dev(int format, const zng_rocm_dict *dict, const zng_rocm_inflate_dev_job *jobs, size_t njobs,
+                                      uint8_t *d_dst, size_t dst_cap, uint32_t align, uint64_t *d_offsets, uint32_t *d_results,
+                                      void *stream);
+
 /* zlib (format 1) / gzip (format 2) members around the LARGE device inflaters: zng_rocm_inflate_large_streams_dev (the
  * batch) and zng_rocm_inflate_large_pieces_dev (one member of any length) for wrapped streams that already sit in device
  * memory.  format 0 is the raw call itself, field for field and byte for byte; any other format value is ZNG_ROCM_EINVAL

@@ -97,6 +97,7 @@ enum ScratchSlot {
     kScrCompressStreams,    // device: file offset | job table of the whole call | a round's check values
                             //   (zng_rocm_compress_streams2_dev, zng_rocm_compress_members_dev)
     kScrCompressStreamsHost, // pinned: the job table on its way up
+    kScrSizes,              // device: the sizing rows of zng_rocm_uncompress_packed_dev (4 words per job)
     kScrCount
 };
 

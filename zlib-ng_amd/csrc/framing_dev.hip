@@ -28,6 +28,7 @@
 #include "checksum_args.h"
 #include "context.h"
 #include "dict_dev.h"
+#include "framing_dev.h"
 #include "framing_parse.h"
 #include "gf2.h"
 #include "inflate_dev.h"
@@ -213,9 +214,43 @@ static int compress_streams_body(int format, const zng_rocm_dict *dict, const zn
     return ZNG_ROCM_OK;
 }
 
+// the two halves of the uncompress pipeline over tables that already sit in device memory (framing_dev.h): the header pass,
+// and everything behind it -- what zng_rocm_uncompress_packed_dev (inflate_sizes.hip) runs on a table the device patched
+int launch_parse_header(int format, const zng_rocm_dict *dict, const InflateJobDev *d_given, size_t njobs, InflateJobDev *d_patched,
+                        uint32_t *d_head, hipStream_t st) {
+    if (!njobs) return ZNG_ROCM_OK;
+    const dim3 grid((unsigned)((njobs + 255) / 256)), block(256);
+    hipLaunchKernelGGL(parse_header_kernel, grid, block, 0, st, d_given, (uint32_t)njobs, format, dict ? dict->id : 0u,
+                       dict ? dict->window : 0u, dict ? 1 : 0, ctx()->tables, d_patched, d_head);
+    ZR_HIP(hipGetLastError());
+    return ZNG_ROCM_OK;
+}
+
+int uncompress_patched_device(int format, const zng_rocm_dict *dict, const InflateJobDev *d_given, const InflateJobDev *d_patched,
+                              const uint32_t *d_head, uint32_t *d_checks, uint8_t *d_msg, Partial *d_part, size_t njobs,
+                              uint32_t *d_results, hipStream_t st) {
+    if (!njobs) return ZNG_ROCM_OK;
+    Context *c = ctx();
+    const dim3 grid((unsigned)((njobs + 255) / 256)), block(256);
+    if (int rc = dict ? launch_inflate_streams_dict_device(d_patched, njobs, d_results, dict->d_window + dict->window, st)
+                      : launch_inflate_streams_device(d_patched, njobs, d_results, st))
+        return rc;
+    if (format) {
+        StreamArgs *d_sa = reinterpret_cast<StreamArgs *>(d_msg);
+        FinalArgs *d_fa = reinterpret_cast<FinalArgs *>(d_msg + njobs * sizeof(StreamArgs));
+        const bool adler = format == 1, crc = format == 2;
+        hipLaunchKernelGGL(fill_check_args_kernel, grid, block, 0, st, d_patched, d_results, (uint32_t)njobs, c->tables,
+                           adler ? 1 : 0, crc ? 1 : 0, d_sa, d_fa);
+        ZR_HIP(hipGetLastError());
+        if (int rc = launch_checksum_batch_device(adler, crc, d_sa, d_fa, d_part, njobs, d_checks, st)) return rc;
+    }
+    hipLaunchKernelGGL(verify_trailer_kernel, grid, block, 0, st, d_given, d_head, d_checks, (uint32_t)njobs, format, d_results);
+    ZR_HIP(hipGetLastError());
+    return ZNG_ROCM_OK;
+}
+
 static int uncompress_streams_body(int format, const zng_rocm_dict *dict, const zng_rocm_inflate_dev_job *jobs, size_t njobs,
                                    uint32_t *d_results, hipStream_t st) {
-    Context *c = ctx();
     DeviceGuard dev;
     Workspace *ws = workspace_for(st);
     if (!ws) return ZNG_ROCM_ENOMEM;
@@ -246,25 +281,8 @@ static int uncompress_streams_body(int format, const zng_rocm_dict *dict, const 
     }
     ZR_HIP(hipMemcpyAsync(d_given, h_given, njobs * sizeof(InflateJobDev), hipMemcpyHostToDevice, st));
     if (int rc = host_tables_release(ws, st)) return rc;
-    const dim3 grid((unsigned)((njobs + 255) / 256)), block(256);
-    hipLaunchKernelGGL(parse_header_kernel, grid, block, 0, st, d_given, (uint32_t)njobs, format, dict ? dict->id : 0u,
-                       dict ? dict->window : 0u, dict ? 1 : 0, c->tables, d_patched, d_head);
-    ZR_HIP(hipGetLastError());
-    if (int rc = dict ? launch_inflate_streams_dict_device(d_patched, njobs, d_results, dict->d_window + dict->window, st)
-                      : launch_inflate_streams_device(d_patched, njobs, d_results, st))
-        return rc;
-    if (format) {
-        StreamArgs *d_sa = reinterpret_cast<StreamArgs *>(d_msg);
-        FinalArgs *d_fa = reinterpret_cast<FinalArgs *>(d_msg + njobs * sizeof(StreamArgs));
-        const bool adler = format == 1, crc = format == 2;
-        hipLaunchKernelGGL(fill_check_args_kernel, grid, block, 0, st, d_patched, d_results, (uint32_t)njobs, c->tables,
-                           adler ? 1 : 0, crc ? 1 : 0, d_sa, d_fa);
-        ZR_HIP(hipGetLastError());
-        if (int rc = launch_checksum_batch_device(adler, crc, d_sa, d_fa, d_part, njobs, d_checks, st)) return rc;
-    }
-    hipLaunchKernelGGL(verify_trailer_kernel, grid, block, 0, st, d_given, d_head, d_checks, (uint32_t)njobs, format, d_results);
-    ZR_HIP(hipGetLastError());
-    return ZNG_ROCM_OK;
+    if (int rc = launch_parse_header(format, dict, d_given, njobs, d_patched, d_head, st)) return rc;
+    return uncompress_patched_device(format, dict, d_given, d_patched, d_head, d_checks, d_msg, d_part, njobs, d_results, st);
 }
 
 }  // namespace zr

@@ -260,10 +260,46 @@ class InflateDevBatch:
                                                                     rocm._dev_ptr(self.results), rocm._stream_ptr(stream)),
                     "zng_rocm_uncompress_streams_dict_dev")
 
+    def run_sizes(self, fmt, dictionary=None, stream=None):
+        """the sizing pass over the same streams (zng_rocm_inflate_sizes_dev): fmt 0 raw, 1 zlib, 2 gzip; `results` gets the row
+        the decode would write with all the room there is -- plaintext length, input consumed, status, message -- with no byte
+        of output or history touched and no check value compared.  Of the history only its length counts: dict_len (fmt 0
+        without a dictionary) or the deflate.Dictionary's window.  Asynchronous on `stream`."""
+        rocm._check(rocm.lib().zng_rocm_inflate_sizes_dev(int(fmt), dictionary.h if dictionary is not None else None,
+                                                          C.byref(self.jobs), self.n, rocm._dev_ptr(self.results),
+                                                          rocm._stream_ptr(stream)), "zng_rocm_inflate_sizes_dev")
+
     def rows(self):
         """[(status, out_len, in_used, message)] (synchronises)"""
         r = self.results.cpu().tolist()
         return [(row[2], row[0], row[1], inflate_message(row[3])) for row in r]
+
+
+def packed_jobs(src, in_off, in_len):
+    """the job table of uncompress_packed_dev: member i = src[in_off[i] : in_off[i] + in_len[i]] of the uint8 CUDA tensor `src`"""
+    n = len(in_len)
+    jobs = (InflateDevJob * max(n, 1))()
+    base = src.data_ptr() if src is not None and src.numel() else 0
+    for i in range(n):
+        if int(in_off[i]) + int(in_len[i]) > (src.numel() if src is not None else 0):
+            raise ValueError("stream %d does not fit its tensor" % i)
+        jobs[i].in_ptr = base + int(in_off[i]) if int(in_len[i]) else None
+        jobs[i].in_len = int(in_len[i])
+    return jobs
+
+
+def uncompress_packed_dev(fmt, jobs, njobs, dst, offsets, results, align=1, dictionary=None, stream=None):
+    """zng_rocm_uncompress_packed_dev: the members of `jobs` (packed_jobs) sized, placed and decoded back to back in the uint8
+    CUDA tensor `dst` (dst.numel() is dst_cap; None: no destination), every start rounded up to `align`.  `offsets`: int64
+    CUDA tensor of njobs + 1 (starts, then the room the batch needs -- above dst_cap when it did not all fit); `results`: int32
+    CUDA tensor [njobs, 4] = {bytes, input used, status, message id}.  Asynchronous on `stream`; returns the status."""
+    rocm._need_init()
+    cap = int(dst.numel()) if dst is not None else 0
+    return rocm.lib().zng_rocm_uncompress_packed_dev(int(fmt), dictionary.h if dictionary is not None else None, C.byref(jobs),
+                                                     int(njobs), rocm._dev_ptr(dst) if cap else None, cap, int(align),
+                                                     rocm._dev_ptr(offsets) if offsets is not None else None,
+                                                     rocm._dev_ptr(results) if results is not None else None,
+                                                     rocm._stream_ptr(stream))
 
 
 SUBBLOCK = 1                                              # ZNG_ROCM_INFLATE_SUBBLOCK

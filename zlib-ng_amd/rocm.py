@@ -124,6 +124,9 @@ _PROTOS = {
                                                       C.c_void_p, C.c_void_p]),
     "zng_rocm_compress_members_dict_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                                      C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "zng_rocm_inflate_sizes_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "zng_rocm_uncompress_packed_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "zng_rocm_inflate_message": (C.c_char_p, [C.c_uint32]),
     "zng_rocm_inflate_tokens_free": (None, [C.c_void_p]),
     "zng_rocm_inflate_resolve_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
