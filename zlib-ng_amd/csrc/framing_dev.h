@@ -1,5 +1,6 @@
 // framing_dev.h -- the uncompress pipeline of framing_dev.hip over tables that already sit in device memory, for the calls that
-// fill such a table on the device themselves (inflate_sizes.hip).  Everything is enqueued on `stream`; nothing synchronises.
+// fill such a table on the device themselves (inflate_sizes.hip), and the upload of the caller's jobs in front of it.
+// Everything is enqueued on `stream`; nothing synchronises.
 #pragma once
 #include "checksum_args.h"
 #include "context.h"
@@ -19,5 +20,19 @@ int launch_parse_header(int format, const zng_rocm_dict *dict, const InflateJobD
 int uncompress_patched_device(int format, const zng_rocm_dict *dict, const InflateJobDev *d_given, const InflateJobDev *d_patched,
                               const uint32_t *d_head, uint32_t *d_checks, uint8_t *d_msg, Partial *d_part, size_t njobs,
                               uint32_t *d_results, hipStream_t stream);
+
+// The front of every uncompress and sizing call: the caller's jobs as a device table, and their headers parsed.  Reserves the
+// scratch of the pipeline above (the given and the patched table, the head rows and, with `checks`, the check values' words,
+// messages and partials), fills the pinned host table, copies it up and runs launch_parse_header.  with_out: the jobs carry
+// out / out_cap and take neither dict_len nor flags -- a job that breaks this is refused here, ZNG_ROCM_EINVAL; else they carry
+// dict_len, have no output yet, and the caller has checked them.  The caller holds ws->mu.
+struct GivenJobs {
+    InflateJobDev *d_given, *d_patched;
+    uint32_t *d_head, *d_checks;            // d_checks, d_msg, d_part: null without `checks`
+    uint8_t *d_msg;
+    Partial *d_part;
+};
+int upload_given_jobs(Workspace *ws, int format, const zng_rocm_dict *dict, const zng_rocm_inflate_dev_job *jobs, size_t njobs,
+                      bool with_out, bool checks, GivenJobs *g, hipStream_t stream);
 
 }  // namespace zr

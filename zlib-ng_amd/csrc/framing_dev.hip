@@ -215,7 +215,8 @@ static int compress_streams_body(int format, const zng_rocm_dict *dict, const zn
 }
 
 // the two halves of the uncompress pipeline over tables that already sit in device memory (framing_dev.h): the header pass,
-// and everything behind it -- what zng_rocm_uncompress_packed_dev (inflate_sizes.hip) runs on a table the device patched
+// and everything behind it -- what zng_rocm_uncompress_packed_dev (inflate_sizes.hip) runs on a table the device patched --
+// and, behind them, the one place that puts a caller's jobs there (upload_given_jobs)
 int launch_parse_header(int format, const zng_rocm_dict *dict, const InflateJobDev *d_given, size_t njobs, InflateJobDev *d_patched,
                         uint32_t *d_head, hipStream_t st) {
     if (!njobs) return ZNG_ROCM_OK;
@@ -249,26 +250,27 @@ int uncompress_patched_device(int format, const zng_rocm_dict *dict, const Infla
     return ZNG_ROCM_OK;
 }
 
-static int uncompress_streams_body(int format, const zng_rocm_dict *dict, const zng_rocm_inflate_dev_job *jobs, size_t njobs,
-                                   uint32_t *d_results, hipStream_t st) {
-    DeviceGuard dev;
-    Workspace *ws = workspace_for(st);
-    if (!ws) return ZNG_ROCM_ENOMEM;
-    std::lock_guard<std::mutex> use(ws->mu);
-    InflateJobDev *d_given = nullptr, *h_given = nullptr, *d_patched = nullptr;
-    uint32_t *d_words = nullptr;
-    uint8_t *d_msg = nullptr;
-    Partial *d_part = nullptr;
-    if (int rc = scratch_reserve(ws, kScrInflateDevJobs, 2 * njobs * sizeof(InflateJobDev), false, (void **)&d_given)) return rc;
-    d_patched = d_given + njobs;
-    if (int rc = scratch_reserve(ws, kScrFrameWords, njobs * 4 * sizeof(uint32_t), false, (void **)&d_words)) return rc;
-    uint32_t *d_head = d_words, *d_checks = d_words + 2 * njobs;
-    if (int rc = scratch_reserve(ws, kScrCheckMessages, njobs * (sizeof(StreamArgs) + sizeof(FinalArgs)), false, (void **)&d_msg)) return rc;
-    if (int rc = scratch_reserve(ws, kScrCheckPartials, njobs * sizeof(Partial), false, (void **)&d_part)) return rc;
+int upload_given_jobs(Workspace *ws, int format, const zng_rocm_dict *dict, const zng_rocm_inflate_dev_job *jobs, size_t njobs,
+                      bool with_out, bool checks, GivenJobs *g, hipStream_t st) {
+    InflateJobDev *h_given = nullptr;
+    *g = GivenJobs{};
+    if (int rc = scratch_reserve(ws, kScrInflateDevJobs, 2 * njobs * sizeof(InflateJobDev), false, (void **)&g->d_given)) return rc;
+    g->d_patched = g->d_given + njobs;
+    // head rows: 2 words per job; the check values: 2 more
+    if (int rc = scratch_reserve(ws, kScrFrameWords, njobs * (checks ? 4 : 2) * sizeof(uint32_t), false, (void **)&g->d_head)) return rc;
+    if (checks) {
+        g->d_checks = g->d_head + 2 * njobs;
+        if (int rc = scratch_reserve(ws, kScrCheckMessages, njobs * (sizeof(StreamArgs) + sizeof(FinalArgs)), false, (void **)&g->d_msg)) return rc;
+        if (int rc = scratch_reserve(ws, kScrCheckPartials, njobs * sizeof(Partial), false, (void **)&g->d_part)) return rc;
+    }
     if (int rc = host_tables_acquire(ws)) return rc;
     if (int rc = scratch_reserve(ws, kScrInflateDevJobsHost, njobs * sizeof(InflateJobDev), true, (void **)&h_given)) return rc;
     for (size_t i = 0; i < njobs; ++i) {
         const zng_rocm_inflate_dev_job &j = jobs[i];
+        if (!with_out) {
+            h_given[i] = InflateJobDev{(const uint8_t *)j.in, nullptr, j.in_len, 0u, j.dict_len, 0u};
+            continue;
+        }
         if ((j.in_len && !j.in) || (j.out_cap && !j.out) || j.in_len > 0x7fffffffull || j.out_cap > 0x7fffffffull ||
             j.dict_len || j.flags) {
             set_error(dict ? "job %zu: null buffer, a stream or output of 2 GiB and more, or dict_len / flags (the history is the "
@@ -279,10 +281,20 @@ static int uncompress_streams_body(int format, const zng_rocm_dict *dict, const 
         }
         h_given[i] = InflateJobDev{(const uint8_t *)j.in, (uint8_t *)j.out, j.in_len, j.out_cap, 0u, 0u};
     }
-    ZR_HIP(hipMemcpyAsync(d_given, h_given, njobs * sizeof(InflateJobDev), hipMemcpyHostToDevice, st));
+    ZR_HIP(hipMemcpyAsync(g->d_given, h_given, njobs * sizeof(InflateJobDev), hipMemcpyHostToDevice, st));
     if (int rc = host_tables_release(ws, st)) return rc;
-    if (int rc = launch_parse_header(format, dict, d_given, njobs, d_patched, d_head, st)) return rc;
-    return uncompress_patched_device(format, dict, d_given, d_patched, d_head, d_checks, d_msg, d_part, njobs, d_results, st);
+    return launch_parse_header(format, dict, g->d_given, njobs, g->d_patched, g->d_head, st);
+}
+
+static int uncompress_streams_body(int format, const zng_rocm_dict *dict, const zng_rocm_inflate_dev_job *jobs, size_t njobs,
+                                   uint32_t *d_results, hipStream_t st) {
+    DeviceGuard dev;
+    Workspace *ws = workspace_for(st);
+    if (!ws) return ZNG_ROCM_ENOMEM;
+    std::lock_guard<std::mutex> use(ws->mu);
+    GivenJobs g;
+    if (int rc = upload_given_jobs(ws, format, dict, jobs, njobs, true, true, &g, st)) return rc;
+    return uncompress_patched_device(format, dict, g.d_given, g.d_patched, g.d_head, g.d_checks, g.d_msg, g.d_part, njobs, d_results, st);
 }
 
 }  // namespace zr

@@ -10,13 +10,15 @@
 // Nothing crosses PCIe between the kernels and nothing synchronises: the lengths only ever exist on the device.
 //
 // The sizing kernel is the stream kernel of inflate_dev.hip with everything taken out that moves a byte: one wavefront per
-// stream, the same 64-word fetch and bit buffer, the same block headers and the same table builder (inflate_tables.h), and a
-// symbol loop that adds a literal's 1 and a match's length to a count.  It still decodes every distance -- for its bits, and
-// for "invalid distance too far back" against count + history length -- but has no window, no ring, no copy and no store: the
-// history's LENGTH is all it knows of the history.  Every verdict, message and count of consumed bytes is the decoder's
-// (inflate_streams_body.h), the truncation rule of kBadWide included: the two are held against each other stream by stream
-// in tests/test_gpu_inflate_sizes.py.  The rules on top -- argument checks, saturation, the member's row, places, fit, final
-// rows -- are inflate_sizes_plan.h's, for host and device alike.
+// stream and a symbol loop that adds a literal's 1 and a match's length to a count.  What comes in front of the symbol loop is
+// the decoder's own text, included here as it is there: the 64-word fetch and bit buffer (inflate_bits_body.h), the fixed
+// tables and the dynamic block header (inflate_block_tables_body.h), the table builder and the packed LDS layout
+// (inflate_tables.h) -- so the same bits are consumed in front of every header fault by construction.  The loop still decodes
+// every distance -- for its bits, and for "invalid distance too far back" against count + history length -- but has no window,
+// no ring, no copy and no store: the history's LENGTH is all it knows of the history.  Every verdict, message and count of
+// consumed bytes of the loop is the decoder's (inflate_streams_body.h), the truncation rule of kBadWide included: the two are
+// held against each other stream by stream in tests/test_gpu_inflate_sizes.py.  The rules on top -- argument checks,
+// saturation, the member's row, places, fit, final rows -- are inflate_sizes_plan.h's, for host and device alike.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -28,51 +30,6 @@
 #include "inflate_tables.h"
 
 namespace zr {
-
-// The tables of one stream, packed as InflateLdsPart packs them (the code-length code only lives while a dynamic header is
-// read: it shares the distance table's place) and without a ring: 7.2 KiB against the decoder's 9.9 KiB.
-template <int DR, int LR>
-struct SizesLds {
-    uint32_t lit[1 << LR];                  // wide entries (wide_literal); the builder's 16-bit entries lie in the first half
-    union {
-        uint32_t dist[1 << DR];             // wide entries (wide_distance)
-        struct {
-            uint16_t cl[1 << kClRoot];
-            uint16_t sorted_cl[32];
-            uint32_t cnt[16];
-            uint16_t first[16], offs[16];
-            uint8_t  cl_lens[24];
-        } h;
-    };
-    uint32_t cnt_[2][16];               // [code][length]; slot 0 of a code: its longest length
-    uint16_t first_[2][16], offs_[2][16], run[16];
-    uint16_t sorted_lit[288], sorted_dist[32];
-    uint8_t  lens[320 + 8];
-    __device__ __forceinline__ uint32_t *cnt(int which) { return which == kCodeCl ? h.cnt : cnt_[which]; }
-    __device__ __forceinline__ uint16_t *first(int which) { return which == kCodeCl ? h.first : first_[which]; }
-    __device__ __forceinline__ uint16_t *offs(int which) { return which == kCodeCl ? h.offs : offs_[which]; }
-    __device__ __forceinline__ uint16_t *cl() { return h.cl; }
-    __device__ __forceinline__ uint16_t *sorted_cl() { return h.sorted_cl; }
-    __device__ __forceinline__ uint8_t *cl_lens() { return h.cl_lens; }
-};
-constexpr int kSizesLitRoot = kLitRootStream, kSizesDistRoot = kDistRootStream;
-static_assert(sizeof(((SizesLds<kSizesDistRoot, kSizesLitRoot> *)nullptr)->h) <= sizeof(uint32_t) << kSizesDistRoot,
-              "the header's tables must fit the distance table's place");
-
-// The literal/length table's loop form.  The sizing pass never needs a literal's VALUE, so a literal's entry is its code length
-// alone (1 .. 15: "entry < 16" is the literal test and the entry is the shift), and a length symbol's entry carries its base
-// length and extra-bit count, as wide_distance's entries do: no arithmetic on the symbol in the loop.
-constexpr uint32_t kLitLength = 1u << 20, kLitEob = 1u << 21, kLitLong = 1u << 22, kLitBad = 1u << 23, kLitHalt = 1u << 24;
-__device__ __forceinline__ uint32_t wide_literal(uint32_t e) {            // e: a 16-bit entry
-    if (e == kLongMark) return kLitLong;
-    const uint32_t sym = e >> 4, nb = e & 15u;
-    if (sym < 256u) return nb;
-    if (sym == 256u) return kLitEob | nb;
-    if (sym > 285u) return kLitBad | nb;                                      // 286, 287 (inftrees.c:44-45), no code
-    uint32_t b = 0, x = 0;
-    length_of(sym - 257u, &b, &x);
-    return kLitLength | (b << 8) | (x << 4) | nb;
-}
 
 __device__ __forceinline__ IsRow load_row(const uint32_t *rows, uint32_t i) {
     return IsRow{rows[4 * i], rows[4 * i + 1], rows[4 * i + 2], rows[4 * i + 3]};
@@ -91,8 +48,8 @@ __global__ __launch_bounds__(64)
 void inflate_sizes_kernel(const InflateJobDev *__restrict__ given, const InflateJobDev *__restrict__ patched,
                           const uint32_t *__restrict__ head, uint32_t njobs, int format, int own_hist,
                           uint32_t *__restrict__ results) {
-    constexpr int kLR = kSizesLitRoot, kDR = kSizesDistRoot;
-    __shared__ SizesLds<kDR, kLR> L;
+    constexpr int kLitRoot = kLitRootStream, kDistRoot = kDistRootStream;
+    __shared__ SizesLds<kDistRoot, kLitRoot> L;
     const int lane = threadIdx.x;
     const uint32_t job = blockIdx.x;
     if (job >= njobs) return;
@@ -106,62 +63,17 @@ void inflate_sizes_kernel(const InflateJobDev *__restrict__ given, const Inflate
     const ZR_GLOBAL uint8_t *const in = (const ZR_GLOBAL uint8_t *)J.in;
     const uint32_t in_len = (uint32_t)J.in_len, hist = own_hist ? given[job].dict_len : J.dict_len;
 
-    // ---- compressed words: 64 per fetch, the next 64 prefetched (as the stream kernel) --------------------------------
-    const uint32_t lead = (uint32_t)((uintptr_t)J.in & 3u);
-    const ZR_GLOBAL uint32_t *const words = (const ZR_GLOBAL uint32_t *)(in - lead);
-    const uint32_t total_words = (lead + in_len + 3u) >> 2;
-    auto fetch = [&](uint32_t base) __attribute__((always_inline)) -> uint32_t {
-        const uint32_t k = base + (uint32_t)lane;
-        return k < total_words ? words[k] : 0u;
-    };
-    uint32_t cbase = 0, cur = 0, nxt = 0;
-    uint32_t wnext = 0;                                  // index of the next word to enter the bit buffer
-    unsigned long long hold = 0;
-    uint32_t cnt = 0;
-    auto append = [&]() __attribute__((always_inline)) {                                // cnt <= 32 on entry
-        const uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)cur, (int)(wnext - cbase));
-        hold |= (unsigned long long)w << cnt;
-        cnt += 32;
-        ++wnext;
-        if (wnext - cbase == 64) {
-            cbase += 64;
-            cur = nxt;
-            nxt = fetch(cbase + 64);
-        }
-    };
-    auto seek = [&](uint32_t byte_off) __attribute__((always_inline)) {                 // restart the bit buffer at a byte of the stream
-        const uint32_t a = lead + byte_off;
-        wnext = a >> 2;
-        cbase = wnext;
-        cur = fetch(cbase);
-        nxt = fetch(cbase + 64);
-        hold = 0;
-        cnt = 0;
-        append();
-        hold >>= 8 * (a & 3u);
-        cnt -= 8 * (a & 3u);
-    };
-    auto bit_pos = [&]() __attribute__((always_inline)) -> unsigned long long {         // stream bits consumed so far
-        return 32ull * wnext - 8ull * lead - cnt;
-    };
-    auto widen_distances = [&]() __attribute__((always_inline)) {
-        uint32_t w[(1 << kDR) / 64];
-#pragma unroll
-        for (int j = 0; j < (1 << kDR) / 64; ++j) w[j] = wide_distance(reinterpret_cast<const uint16_t *>(L.dist)[lane + 64 * j]);
-        wave_sync();
-#pragma unroll
-        for (int j = 0; j < (1 << kDR) / 64; ++j) L.dist[lane + 64 * j] = w[j];
-        wave_sync();
-    };
+#include "inflate_bits_body.h"
     auto widen_literals = [&]() __attribute__((always_inline)) {
-        uint32_t w[(1 << kLR) / 64];
+        uint32_t w[(1 << kLitRoot) / 64];
 #pragma unroll
-        for (int j = 0; j < (1 << kLR) / 64; ++j) w[j] = wide_literal(reinterpret_cast<const uint16_t *>(L.lit)[lane + 64 * j]);
+        for (int j = 0; j < (1 << kLitRoot) / 64; ++j) w[j] = wide_literal(reinterpret_cast<const uint16_t *>(L.lit)[lane + 64 * j]);
         wave_sync();
 #pragma unroll
-        for (int j = 0; j < (1 << kLR) / 64; ++j) L.lit[lane + 64 * j] = w[j];
+        for (int j = 0; j < (1 << kLitRoot) / 64; ++j) L.lit[lane + 64 * j] = w[j];
         wave_sync();
     };
+    auto tables_ready = [&]() __attribute__((always_inline)) { widen_literals(); widen_distances<kDistRoot>(L, lane); };
     seek(0);
 
     // `count`: what the decode's `op` would be.  `sure`: the count behind the last symbol whose bits were ALL input -- the zero
@@ -202,80 +114,7 @@ void inflate_sizes_kernel(const InflateJobDev *__restrict__ given, const Inflate
             seek(from + len);
             continue;
         }
-        if (type == 1) {
-            // fixed codes (RFC 1951 3.2.6, inflate.c:801-813): the same builder, from the fixed lengths
-            for (int s = lane; s < 288; s += 64) L.lens[s] = s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : 8;
-            if (lane < 32) L.lens[288 + lane] = 5;
-            wave_sync();
-            build_code(L, kCodeLit, L.lens, 288, kLR, reinterpret_cast<uint16_t *>(L.lit), L.sorted_lit, lane);
-            build_code(L, kCodeDist, L.lens + 288, 32, kDR, reinterpret_cast<uint16_t *>(L.dist), L.sorted_dist, lane);
-            widen_literals();
-            widen_distances();
-        } else {
-            // dynamic block header (inflate.c:814-917), read as the stream kernel reads it: the same bits consumed in
-            // front of every fault
-            if (cnt < 32) append();
-            const uint32_t nlen = ((uint32_t)hold & 31u) + 257u, ndist = ((uint32_t)(hold >> 5) & 31u) + 1u,
-                           ncode = ((uint32_t)(hold >> 10) & 15u) + 4u;
-            hold >>= 14;
-            cnt -= 14;
-            if (nlen > 286 || ndist > 30) { msg = kMsgTooMany; break; }
-            if (lane < 19) L.cl_lens()[lane] = 0;
-            wave_sync();
-            for (uint32_t i = 0; i < ncode; ++i) {
-                if (cnt < 32) append();
-                if (lane == 0) L.cl_lens()[kClOrder[i]] = (uint8_t)(hold & 7u);
-                hold >>= 3;
-                cnt -= 3;
-            }
-            wave_sync();
-            if (uni((uint32_t)build_code(L, kCodeCl, L.cl_lens(), 19, kClRoot, L.cl(), L.sorted_cl(), lane))) { msg = kMsgCodeLengthsSet; break; }
-            uint32_t have = 0;
-            while (have < nlen + ndist) {
-                if (cnt < 32) append();
-                const uint32_t e = uni(L.cl()[(uint32_t)hold & ((1u << kClRoot) - 1u)]);
-                const uint32_t nb = e & 15u, sym = e >> 4;
-                hold >>= nb;
-                cnt -= nb;
-                if (sym < 16) {
-                    if (lane == 0) L.lens[have] = (uint8_t)sym;
-                    ++have;
-                    continue;
-                }
-                uint32_t rep, val = 0;
-                if (sym == 16) {
-                    rep = 3u + ((uint32_t)hold & 3u);
-                    hold >>= 2;
-                    cnt -= 2;
-                    if (have == 0) { msg = kMsgBitRepeat; break; }
-                    wave_sync();
-                    val = uni(L.lens[have - 1]);
-                } else if (sym == 17) {
-                    rep = 3u + ((uint32_t)hold & 7u);
-                    hold >>= 3;
-                    cnt -= 3;
-                } else {
-                    rep = 11u + ((uint32_t)hold & 127u);
-                    hold >>= 7;
-                    cnt -= 7;
-                }
-                if (have + rep > nlen + ndist) { msg = kMsgBitRepeat; break; }
-                for (uint32_t k = (uint32_t)lane; k < rep; k += 64) L.lens[have + k] = (uint8_t)val;
-                have += rep;
-            }
-            if (msg != kMsgNone) break;
-            wave_sync();
-            if (bit_pos() > 8ull * in_len) { msg = kMsgStarved; break; }
-            if (uni(L.lens[256]) == 0) { msg = kMsgNoEob; break; }
-            if (uni((uint32_t)build_code(L, kCodeLit, L.lens, (int)nlen, kLR, reinterpret_cast<uint16_t *>(L.lit), L.sorted_lit, lane))) { msg = kMsgLitLenSet; break; }
-            if (uni((uint32_t)build_code(L, kCodeDist, L.lens + nlen, (int)ndist, kDR, reinterpret_cast<uint16_t *>(L.dist),
-                                         L.sorted_dist, lane))) {
-                msg = kMsgDistSet;
-                break;
-            }
-            widen_literals();
-            widen_distances();
-        }
+#include "inflate_block_tables_body.h"
 
         // ---- symbol loop: the decode half of inflate_fast (inffast_tpl.h:140-226) and nothing of its store half ------------
         // Every branch is wave-uniform and every loop has ONE exit (the stream kernel's lesson: anything else makes the compiler
@@ -299,7 +138,7 @@ void inflate_sizes_kernel(const InflateJobDev *__restrict__ given, const Inflate
                     if (wnext + 1u >= total_words) tail = halt = kLitHalt;            // the last word of input comes in
                     append();
                 }
-                e = uni(L.lit[(uint32_t)hold & ((1u << kLR) - 1u)]) | halt;
+                e = uni(L.lit[(uint32_t)hold & ((1u << kLitRoot) - 1u)]) | halt;
                 const uint32_t nb = e < 16u ? e : 0u;                                 // a literal: taken; anything else: looked at below
                 hold >>= nb;
                 cnt -= nb;
@@ -310,7 +149,7 @@ void inflate_sizes_kernel(const InflateJobDev *__restrict__ given, const Inflate
                 end = 2;
             } else {
                 e &= ~kLitHalt;
-                if (e == kLitLong) e = wide_literal(long_code(L, kCodeLit, kLR, L.sorted_lit, hold));
+                if (e == kLitLong) e = wide_literal(long_code(L, kCodeLit, kLitRoot, L.sorted_lit, hold));
                 const uint32_t nb = e & 15u;
                 if (e & kLitBad) {
                     msg = bit_pos() + nb > 8ull * in_len ? kMsgStarved : kMsgLitLenCode;  // (its bits must all be input)
@@ -328,8 +167,8 @@ void inflate_sizes_kernel(const InflateJobDev *__restrict__ given, const Inflate
                         hold >>= xb;
                         cnt -= xb;
                         if (cnt < 32) append();
-                        uint32_t d = uni(L.dist[(uint32_t)hold & ((1u << kDR) - 1u)]);
-                        if (d == kLongWide) d = wide_distance(long_code(L, kCodeDist, kDR, L.sorted_dist, hold));
+                        uint32_t d = uni(L.dist[(uint32_t)hold & ((1u << kDistRoot) - 1u)]);
+                        if (d == kLongWide) d = wide_distance(long_code(L, kCodeDist, kDistRoot, L.sorted_dist, hold));
                         if (d >= kBadWide) {
                             msg = bit_pos() + (d & 15u) > 8ull * in_len ? kMsgStarved : kMsgDistCode;
                             end = 2;
@@ -466,38 +305,21 @@ static int sizes_body(bool packed, int format, const zng_rocm_dict *dict, const 
         ZR_HIP(hipGetLastError());
         return ZNG_ROCM_OK;
     }
-    InflateJobDev *d_given = nullptr, *h_given = nullptr, *d_patched = nullptr;
-    uint32_t *d_words = nullptr, *d_sizing = d_results;
-    uint8_t *d_msg = nullptr;
-    Partial *d_part = nullptr;
-    if (int rc = scratch_reserve(ws, kScrInflateDevJobs, 2 * njobs * sizeof(InflateJobDev), false, (void **)&d_given)) return rc;
-    d_patched = d_given + njobs;
-    // head rows: 2 words per job; the packed call's check values: 2 more
-    if (int rc = scratch_reserve(ws, kScrFrameWords, njobs * (packed ? 4 : 2) * sizeof(uint32_t), false, (void **)&d_words)) return rc;
-    uint32_t *d_head = d_words, *d_checks = packed ? d_words + 2 * njobs : nullptr;
-    if (packed) {
+    uint32_t *d_sizing = d_results;
+    if (packed)
         if (int rc = scratch_reserve(ws, kScrSizes, njobs * 4 * sizeof(uint32_t), false, (void **)&d_sizing)) return rc;
-        if (int rc = scratch_reserve(ws, kScrCheckMessages, njobs * (sizeof(StreamArgs) + sizeof(FinalArgs)), false, (void **)&d_msg)) return rc;
-        if (int rc = scratch_reserve(ws, kScrCheckPartials, njobs * sizeof(Partial), false, (void **)&d_part)) return rc;
-    }
-    if (int rc = host_tables_acquire(ws)) return rc;
-    if (int rc = scratch_reserve(ws, kScrInflateDevJobsHost, njobs * sizeof(InflateJobDev), true, (void **)&h_given)) return rc;
-    for (size_t i = 0; i < njobs; ++i) {
-        const zng_rocm_inflate_dev_job &j = jobs[i];
-        h_given[i] = InflateJobDev{(const uint8_t *)j.in, nullptr, j.in_len, 0u, j.dict_len, 0u};
-    }
-    ZR_HIP(hipMemcpyAsync(d_given, h_given, njobs * sizeof(InflateJobDev), hipMemcpyHostToDevice, st));
-    if (int rc = host_tables_release(ws, st)) return rc;
-    if (int rc = launch_parse_header(format, dict, d_given, njobs, d_patched, d_head, st)) return rc;
-    if (int rc = launch_inflate_sizes(d_given, d_patched, d_head, njobs, format, format == 0 && !dict, d_sizing, st)) return rc;
+    GivenJobs g;
+    if (int rc = upload_given_jobs(ws, format, dict, jobs, njobs, false, packed, &g, st)) return rc;
+    if (int rc = launch_inflate_sizes(g.d_given, g.d_patched, g.d_head, njobs, format, format == 0 && !dict, d_sizing, st)) return rc;
     if (!packed) return ZNG_ROCM_OK;
     const dim3 grid((unsigned)((njobs + 255) / 256)), block(256);
     hipLaunchKernelGGL(sizes_place_kernel, dim3(1), dim3(1024), 0, st, d_sizing, (uint32_t)njobs, align, d_off);
     ZR_HIP(hipGetLastError());
     hipLaunchKernelGGL(sizes_patch_kernel, grid, block, 0, st, d_sizing, d_off, (uint32_t)njobs, d_dst, (unsigned long long)dst_cap,
-                       d_patched);
+                       g.d_patched);
     ZR_HIP(hipGetLastError());
-    if (int rc = uncompress_patched_device(format, dict, d_given, d_patched, d_head, d_checks, d_msg, d_part, njobs, d_results, st))
+    if (int rc = uncompress_patched_device(format, dict, g.d_given, g.d_patched, g.d_head, g.d_checks, g.d_msg, g.d_part, njobs,
+                                           d_results, st))
         return rc;
     hipLaunchKernelGGL(sizes_final_kernel, grid, block, 0, st, d_sizing, d_off, (uint32_t)njobs, (unsigned long long)dst_cap,
                        d_results);
@@ -505,7 +327,7 @@ static int sizes_body(bool packed, int format, const zng_rocm_dict *dict, const 
     return ZNG_ROCM_OK;
 }
 
-// the refusals in inflate_sizes_plan.h's order, then the device: 0 = go on
+// the refusals in inflate_sizes_plan.h's order, then the device (the dictionary's, or the context of zng_rocm_init): 0 = go on
 static int sizes_enter(bool packed, int format, const zng_rocm_dict *dict, const zng_rocm_inflate_dev_job *jobs, size_t njobs,
                        const void *d_dst, size_t dst_cap, uint32_t align, const void *d_offsets, const void *d_results) {
     const int rc = packed ? is_packed_call_check(format, dict != nullptr, jobs, njobs, d_dst, dst_cap, align, d_offsets, d_results)
@@ -522,6 +344,12 @@ static int sizes_enter(bool packed, int format, const zng_rocm_dict *dict, const
                   "dictionary object, a wrapped format or a packed destination", (unsigned long long)bad);
         return jrc;
     }
+    if (!packed && !njobs) return ZNG_ROCM_OK;           // (the caller returns: nothing to do needs no device)
+    if (dict) return dict_usable(dict);
+    if (!ctx()) {
+        set_error("zng_rocm_init() has not succeeded");
+        return ZNG_ROCM_ENODEV;
+    }
     return ZNG_ROCM_OK;
 }
 
@@ -535,12 +363,6 @@ int zng_rocm_inflate_sizes_dev(int format, const zng_rocm_dict *dict, const zng_
                                uint32_t *d_results, void *stream) {
     if (int rc = sizes_enter(false, format, dict, jobs, njobs, nullptr, 0, 0, nullptr, d_results)) return rc;
     if (!njobs) return ZNG_ROCM_OK;
-    if (dict) {
-        if (int rc = dict_usable(dict)) return rc;
-    } else if (!ctx()) {
-        set_error("zng_rocm_init() has not succeeded");
-        return ZNG_ROCM_ENODEV;
-    }
     return sizes_body(false, format, dict, jobs, njobs, nullptr, 0, 0, nullptr, d_results, (hipStream_t)stream);
 }
 
@@ -548,12 +370,6 @@ int zng_rocm_uncompress_packed_dev(int format, const zng_rocm_dict *dict, const 
                                    uint8_t *d_dst, size_t dst_cap, uint32_t align, uint64_t *d_offsets, uint32_t *d_results,
                                    void *stream) {
     if (int rc = sizes_enter(true, format, dict, jobs, njobs, d_dst, dst_cap, align, d_offsets, d_results)) return rc;
-    if (dict) {
-        if (int rc = dict_usable(dict)) return rc;
-    } else if (!ctx()) {
-        set_error("zng_rocm_init() has not succeeded");
-        return ZNG_ROCM_ENODEV;
-    }
     return sizes_body(true, format, dict, jobs, njobs, d_dst, dst_cap, align, d_offsets, d_results, (hipStream_t)stream);
 }
 

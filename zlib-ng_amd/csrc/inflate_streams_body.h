@@ -7,6 +7,8 @@
 //                              decode starts spans[job].start_bit bits (0..7) into the first byte, and reaching out_cap is the
 //                              expected end (inflate_streams_span_kernel: one span of an indexed stream)
 //   jobs, njobs, results, starts, marks, hist_end, spans   the kernel's arguments (null where a form has none)
+// It includes two more pieces of program text, which the sizing kernel (inflate_sizes.hip) includes too: the word fetcher and
+// bit buffer (inflate_bits_body.h) and the tables of a fixed-code or dynamic block (inflate_block_tables_body.h).
 // Textual sharing keeps every existing instantiation the very function it was: same arguments, same attributes, same code.
 // The fast loop leaves for any source in front of the stream (ZR_INFLATE_BEFORE_STREAM); the general copy path is the one
 // place that reads such a byte, and it reads hist_end[sp] instead of out[sp] in the dictionary form.
@@ -32,44 +34,7 @@
     if (PART && out_cap == 0) return;                    // a part whose earlier result stands (inflate_large.hip reruns only some)
     const uint32_t a0 = (uint32_t)((uintptr_t)J.out & 15u) / (uint32_t)sizeof(T);   // ring slot of position p is (p + a0) & M
 
-    // ---- compressed words: 64 per fetch, the next 64 prefetched -------------------------------------------------
-    const uint32_t lead = (uint32_t)((uintptr_t)J.in & 3u);
-    const ZR_GLOBAL uint32_t *const words = (const ZR_GLOBAL uint32_t *)(in - lead);
-    const uint32_t total_words = (lead + in_len + 3u) >> 2;
-    auto fetch = [&](uint32_t base) __attribute__((always_inline)) -> uint32_t {
-        const uint32_t k = base + (uint32_t)lane;
-        return k < total_words ? words[k] : 0u;
-    };
-    uint32_t cbase = 0, cur = 0, nxt = 0;
-    uint32_t wnext = 0;                                  // index of the next word to enter the bit buffer
-    unsigned long long hold = 0;
-    uint32_t cnt = 0;
-    auto append = [&]() __attribute__((always_inline)) {                                // cnt <= 32 on entry
-        const uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)cur, (int)(wnext - cbase));
-        hold |= (unsigned long long)w << cnt;
-        cnt += 32;
-        ++wnext;
-        if (wnext - cbase == 64) {
-            cbase += 64;
-            cur = nxt;
-            nxt = fetch(cbase + 64);
-        }
-    };
-    auto seek = [&](uint32_t byte_off) __attribute__((always_inline)) {                 // restart the bit buffer at a byte of the stream
-        const uint32_t a = lead + byte_off;
-        wnext = a >> 2;
-        cbase = wnext;
-        cur = fetch(cbase);
-        nxt = fetch(cbase + 64);
-        hold = 0;
-        cnt = 0;
-        append();
-        hold >>= 8 * (a & 3u);
-        cnt -= 8 * (a & 3u);
-    };
-    auto bit_pos = [&]() __attribute__((always_inline)) -> unsigned long long {         // stream bits consumed so far
-        return 32ull * wnext - 8ull * lead - cnt;
-    };
+#include "inflate_bits_body.h"
     uint32_t reach = 0, hit = 0xffffffffu;               // PART: furthest source in front of the part; the start it ended on
     // SUB: the part's own key; the identity of the block being decoded (1 fixed, H + 2 dynamic) and the next sub-start of
     // that identity ahead (its bit, its index; ~0 = none); handed off; a fixed-code sub-part still in its first block
@@ -170,15 +135,7 @@
     };
 
     // the 16-bit distance entries the builder left in the first half of L.dist -> wide entries, through registers
-    auto widen_distances = [&]() __attribute__((always_inline)) {
-        uint32_t w[(1 << kDistRoot) / 64];
-#pragma unroll
-        for (int j = 0; j < (1 << kDistRoot) / 64; ++j) w[j] = wide_distance(reinterpret_cast<const uint16_t *>(L.dist)[lane + 64 * j]);
-        wave_sync();
-#pragma unroll
-        for (int j = 0; j < (1 << kDistRoot) / 64; ++j) L.dist[lane + 64 * j] = w[j];
-        wave_sync();
-    };
+    auto tables_ready = [&]() __attribute__((always_inline)) { widen_distances<kDistRoot>(L, lane); };
 
     // (Every lambda above is always_inline: one that is called out of line gets its captures through the stack -- the
     // whole bit-parse state would live in scratch memory.)
@@ -301,79 +258,7 @@
             if (PART && !last && block_end_stop()) break;
             continue;
         }
-        if (type == 1) {
-            // fixed codes (RFC 1951 3.2.6, inflate.c:801-813): the same builder, from the fixed lengths
-            for (int s = lane; s < 288; s += 64) L.lens[s] = s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : 8;
-            if (lane < 32) L.lens[288 + lane] = 5;
-            wave_sync();
-            build_code(L, kCodeLit, L.lens, 288, kLitRoot, L.lit, L.sorted_lit, lane);
-            build_code(L, kCodeDist, L.lens + 288, 32, kDistRoot, reinterpret_cast<uint16_t *>(L.dist), L.sorted_dist, lane);
-            widen_distances();
-        } else {
-            // dynamic block header (inflate.c:814-917)
-            if (cnt < 32) append();
-            const uint32_t nlen = ((uint32_t)hold & 31u) + 257u, ndist = ((uint32_t)(hold >> 5) & 31u) + 1u,
-                           ncode = ((uint32_t)(hold >> 10) & 15u) + 4u;
-            hold >>= 14;
-            cnt -= 14;
-            if (nlen > 286 || ndist > 30) { msg = kMsgTooMany; break; }
-            if (lane < 19) L.cl_lens()[lane] = 0;
-            wave_sync();
-            for (uint32_t i = 0; i < ncode; ++i) {
-                if (cnt < 32) append();
-                if (lane == 0) L.cl_lens()[kClOrder[i]] = (uint8_t)(hold & 7u);
-                hold >>= 3;
-                cnt -= 3;
-            }
-            wave_sync();
-            if (uni((uint32_t)build_code(L, kCodeCl, L.cl_lens(), 19, kClRoot, L.cl(), L.sorted_cl(), lane))) { msg = kMsgCodeLengthsSet; break; }
-            uint32_t have = 0;
-            while (have < nlen + ndist) {
-                if (cnt < 32) append();
-                const uint32_t e = uni(L.cl()[(uint32_t)hold & ((1u << kClRoot) - 1u)]);
-                // an empty code-length code yields one-bit entries of value 0: each reads as length 0
-                // (inftrees.c:114-122 + inflate.c:846-849)
-                const uint32_t nb = e & 15u, sym = e >> 4;
-                hold >>= nb;
-                cnt -= nb;
-                if (sym < 16) {
-                    if (lane == 0) L.lens[ZR_IDX(have, 320)] = (uint8_t)sym;
-                    ++have;
-                    continue;
-                }
-                uint32_t rep, val = 0;
-                if (sym == 16) {
-                    rep = 3u + ((uint32_t)hold & 3u);                 // NEEDBITS(here.bits + 2) comes first (inflate.c:856-864):
-                    hold >>= 2;                                       // at the end of a truncated stream the answer is
-                    cnt -= 2;                                         // "input ended", not this error
-                    if (have == 0) { msg = kMsgBitRepeat; break; }
-                    wave_sync();
-                    val = uni(L.lens[have - 1]);
-                } else if (sym == 17) {
-                    rep = 3u + ((uint32_t)hold & 7u);
-                    hold >>= 3;
-                    cnt -= 3;
-                } else {
-                    rep = 11u + ((uint32_t)hold & 127u);
-                    hold >>= 7;
-                    cnt -= 7;
-                }
-                if (have + rep > nlen + ndist) { msg = kMsgBitRepeat; break; }
-                for (uint32_t k = (uint32_t)lane; k < rep; k += 64) L.lens[ZR_IDX(have + k, 320)] = (uint8_t)val;
-                have += rep;
-            }
-            if (msg != kMsgNone) break;
-            wave_sync();
-            if (bit_pos() > 8ull * in_len) { msg = kMsgStarved; break; }
-            if (uni(L.lens[256]) == 0) { msg = kMsgNoEob; break; }
-            if (uni((uint32_t)build_code(L, kCodeLit, L.lens, (int)nlen, kLitRoot, L.lit, L.sorted_lit, lane))) { msg = kMsgLitLenSet; break; }
-            if (uni((uint32_t)build_code(L, kCodeDist, L.lens + nlen, (int)ndist, kDistRoot, reinterpret_cast<uint16_t *>(L.dist),
-                                         L.sorted_dist, lane))) {
-                msg = kMsgDistSet;
-                break;
-            }
-            widen_distances();
-        }
+#include "inflate_block_tables_body.h"
         if constexpr (SUB) {
             cur_id = type == 1 ? 1ull : hdr_bit + 2ull;
             if (entering) {                              // into the block at the sub-start's bit

@@ -1,7 +1,8 @@
 // inflate_tables.h -- what the device inflaters share in front of their symbol loops (inflate_dev.hip's stream, part and sync
 // kernels, inflate_sizes.hip's sizing kernel): the 16-bit table entry and its marks, the LDS layouts of a wave's tables, the
-// base values and extra bits of the length and distance symbols, the wide distance entry, and the wavefront's canonical-code
-// builder with the lookup of a code longer than the root.  Device code; include it inside a HIP translation unit.
+// base values and extra bits of the length and distance symbols, the wide distance and literal/length entries, and the
+// wavefront's canonical-code builder with the lookup of a code longer than the root.  Device code; include it inside a HIP
+// translation unit.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -52,18 +53,16 @@ struct InflateLdsStream {
     __device__ __forceinline__ uint16_t *sorted_cl() { return sorted_cl_; }
     __device__ __forceinline__ uint8_t *cl_lens() { return cl_lens_; }
 };
-// Parts, when there are many (16-bit symbols: the ring alone is 8 KiB): LDS is what limits how many decode at once, so
-// the layout is packed.
+// The packed layout: LDS is what limits how many wavefronts decode at once.
 // The code-length code -- root table, sorted symbols, counts, the 19 lengths -- only lives while a dynamic header is read,
 // and the distance table is only built when that is over: one place for both; the builder's first-code and offset words
-// are 16 bits.  12.2 KiB: a 13th part per CU (part kernel of the cfg3 stream 6.0 -> 5.25 ms).  (The same layout for
-// whole streams cost their kernel 5 % -- 42.1 -> 39.8 GB/s on the level-1 class's streams, with the LDS size padded
-// back to what it was -- so they keep theirs.)
-template <int RING, typename T, int DR, int LR>
-struct InflateLdsPart {
-    uint16_t lit[1 << LR];
+// are 16 bits.  LIT: the literal/length table's element, the builder's 16-bit entry or a wide one (wide_literal: the
+// builder's entries then lie in the first half).
+template <typename LIT, int DR, int LR>
+struct InflateLdsPacked {
+    LIT lit[1 << LR];
     union {
-        uint32_t dist[1 << DR];
+        uint32_t dist[1 << DR];             // wide entries (wide_distance)
         struct {
             uint16_t cl[1 << kClRoot];
             uint16_t sorted_cl[32];
@@ -76,7 +75,6 @@ struct InflateLdsPart {
     uint16_t first_[2][16], offs_[2][16], run[16];
     uint16_t sorted_lit[288], sorted_dist[32];
     uint8_t  lens[320 + 8];
-    T        ring[RING] __attribute__((aligned(16)));
     __device__ __forceinline__ uint32_t *cnt(int which) { return which == kCodeCl ? h.cnt : cnt_[which]; }
     __device__ __forceinline__ uint16_t *first(int which) { return which == kCodeCl ? h.first : first_[which]; }
     __device__ __forceinline__ uint16_t *offs(int which) { return which == kCodeCl ? h.offs : offs_[which]; }
@@ -84,8 +82,20 @@ struct InflateLdsPart {
     __device__ __forceinline__ uint16_t *sorted_cl() { return h.sorted_cl; }
     __device__ __forceinline__ uint8_t *cl_lens() { return h.cl_lens; }
 };
+// Parts, when there are many (16-bit symbols: the ring alone is 8 KiB): the packed tables and the ring.  12.2 KiB: a 13th
+// part per CU (part kernel of the cfg3 stream 6.0 -> 5.25 ms).  (The same layout for whole streams cost their kernel 5 %
+// -- 42.1 -> 39.8 GB/s on the level-1 class's streams, with the LDS size padded back to what it was -- so they keep theirs.)
+template <int RING, typename T, int DR, int LR>
+struct InflateLdsPart : InflateLdsPacked<uint16_t, DR, LR> {
+    T        ring[RING] __attribute__((aligned(16)));
+};
+// The sizing pass (inflate_sizes.hip): the packed tables with wide literal/length entries and no ring, 7.2 KiB against the
+// stream decoder's 9.9 KiB.
+template <int DR, int LR>
+using SizesLds = InflateLdsPacked<uint32_t, DR, LR>;
 static_assert(sizeof(((InflateLdsPart<4096, uint16_t, 8, 10> *)nullptr)->h) <= sizeof(uint32_t) << 8, "the header's tables must fit the distance table's place");
-
+static_assert(sizeof(((SizesLds<kDistRootStream, kLitRootStream> *)nullptr)->h) <= sizeof(uint32_t) << kDistRootStream,
+              "the header's tables must fit the distance table's place");
 
 // base values / extra bits of the length and distance symbols (RFC 1951 3.2.5; inftrees.c:38-49 hold the same numbers)
 __device__ __forceinline__ void length_of(uint32_t k, uint32_t *base, uint32_t *extra) {     // k = symbol - 257, 0..28
@@ -97,6 +107,14 @@ __device__ __forceinline__ void distance_of(uint32_t k, uint32_t *base, uint32_t
     if (k < 4) { *base = 1 + k; *extra = 0; }
     else { const uint32_t e = (k - 2) >> 1; *extra = e; *base = 1 + ((2 + (k & 1)) << e); }
 }
+
+__device__ __forceinline__ void wave_sync() {            // LDS written by some lanes is read by others of the same wave
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+typedef uint32_t u32x4_v __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 
 // the distance table's decode-loop form: base and extra-bit count ride in the entry (the loop is scalar-issue bound and
 // the arithmetic of distance_of is 11 scalar instructions per match; 1 KiB more LDS per stream)
@@ -113,13 +131,32 @@ __device__ __forceinline__ uint32_t wide_distance(uint32_t e) {           // e: 
     return (e & 15u) | (x << 4) | (b << 8);
 }
 
-__device__ __forceinline__ void wave_sync() {            // LDS written by some lanes is read by others of the same wave
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+// the 16-bit distance entries the builder left in the first half of L.dist -> wide entries, through registers
+template <int DR, typename LDS>
+__device__ __forceinline__ void widen_distances(LDS &L, int lane) {
+    uint32_t w[(1 << DR) / 64];
+#pragma unroll
+    for (int j = 0; j < (1 << DR) / 64; ++j) w[j] = wide_distance(reinterpret_cast<const uint16_t *>(L.dist)[lane + 64 * j]);
+    wave_sync();
+#pragma unroll
+    for (int j = 0; j < (1 << DR) / 64; ++j) L.dist[lane + 64 * j] = w[j];
+    wave_sync();
 }
-typedef uint32_t u32x4_v __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+
+// The literal/length table's loop form in the sizing pass.  It never needs a literal's VALUE, so a literal's entry is its code
+// length alone (1 .. 15: "entry < 16" is the literal test and the entry is the shift), and a length symbol's entry carries its
+// base length and extra-bit count, as wide_distance's entries do: no arithmetic on the symbol in the loop.
+constexpr uint32_t kLitLength = 1u << 20, kLitEob = 1u << 21, kLitLong = 1u << 22, kLitBad = 1u << 23, kLitHalt = 1u << 24;
+__device__ __forceinline__ uint32_t wide_literal(uint32_t e) {            // e: a 16-bit entry
+    if (e == kLongMark) return kLitLong;
+    const uint32_t sym = e >> 4, nb = e & 15u;
+    if (sym < 256u) return nb;
+    if (sym == 256u) return kLitEob | nb;
+    if (sym > 285u) return kLitBad | nb;                                      // 286, 287 (inftrees.c:44-45), no code
+    uint32_t b = 0, x = 0;
+    length_of(sym - 257u, &b, &x);
+    return kLitLength | (b << 8) | (x << 4) | nb;
+}
 
 // Canonical code from `n` code lengths (inftrees.c:32-297 re-thought for a wavefront): per-length counts, the
 // over-subscribed / incomplete checks of inftrees.c:104-137, symbols sorted by (length, symbol), and the root-bit
