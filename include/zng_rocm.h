@@ -754,6 +754,42 @@ int  zng_rocm_uncompress_large_streams_dev(int format, zng_rocm_inflate_large_jo
 int  zng_rocm_uncompress_large_dev(int format, const uint8_t *d_src, size_t src_len, const uint8_t *d_dict, uint32_t dict_len,
                                    uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, size_t *in_used, size_t piece_bytes,
                                    uint32_t flags, void *stream);
+/* The plaintext SIZE of large device-resident streams, without decoding them: what a caller needs before it can hand any of
+ * the large inflaters a destination -- raw deflate and zlib do not record the length, gzip records it mod 2^32 only.
+ * One finder pass, ONE launch of a counting part kernel (one wavefront per part; it stores nothing but eight result words per
+ * part) and the chain walk of the decode: no part slots, no rerun of parts above a ratio of 64, no symbol array, no resolve,
+ * and no byte of the stream comes to the host.  Device scratch is the finder's tables (about src_len / 7) and under 100 bytes
+ * per part, against the decode's 128 bytes per compressed byte.  A stream the finder does not cut (below 128 KiB, fewer
+ * than four starts, more parts than a launch takes) is ONE part of the same launch, its whole length walked by one
+ * wavefront; a stream with anything irregular on its chain is sized once more on the device, whole, by one wavefront of a
+ * second kernel that gives the decoder's verdict, message and consumed bytes.
+ *   format    0 raw: d_dict / dict_len (window_len) is the LENGTH (<= 32768) of the history the caller will put in front; its
+ *             bytes are not looked at and the pointer may be NULL.  1 zlib, 2 gzip: the whole member with its wrapper; the
+ *             header is parsed and FDICT / DICTID judged as zng_rocm_uncompress_large_dev does (the dictionary's bytes are
+ *             needed for the DICTID; gzip with a dictionary: ZNG_ROCM_EINVAL); the 4 / 8 trailer bytes must be present and
+ *             are counted, but the check value and ISIZE are NOT compared -- there is no plaintext to check, so a member with
+ *             a damaged trailer still answers 1 (as in zng_rocm_inflate_sizes_dev)
+ *   results   what zng_rocm_inflate_sizes_dev's row says of the same stream and history length, with a 64-bit count that
+ *             does not saturate: 1 with the plaintext length and the bytes used; every header refusal, 2 (Z_NEED_DICT), the
+ *             DICTID mismatch (-3, no text), every data error with its text and consumed bytes, truncation (-5; out_len then
+ *             the bytes of the symbols whose bits were all input) -- header verdicts as zng_rocm_uncompress_large_dev lists
+ *             them.  The single call: *out_len, *in_used, the return value, a data error's text in zng_rocm_last_error().
+ *             The batch: per job status / out_len / in_used / msg / parts, subparts 0; d_dst / dst_cap are not looked at and
+ *             nothing is written there.  The plaintext may be of any size.
+ *   counters  zng_rocm_inflate_large_last_parts() (the single call) and `parts` (the batch): the parts on the chain -- the
+ *             decode's count for the same stream; 1: the stream was not cut; 0: the second kernel sized it whole, as for
+ *             every stream that is not a valid one.  zng_rocm_inflate_large_last_rounds() / _last_part_launches(): as for
+ *             zng_rocm_inflate_large_streams_dev, with exactly one launch of the counting part kernel per round
+ *   refusals  ZNG_ROCM_EINVAL before anything is launched or written: a format outside 0 .. 2; any flag bit (there is no
+ *             ZNG_ROCM_INFLATE_SUBBLOCK form; zng_rocm_last_error() names the bits); dict_len / window_len above 32768; a
+ *             null d_src with a length; a null out_len or in_used; round_bytes outside zng_rocm_inflate_large_streams_dev's
+ *             range; src_len of 2 GiB and more (bit positions must fit the part tables; sizing in pieces is a later step).
+ *             An accepted call before zng_rocm_init: ZNG_ROCM_ENODEV, nothing written.
+ * Both synchronous.  The batch returns 0 or the first device error; a stream's own trouble is its job's status alone. */
+int  zng_rocm_uncompress_large_size_dev(int format, const uint8_t *d_src, size_t src_len, const uint8_t *d_dict, uint32_t dict_len,
+                                        uint64_t *out_len, size_t *in_used, uint32_t flags, void *stream);
+int  zng_rocm_uncompress_large_sizes_dev(int format, zng_rocm_inflate_large_job *jobs, size_t njobs, size_t round_bytes,
+                                         uint32_t flags, void *stream);
 /* The wrapper alone, on HOST bytes: the same rules as the header kernel of the two calls above (one function for both),
  * no device needed -- works before zng_rocm_init and without a GPU.  Returns 0 (header complete and accepted; info filled),
  * 2 (accepted zlib header with FDICT: info->dictid is the Adler-32 the dictionary must have, header_len 6), -3 with the

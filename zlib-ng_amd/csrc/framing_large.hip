@@ -26,6 +26,7 @@
 #include "framing_parse.h"
 #include "inflate_dev.h"
 #include "inflate_large_limits.h"
+#include "inflate_large_size_plan.h"
 #include "gf2.h"
 
 namespace zr {
@@ -517,6 +518,68 @@ int uncompress_large(int format, zng_rocm_inflate_large_job *jobs, size_t njobs,
     return ZNG_ROCM_OK;
 }
 
+// The plaintext SIZES of the members `jobs` (zng_rocm_uncompress_large_size_dev / _sizes_dev): header phase and verdicts as
+// uncompress_large, the counting pass of inflate_large.hip on the payloads, and the trailer's 4 / 8 bytes present and counted
+// but not compared (ls_member_tail) -- there is no plaintext whose check value could be taken.
+int uncompress_large_sizes(int format, zng_rocm_inflate_large_job *jobs, size_t njobs, size_t round_bytes, bool single, hipStream_t st) {
+    if (format == 0) return inflate_large_sizes_raw(jobs, njobs, round_bytes, single, st);
+    DeviceGuard dev;
+    Workspace *ws = workspace_for(st);
+    if (!ws) return ZNG_ROCM_ENOMEM;
+    std::vector<WrapperHead> heads;
+    std::vector<uint32_t> dict_adler;
+    inflate_large_reset_counters();
+    if (int rc = header_phase(format, jobs, njobs, ws, st, heads, dict_adler)) return rc;
+    std::vector<zng_rocm_inflate_large_job> inner;
+    std::vector<size_t> inner_of;
+    for (size_t i = 0; i < njobs; ++i) {
+        uint32_t wl = 0;
+        if (!header_verdict(heads[i], jobs[i], dict_adler[i], &jobs[i], &wl)) continue;
+        zng_rocm_inflate_large_job p = jobs[i];
+        p.d_src = jobs[i].d_src + heads[i].header_len;
+        p.src_len = jobs[i].src_len - (size_t)heads[i].header_len;
+        p.d_window = wl ? jobs[i].d_window : nullptr;
+        p.window_len = wl;
+        inner.push_back(p);
+        inner_of.push_back(i);
+    }
+    const int rc = inflate_large_sizes_raw(inner.data(), inner.size(), round_bytes, single, st);
+    for (size_t k = 0; k < inner.size(); ++k) {
+        const zng_rocm_inflate_large_job &p = inner[k];
+        zng_rocm_inflate_large_job &j = jobs[inner_of[k]];
+        const uint64_t hl = heads[inner_of[k]].header_len;
+        j.status = p.status;
+        j.out_len = p.out_len;
+        j.in_used = p.in_used + (p.status == 1 || p.status == -3 || p.status == -5 ? (size_t)hl : 0);
+        j.msg = p.msg;
+        j.parts = p.parts;
+        j.subparts = 0;
+        if (p.status == 1) {
+            uint64_t used = 0;
+            ls_member_tail(format, hl + p.in_used, j.src_len, &j.status, &used);
+            j.in_used = (size_t)used;
+        }
+    }
+    return rc;
+}
+
+// the refusals of both sizing calls that no job is looked at for: 0 = go on
+int sizes_call_check(const char *who, int format, uint32_t flags, size_t round_bytes) {
+    if (format < 0 || format > 2) {
+        set_error("%s: format %d is none of 0 (raw), 1 (zlib), 2 (gzip)", who, format);
+        return ZNG_ROCM_EINVAL;
+    }
+    if (flags) {
+        set_error("%s: flag bits 0x%x (the counting pass has no SUBBLOCK form and takes no flags)", who, flags);
+        return ZNG_ROCM_EINVAL;
+    }
+    if (!ls_round_ok(round_bytes)) {
+        set_error("%s: round_bytes %zu outside %zu .. 2 GiB", who, round_bytes, kRoundMin);
+        return ZNG_ROCM_EINVAL;
+    }
+    return ZNG_ROCM_OK;
+}
+
 }  // namespace
 
 }  // namespace zr
@@ -599,6 +662,47 @@ int zng_rocm_uncompress_large_streams_dev(int format, zng_rocm_inflate_large_job
     }
     if (!njobs) return ZNG_ROCM_OK;
     return uncompress_large(format, jobs, njobs, false, round_bytes, flags, (hipStream_t)stream);
+}
+
+int zng_rocm_uncompress_large_sizes_dev(int format, zng_rocm_inflate_large_job *jobs, size_t njobs, size_t round_bytes,
+                                        uint32_t flags, void *stream) {
+    static const char who[] = "zng_rocm_uncompress_large_sizes_dev";
+    if (int rc = sizes_call_check(who, format, flags, round_bytes)) return rc;
+    if ((njobs && !jobs) || njobs > 0x7fffffffull) return ZNG_ROCM_EINVAL;
+    for (size_t i = 0; i < njobs; ++i)
+        if (!ls_job_ok(format, jobs[i].d_src, jobs[i].src_len, jobs[i].d_window, jobs[i].window_len)) {
+            set_error("%s: job %zu: a null d_src with a length, a stream of 2 GiB and more, window_len above 32768, a zlib "
+                      "dictionary without its bytes, or a gzip member with a dictionary", who, i);
+            return ZNG_ROCM_EINVAL;
+        }
+    if (!ctx()) {
+        set_error("zng_rocm_init() has not succeeded");
+        return ZNG_ROCM_ENODEV;
+    }
+    if (!njobs) return ZNG_ROCM_OK;
+    return uncompress_large_sizes(format, jobs, njobs, round_bytes, false, (hipStream_t)stream);
+}
+
+int zng_rocm_uncompress_large_size_dev(int format, const uint8_t *d_src, size_t src_len, const uint8_t *d_dict, uint32_t dict_len,
+                                       uint64_t *out_len, size_t *in_used, uint32_t flags, void *stream) {
+    static const char who[] = "zng_rocm_uncompress_large_size_dev";
+    if (int rc = sizes_call_check(who, format, flags, 0)) return rc;
+    if (!out_len || !in_used || !ls_job_ok(format, d_src, src_len, d_dict, dict_len)) {
+        set_error("%s: a null out_len or in_used, a null d_src with a length, a stream of 2 GiB and more, dict_len above 32768, a "
+                  "zlib dictionary without its bytes, or a gzip member with a dictionary", who);
+        return ZNG_ROCM_EINVAL;
+    }
+    if (!ctx()) {
+        set_error("zng_rocm_init() has not succeeded");
+        return ZNG_ROCM_ENODEV;
+    }
+    zng_rocm_inflate_large_job job = {d_src, src_len, d_dict, dict_len, nullptr, 0, 0, 0, 0, nullptr, 0, 0};
+    const int rc = uncompress_large_sizes(format, &job, 1, 0, true, (hipStream_t)stream);
+    if (rc != ZNG_ROCM_OK) return rc;
+    *out_len = job.out_len;
+    *in_used = job.in_used;
+    if (job.status == -3 && job.msg) set_error("%s", job.msg);
+    return job.status;
 }
 
 int zng_rocm_uncompress_large_dev(int format, const uint8_t *d_src, size_t src_len, const uint8_t *d_dict, uint32_t dict_len,

@@ -31,6 +31,13 @@ int launch_inflate_streams_span_device(const InflateJobDev *d_jobs, size_t njobs
 int launch_inflate_parts_device(const InflateJobDev *d_jobs, size_t njobs, uint32_t *d_results, const unsigned long long *d_starts,
                                 bool many, hipStream_t stream, uint32_t *d_marks = nullptr, uint32_t *d_side = nullptr);
 
+// the counting forms (inflate_large_size.hip): the parts of large streams, one wavefront each, no output -- d_jobs as above
+// (out / out_cap not looked at), 8 result words per part; and whole streams, one wavefront each, 8 words per stream
+// (inflate_large_size_plan.h: ls_part_count, ls_stream_row)
+int launch_inflate_size_parts_device(const InflateJobDev *d_jobs, size_t njobs, const unsigned long long *d_starts, uint32_t *d_results,
+                                     hipStream_t stream);
+int launch_inflate_size_streams_device(const InflateJobDev *d_jobs, size_t njobs, uint32_t *d_results, hipStream_t stream);
+
 // the sync kernel over a table of regions (SubRegionDev: inflate_dev_types.h)
 int launch_subblock_sync(const uint8_t *d_src, size_t src_len, const SubRegionDev *d_regions, size_t nregions,
                          unsigned long long *d_bit, unsigned long long *d_key, hipStream_t stream);
@@ -62,6 +69,8 @@ int inflate_large_device_only(const uint8_t *d_src, size_t src_len, const uint8_
 int inflate_large_blocks_device_only(const uint8_t *d_src, size_t src_len, unsigned start_bit, const uint8_t *d_window,
                                      uint32_t window_len, uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, uint64_t *end_bit,
                                      int *final, hipStream_t st);
+// the plaintext sizes of raw streams by the counting pass (zng_rocm_uncompress_large_size_dev / _sizes_dev, framing_large.hip)
+int inflate_large_sizes_raw(zng_rocm_inflate_large_job *jobs, size_t njobs, size_t round_bytes, bool single, hipStream_t st);
 // The block starts a pieces call meets, for zng_rocm_inflate_index_build_dev (inflate_index.hip): while the calling thread has
 // a sink set, inflate_pieces_call appends {bit of its d_src, offset in its output} of every genuine part that begins at a
 // block start and of every block start it establishes between pieces, and framing_large.hip notes the wrapper header's

@@ -47,6 +47,7 @@
 #include "context.h"
 #include "deflate_dev.h"
 #include "inflate_dev.h"
+#include "inflate_large_size_plan.h"
 #include "inflate_threads.h"
 
 namespace zr {
@@ -548,6 +549,8 @@ struct PassStream {
     int            status = 0;                            // 1: chain.produced bytes are at d_dst; -5: they do not fit dst_cap and
                                                           // nothing was written (the chain's counts hold either way)
     Chain          chain;                                 // parts: chain.copies.size(), subparts: chain.subparts
+    size_t         counted_parts = 0;                     // the counting mode: genuine parts (there are no copies); chain holds
+                                                          // produced / end_bit / final alone
     size_t         substarts = 0;                         // SUBBLOCK: sub-starts placed (deduplicated)
     std::vector<unsigned long long> keys;                 // SUBBLOCK, per start: 0 a block start, 1 inside a fixed-code block,
                                                           // H + 2 inside the dynamic block at H
@@ -558,6 +561,62 @@ struct PassStream {
 static void leave(PassStream &s, const char *reason) {
     s.left = true;
     why(reason);
+}
+
+// pass_run's counting mode (zng_rocm_uncompress_large_size_dev / _sizes_dev): the parts of the streams `on` -- `np` together,
+// placed by pass_run -- through inflate_size_parts_kernel (inflate_large_size.hip) in ONE launch, and one walk per stream
+// (inflate_large_size_plan.h).  A counting part has no slot, so nothing overflows and nothing runs again; the scratch is
+// jobs | starts | results and nothing else.  A stream whose walk fails leaves the pass: the caller sizes it whole, with the
+// decoder's verdict.  (A stream of one part is a chain of one: what the finder could not cut, see pass_run.)
+static int count_parts(Workspace *ws, std::vector<PassStream> &ss, const std::vector<size_t> &on, size_t np, hipStream_t st,
+                       int *launches) {
+    const PartTables T = part_tables(np, false, false, 0);
+    uint8_t *sp = nullptr, *hq = nullptr;
+    if (scratch_reserve(ws, kScrLargeParts, T.device_bytes, false, (void **)&sp) != ZNG_ROCM_OK ||
+        scratch_reserve(ws, kScrLargePartsHost, T.mirror_bytes, true, (void **)&hq) != ZNG_ROCM_OK) {
+        for (size_t k : on) ss[k].left = true;
+        return why("no room for the part tables");
+    }
+    InflateJobDev *pj = (InflateJobDev *)(hq + T.jobs);
+    unsigned long long *h_starts = (unsigned long long *)(hq + T.starts);
+    uint32_t *res = (uint32_t *)(hq + T.res);
+    for (size_t k : on) {
+        const PassStream &s = ss[k];
+        const size_t n = s.starts.size();
+        std::copy(s.starts.begin(), s.starts.end(), h_starts + s.pbase);
+        // (a part that is not its stream's first has all the history a distance can reach: inflate_size_parts_kernel)
+        for (size_t i = 0; i < n; ++i)
+            pj[s.pbase + i] = InflateJobDev{s.d_src, nullptr, s.src_len, 0, i == 0 ? s.window_len : 32768u, (uint32_t)(s.pbase + n)};
+    }
+    ZR_HIP(hipMemcpyAsync(sp, hq, T.up_bytes, hipMemcpyHostToDevice, st));       // jobs | starts in one copy
+    if (int rc = launch_inflate_size_parts_device((const InflateJobDev *)(sp + T.jobs), np, (const unsigned long long *)(sp + T.starts),
+                                                  (uint32_t *)(sp + T.res), st))
+        return rc;
+    ++*launches;
+    ZR_HIP(hipMemcpyAsync(res, sp + T.res, np * 32, hipMemcpyDeviceToHost, st));
+    ZR_HIP(hipStreamSynchronize(st));
+    for (size_t k : on) {
+        PassStream &s = ss[k];
+        s.res = res + 8 * s.pbase;
+        SizeChain c;
+        if (!walk_size_chain(res, s.pbase, s.starts.size(), s.starts.data(), s.window_len, c)) {
+            // (readable through zng_rocm_last_error() until the stream's own verdict replaces it)
+            if (c.bad_part < s.starts.size())
+                set_error("inflate_large: sized whole by one wavefront (job %ld, part %zu of %zu at bit %llu: message %u \"%s\")", s.job,
+                          c.bad_part, s.starts.size(), s.starts[c.bad_part], s.res[8 * c.bad_part + 4],
+                          zng_rocm_inflate_message(s.res[8 * c.bad_part + 4]));
+            else
+                set_error("inflate_large: sized whole by one wavefront (job %ld: %s)", s.job, c.reason);
+            s.left = true;
+            continue;
+        }
+        s.status = 1;
+        s.chain.produced = c.produced;
+        s.chain.end_bit = c.end_bit;
+        s.chain.final = true;
+        s.counted_parts = c.parts;
+    }
+    return ZNG_ROCM_OK;
 }
 
 // The device pass over the streams `ss` whose starts are found, ONE of each step for all of them: the SUBBLOCK sync launch,
@@ -574,11 +633,13 @@ static void leave(PassStream &s, const char *reason) {
 // A stream the pass cannot do leaves it (PassStream::left); the others do not notice.  The streams from *taken on were not
 // taken up: their parts and those in front of them would be more than one launch (and the compaction grid) takes.
 // *launches counts the part launches.  Negative returns are HIP and allocation errors of the whole pass.
+// `counting` (never with `sub`, `blocks` or `pp`): the sizes alone -- the same streams are taken up and placed, and
+// count_parts does the rest: no slots, no rerun, no compaction, no resolve.
 static int pass_run(Workspace *ws, std::vector<PassStream> &ss, bool sub, bool blocks, PiecePass *pp, hipStream_t st, size_t *taken,
-                    int *launches) {
+                    int *launches, bool counting = false) {
     *taken = ss.size();
-    if (((blocks || pp) && ss.size() != 1) || (sub && blocks)) {
-        set_error("inflate_large: blocks mode and pieces take one stream, blocks mode no sub-starts");
+    if (((blocks || pp) && ss.size() != 1) || (sub && blocks) || (counting && (sub || blocks || pp))) {
+        set_error("inflate_large: blocks mode and pieces take one stream, blocks mode no sub-starts, the counting mode neither");
         return ZNG_ROCM_EINVAL;
     }
     const size_t cus = (size_t)ctx()->cus;
@@ -648,10 +709,16 @@ static int pass_run(Workspace *ws, std::vector<PassStream> &ss, bool sub, bool b
     for (size_t k = 0; k < ss.size(); ++k) {
         PassStream &s = ss[k];
         if (s.left) continue;
+        // (the counting mode: a stream that is not cut -- not scanned, too few starts, too many -- is ONE part from its first
+        // bit, which costs what sizing it whole costs and, when the stream is sound, is the answer)
         if (s.starts.size() < 4) {
-            leave(s, "fewer than four block starts found");
-            continue;
+            if (!counting) {
+                leave(s, "fewer than four block starts found");
+                continue;
+            }
+            s.starts.assign(1, s.start_bit);
         }
+        if (counting && on.empty() && s.starts.size() > kPieceMaxParts) s.starts.assign(1, s.start_bit);
         if (np + s.starts.size() > kPieceMaxParts) {      // more parts than one launch (and the compaction grid's y) takes
             if (on.empty()) {                             // one stream alone has them: not a stream for the device path
                 if (pp) pp->halve = true;
@@ -667,6 +734,7 @@ static int pass_run(Workspace *ws, std::vector<PassStream> &ss, bool sub, bool b
         on.push_back(k);
     }
     if (on.empty()) return ZNG_ROCM_OK;
+    if (counting) return count_parts(ws, ss, on, np, st, launches);
     auto all_out = [&](const char *reason) {
         for (size_t k : on) ss[k].left = true;
         return why(reason);
@@ -1356,8 +1424,9 @@ static int round_find(Workspace *ws, std::vector<PassStream> &ss, std::vector<st
 // One round: the jobs idx[0 .. *taken) (all of idx unless their parts together pass one launch's) through the table finder
 // and the pass.  Jobs done on the device have their output fields set; the others are appended to `host` (the caller
 // decodes them sequentially, as zng_rocm_inflate_large_ex_dev does it, behind the round's device work).
+// `counting`: pass_run's counting mode -- d_dst / dst_cap are not looked at, and `host` are the jobs to be sized whole.
 static int round_run(Workspace *ws, zng_rocm_inflate_large_job *jobs, const std::vector<size_t> &idx, bool sub, hipStream_t st,
-                     std::vector<size_t> &host, size_t *taken) {
+                     std::vector<size_t> &host, size_t *taken, bool counting = false) {
     std::vector<PassStream> ss(idx.size());
     std::vector<std::vector<unsigned long long>> good(idx.size());
     std::vector<size_t> scan;
@@ -1371,8 +1440,8 @@ static int round_run(Workspace *ws, zng_rocm_inflate_large_job *jobs, const std:
         s.d_dst = J.d_dst;
         s.dst_cap = J.dst_cap;
         s.job = (long)idx[k];
-        if (!large_length_ok(J.src_len)) s.left = true;
-        else scan.push_back(k);
+        if (large_length_ok(J.src_len)) scan.push_back(k);
+        else if (!counting) s.left = true;                // (the counting mode takes it as one part: pass_run)
     }
     // ---- candidates: the byte patterns for every stream; F1 + F2 for those they do not cut ---------------------------
     if (int rc = round_find(ws, ss, good, scan, true, false, st)) return rc;
@@ -1391,7 +1460,7 @@ static int round_run(Workspace *ws, zng_rocm_inflate_large_job *jobs, const std:
         else thin_starts(good[k], 0, s.src_len, s.starts, s.heavy);
     }
     int launches = 0;
-    const int rc = pass_run(ws, ss, sub, false, nullptr, st, taken, &launches);
+    const int rc = pass_run(ws, ss, sub, false, nullptr, st, taken, &launches, counting);
     t_batch_part_launches += launches;
     if (rc) return rc;
     for (size_t k = 0; k < *taken; ++k) {
@@ -1405,7 +1474,7 @@ static int round_run(Workspace *ws, zng_rocm_inflate_large_job *jobs, const std:
         J.out_len = s.chain.produced;
         J.in_used = (size_t)((s.chain.end_bit + 7) >> 3);
         J.msg = nullptr;
-        J.parts = (uint32_t)s.chain.copies.size();
+        J.parts = (uint32_t)(counting ? s.counted_parts : s.chain.copies.size());
         J.subparts = (uint32_t)s.chain.subparts;
     }
     return ZNG_ROCM_OK;
@@ -1419,6 +1488,102 @@ static void job_answer(zng_rocm_inflate_large_job &j, int status, uint64_t n, si
     j.msg = msg;
     j.parts = j.subparts = 0;
 }
+
+// The jobs `list` sized WHOLE, one wavefront each (inflate_size_stream_kernel), in one launch: every stream the counting chain
+// cannot do.  The row is zng_rocm_inflate_sizes_dev's with a 64-bit count -- the decoder's verdict, message and consumed
+// bytes -- so nothing of the stream comes to the host.
+static int size_whole_streams(Workspace *ws, zng_rocm_inflate_large_job *jobs, const std::vector<size_t> &list, hipStream_t st) {
+    const size_t n = list.size();
+    if (!n) return ZNG_ROCM_OK;
+    const PartTables T = part_tables(n, false, false, 0);                        // jobs | (starts: unused) | 8 result words
+    uint8_t *sp = nullptr, *hq = nullptr;
+    if (int rc = scratch_reserve(ws, kScrLargeParts, T.device_bytes, false, (void **)&sp)) return rc;
+    if (int rc = scratch_reserve(ws, kScrLargePartsHost, T.mirror_bytes, true, (void **)&hq)) return rc;
+    InflateJobDev *pj = (InflateJobDev *)(hq + T.jobs);
+    const uint32_t *res = (const uint32_t *)(hq + T.res);
+    for (size_t k = 0; k < n; ++k) {
+        const zng_rocm_inflate_large_job &j = jobs[list[k]];
+        pj[k] = InflateJobDev{j.d_src, nullptr, j.src_len, 0, j.window_len, 0u};
+    }
+    ZR_HIP(hipMemcpyAsync(sp + T.jobs, pj, n * sizeof(InflateJobDev), hipMemcpyHostToDevice, st));
+    if (int rc = launch_inflate_size_streams_device((const InflateJobDev *)(sp + T.jobs), n, (uint32_t *)(sp + T.res), st)) return rc;
+    ZR_HIP(hipMemcpyAsync(hq + T.res, sp + T.res, n * 32, hipMemcpyDeviceToHost, st));
+    ZR_HIP(hipStreamSynchronize(st));
+    for (size_t k = 0; k < n; ++k) {
+        const LsRow r = ls_stream_row(res + 8 * k);
+        const int status = (int)(int32_t)r.status;
+        job_answer(jobs[list[k]], status, r.out_len, r.used, status == -3 && r.msg != kMsgNone ? zng_rocm_inflate_message(r.msg) : nullptr);
+    }
+    return ZNG_ROCM_OK;
+}
+
+// The rounds of zng_rocm_inflate_large_streams_dev, and (`counting`) of the sizing calls: the arguments have been checked.
+static int rounds_run(zng_rocm_inflate_large_job *jobs, size_t njobs, size_t round_bytes, bool sub, bool counting, hipStream_t st) {
+    if (!round_bytes) round_bytes = kRoundDefault;
+    DeviceGuard dev;
+    Workspace *ws = workspace_for(st);                   // scratch is keyed by the caller's HIP stream (context.h)
+    if (!ws) return ZNG_ROCM_ENOMEM;
+    int first_err = ZNG_ROCM_OK;
+    size_t next = 0;
+    while (next < njobs) {
+        // a round: jobs in order until their compressed bytes would pass round_bytes (a larger job is a round of its own)
+        std::vector<size_t> idx;
+        size_t bytes = 0;
+        for (size_t i = next; i < njobs; ++i) {
+            if (!idx.empty() && bytes + jobs[i].src_len > round_bytes) break;
+            idx.push_back(i);
+            bytes += jobs[i].src_len;
+        }
+        std::vector<size_t> host;
+        size_t taken = idx.size();
+        int rc;
+        {
+            std::lock_guard<std::mutex> use(ws->mu);
+            rc = round_run(ws, jobs, idx, sub, st, host, &taken, counting);
+            // the jobs that left a counting round: sized whole on the device, behind the round's parts
+            if (rc == ZNG_ROCM_OK && counting) rc = size_whole_streams(ws, jobs, host, st);
+        }
+        ++t_batch_rounds;
+        if (rc != ZNG_ROCM_OK) {                         // a device error: the round's jobs have it, and the call ends
+            for (size_t i = idx[0]; i < njobs; ++i) job_answer(jobs[i], rc, 0, 0, nullptr);
+            return rc;
+        }
+        // the jobs that left the round: the sequential decoder on a host copy, exactly as zng_rocm_inflate_large_ex_dev
+        if (counting) host.clear();                      // (sized above)
+        for (size_t i : host) {
+            zng_rocm_inflate_large_job &j = jobs[i];
+            std::vector<uint8_t> copy(j.src_len ? j.src_len : 1);
+            int s = ZNG_ROCM_OK;
+            if (j.src_len && (hipMemcpyAsync(copy.data(), j.d_src, j.src_len, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                              hipStreamSynchronize(st) != hipSuccess)) {
+                set_error("zng_rocm_inflate_large_streams_dev: copying job %zu to the host failed", i);
+                s = ZNG_ROCM_EHIP;
+            }
+            uint64_t n = 0;
+            size_t used = 0;
+            const char *msg = nullptr;
+            if (s == ZNG_ROCM_OK)
+                s = inflate_raw_window_sequential_msg(copy.data(), j.src_len, j.d_window, j.window_len, j.d_dst, j.dst_cap, &n, &used,
+                                                      &msg, st);
+            job_answer(j, s, n, used, s == -3 ? msg : nullptr);
+            if ((s == ZNG_ROCM_EHIP || s == ZNG_ROCM_ENOMEM) && first_err == ZNG_ROCM_OK) first_err = s;
+        }
+        next = idx[0] + taken;
+    }
+    return first_err;
+}
+
+namespace zr {
+// zng_rocm_uncompress_large_size_dev / _sizes_dev (framing_large.hip) on raw payloads whose arguments have been checked:
+// per job status / out_len / in_used / msg / parts as the decode batch sets them, d_dst / dst_cap not looked at.  `single`:
+// the one-stream call, whose parts zng_rocm_inflate_large_last_parts() reports.
+int inflate_large_sizes_raw(zng_rocm_inflate_large_job *jobs, size_t njobs, size_t round_bytes, bool single, hipStream_t st) {
+    inflate_large_reset_counters();
+    const int rc = rounds_run(jobs, njobs, round_bytes, false, true, st);
+    if (single && njobs == 1 && jobs[0].status == 1) t_large_parts = (int)jobs[0].parts;
+    return rc;
+}
+}  // namespace zr
 
 extern "C" {
 
@@ -1450,57 +1615,7 @@ int zng_rocm_inflate_large_streams_dev(zng_rocm_inflate_large_job *jobs, size_t 
         }
     }
     if (!njobs) return ZNG_ROCM_OK;
-    if (!round_bytes) round_bytes = kRoundDefault;
-    DeviceGuard dev;
-    hipStream_t st = (hipStream_t)stream;
-    const bool sub = flags != 0;
-    Workspace *ws = workspace_for(st);                   // scratch is keyed by the caller's HIP stream (context.h)
-    if (!ws) return ZNG_ROCM_ENOMEM;
-    int first_err = ZNG_ROCM_OK;
-    size_t next = 0;
-    while (next < njobs) {
-        // a round: jobs in order until their compressed bytes would pass round_bytes (a larger job is a round of its own)
-        std::vector<size_t> idx;
-        size_t bytes = 0;
-        for (size_t i = next; i < njobs; ++i) {
-            if (!idx.empty() && bytes + jobs[i].src_len > round_bytes) break;
-            idx.push_back(i);
-            bytes += jobs[i].src_len;
-        }
-        std::vector<size_t> host;
-        size_t taken = idx.size();
-        int rc;
-        {
-            std::lock_guard<std::mutex> use(ws->mu);
-            rc = round_run(ws, jobs, idx, sub, st, host, &taken);
-        }
-        ++t_batch_rounds;
-        if (rc != ZNG_ROCM_OK) {                         // a device error: the round's jobs have it, and the call ends
-            for (size_t i = idx[0]; i < njobs; ++i) job_answer(jobs[i], rc, 0, 0, nullptr);
-            return rc;
-        }
-        // the jobs that left the round: the sequential decoder on a host copy, exactly as zng_rocm_inflate_large_ex_dev
-        for (size_t i : host) {
-            zng_rocm_inflate_large_job &j = jobs[i];
-            std::vector<uint8_t> copy(j.src_len ? j.src_len : 1);
-            int s = ZNG_ROCM_OK;
-            if (j.src_len && (hipMemcpyAsync(copy.data(), j.d_src, j.src_len, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                              hipStreamSynchronize(st) != hipSuccess)) {
-                set_error("zng_rocm_inflate_large_streams_dev: copying job %zu to the host failed", i);
-                s = ZNG_ROCM_EHIP;
-            }
-            uint64_t n = 0;
-            size_t used = 0;
-            const char *msg = nullptr;
-            if (s == ZNG_ROCM_OK)
-                s = inflate_raw_window_sequential_msg(copy.data(), j.src_len, j.d_window, j.window_len, j.d_dst, j.dst_cap, &n, &used,
-                                                      &msg, st);
-            job_answer(j, s, n, used, s == -3 ? msg : nullptr);
-            if ((s == ZNG_ROCM_EHIP || s == ZNG_ROCM_ENOMEM) && first_err == ZNG_ROCM_OK) first_err = s;
-        }
-        next = idx[0] + taken;
-    }
-    return first_err;
+    return rounds_run(jobs, njobs, round_bytes, flags != 0, false, (hipStream_t)stream);
 }
 
 }  // extern "C"

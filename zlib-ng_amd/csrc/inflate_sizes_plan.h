@@ -79,6 +79,11 @@ ZR_HD bool is_count_add(uint32_t *count, uint32_t n) {
     *count += n;
     return false;
 }
+// the same on a 64-bit count (the sizing of large streams, inflate_large_size.hip): it never saturates
+ZR_HD bool is_count_add(unsigned long long *count, uint32_t n) {
+    *count += n;
+    return false;
+}
 ZR_HD uint32_t is_status_of(uint32_t msg) {
     return msg == kMsgNone ? 1u : (msg == kMsgStarved || msg == kMsgOutFull) ? kIsBufError : kIsDataError;
 }

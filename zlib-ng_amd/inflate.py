@@ -446,6 +446,45 @@ def uncompress_large_dev(fmt, src_dev, dst, dict=None, piece_bytes=0, stream=Non
             int(lib.zng_rocm_inflate_large_last_pieces()), int(lib.zng_rocm_inflate_large_last_host_bytes()))
 
 
+def uncompress_large_size_dev(fmt, src_dev, dict=None, dict_len=None, stream=None, flags=0):
+    """zng_rocm_uncompress_large_size_dev: the plaintext length of ONE large stream that is already in device memory, found by
+    a counting pass that decodes nothing (fmt 0 raw, 1 zlib, 2 gzip; the member with its wrapper).  `dict`: the preset
+    dictionary of a zlib member (CUDA tensor); fmt 0: the history the caller will put in front -- only its length matters, so
+    `dict_len` alone will do.  Returns (status, plaintext bytes, member bytes used, parts on the chain -- 0 when the
+    one-wavefront kernel sized the stream)."""
+    rocm._need_init()
+    lib = rocm.lib()
+    out_len, in_used = C.c_uint64(0), C.c_size_t(0)
+    dl = (0 if dict is None else int(dict.numel())) if dict_len is None else int(dict_len)
+    n = 0 if src_dev is None else int(src_dev.numel())
+    st = lib.zng_rocm_uncompress_large_size_dev(int(fmt), rocm._dev_ptr(src_dev) if n else None, n,
+                                                rocm._dev_ptr(dict) if dict is not None and dict.numel() else None, dl,
+                                                C.byref(out_len), C.byref(in_used), int(flags), rocm._stream_ptr(stream))
+    return st, int(out_len.value), int(in_used.value), int(lib.zng_rocm_inflate_large_last_parts())
+
+
+def uncompress_large_sizes_dev(fmt, srcs_dev, dicts=None, round_bytes=0, stream=None, flags=0, jobs=None):
+    """zng_rocm_uncompress_large_sizes_dev: uncompress_large_size_dev for a batch, in rounds of one finder pass and ONE
+    counting part launch each.  Returns (return value, rows, rounds, part launches), rows = [(status, out_len, in_used,
+    msg or None, parts, subparts = 0)].  `jobs` (from large_jobs; d_dst / dst_cap are not looked at) is used as it is when
+    given."""
+    rocm._need_init()
+    lib = rocm.lib()
+    n = len(srcs_dev)
+    if jobs is None:
+        jobs = (LargeJob * max(n, 1))()
+        for i in range(n):
+            d = None if dicts is None else dicts[i]
+            dl = 0 if d is None else int(d.numel())
+            jobs[i].d_src, jobs[i].src_len = (rocm._dev_ptr(srcs_dev[i]) if srcs_dev[i].numel() else None), int(srcs_dev[i].numel())
+            jobs[i].d_window, jobs[i].window_len = (rocm._dev_ptr(d) if dl else None), dl
+    rc = lib.zng_rocm_uncompress_large_sizes_dev(int(fmt), C.cast(jobs, C.c_void_p), n, int(round_bytes), int(flags),
+                                                 rocm._stream_ptr(stream))
+    rows = [(int(j.status), int(j.out_len), int(j.in_used), j.msg.decode() if j.msg else None, int(j.parts), int(j.subparts))
+            for j in jobs[:n]]
+    return rc, rows, int(lib.zng_rocm_inflate_large_last_rounds()), int(lib.zng_rocm_inflate_large_last_part_launches())
+
+
 class GzipMember(C.Structure):
     """zng_rocm_gzip_member"""
     _fields_ = [("src_off", C.c_uint64), ("src_len", C.c_uint64), ("dst_off", C.c_uint64), ("out_len", C.c_uint64),

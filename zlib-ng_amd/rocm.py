@@ -161,6 +161,9 @@ _PROTOS = {
     "zng_rocm_uncompress_large_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t,
                                                 C.POINTER(C.c_uint64), C.POINTER(C.c_size_t), C.c_size_t, C.c_uint32,
                                                 C.c_void_p]),
+    "zng_rocm_uncompress_large_size_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32,
+                                                     C.POINTER(C.c_uint64), C.POINTER(C.c_size_t), C.c_uint32, C.c_void_p]),
+    "zng_rocm_uncompress_large_sizes_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32, C.c_void_p]),
     "zng_rocm_gunzip_members_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64),
                                               C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_uint32,
                                               C.c_void_p]),
