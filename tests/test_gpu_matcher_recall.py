@@ -1,0 +1,286 @@
+"""GPU: what the two LZ77 match finders must FIND, black-box: the planted repeats of tests/matcher_cases.py go through the
+public entry points (StreamsBatch at every level 1..9 and deflate_dev for the rows class -- lz_rows_kernel --, QuickBatch for
+the level-1 class -- deflate_quick_kernel), every output is taken apart by tests/deflate_parse.py, and the tokens are held
+against what the input leaves no choice about.  No model of the row tables or of the cost refresh is involved.
+
+  recall   rows class: of the range [at, at + m), whose one earlier copy lies at distance D <= 32506, at most 3 bytes are
+           literals (a remainder shorter than kLzMinMatch = 4), at every level; a range across the 131072 segment border is two
+           ranges (matches end with their segment), 3 bytes each.  Every match token that overlaps the range has distance D
+           (far form) or a multiple of D (near form).
+           level-1 class: at most 63 * ceil(m / 258) + 3 + 8 literal bytes -- and, tighter, 63 only for every 258-byte match
+           that ends inside the range and for a range that starts 1..3 bytes behind a region's first.
+  MAX_DIST no token of any stream has a distance above 32506 = 32768 - 262, none copies from in front of the first byte of
+           dictionary + stream, and a range whose only copy lies 32507 or 32768 back is literals throughout.
+  budget   k = kLevelCand[level] - 1 decoys (at most 7) between the true source and the query, all in one row with one tag and
+           in front of the query's batch: the query is covered from its FIRST byte at the true source's distance.
+  function the output is a function of the input alone: a stream compressed alone, alone again and inside a batch of 24 others
+           gives the same bytes, and deflate_dev gives them too.
+  size     per class of data (the six of synth.segment, 256 KiB each) device size / CPython zlib size at the same level stays
+           within 0.01 of the ratio measured when this file was written (SIZE_RATIO below)."""
+import importlib
+import zlib
+
+import numpy as np
+import pytest
+
+import deflate_parse as dp
+import matcher_cases as mc
+import synth
+from gpu_common import product, torch_mod
+
+pytestmark = pytest.mark.gpu
+
+LEVELS = tuple(range(1, 10))
+LEVEL_CAND = (0, 1, 2, 3, 6, 8, 16, 16, 16, 16)     # kLevelCand, zlib-ng_amd/csrc/deflate_dyn.hip:745
+ROW_ENTRIES = 8                                     # kRowEnt, deflate_rows.h:38: a row cannot hold more candidates
+MIN_MATCH = 4                                       # kLzMinMatch, deflate_lz.h:32
+
+# device size / CPython zlib size (raw deflate, the same level), 256 KiB of each class of synth.segment (_size_classes);
+# measured on MI355X.  The output is deterministic: the 0.01 the tests add is room for later changes, not noise.
+SIZE_SEED = 0x5123
+SIZE_RATIO = {
+    "rows-1": {"text": 0.9065, "records": 1.0472, "dna": 0.9893, "sparse": 0.6829, "random": 0.9998, "xml": 0.9683},
+    "rows-6": {"text": 1.0132, "records": 0.9870, "dna": 0.9923, "sparse": 0.8679, "random": 0.9998, "xml": 1.0213},
+    "rows-9": {"text": 1.0376, "records": 0.9823, "dna": 1.0062, "sparse": 0.9748, "random": 0.9998, "xml": 1.0555},
+    "quick-1": {"text": 1.2778, "records": 1.3268, "dna": 1.5762, "sparse": 4.3673, "random": 1.0543, "xml": 1.4168},
+}
+
+
+class Device:
+    def __init__(self):
+        zr = product()
+        zr.init()
+        self.torch = torch_mod()
+        self.dfl = importlib.import_module("zlib-ng_amd.deflate")
+        self.cells, self.budget = mc.cells(), mc.budget_streams()
+        items = [(c.history, c.data) for c in self.cells] + [(b"", s.data) for s in self.budget]
+        self.host, self.offs, self.lens, self.dls = mc.pack(items)
+        assert self.host.size < 32 << 20                   # one call of this size cuts 128 KiB segments
+        self.src = self.torch.from_numpy(self.host).cuda()
+        self.history = [h for h, _ in items]
+        self.data = [d for _, d in items]
+        self._comp, self._parsed = {}, {}
+
+    def comp(self, key):
+        """key: a level of the rows class, or "quick" -> the compressed streams of one ragged batch"""
+        if key not in self._comp:
+            if key == "quick":
+                b = self.dfl.QuickBatch(self.src, self.offs, self.lens, dict_len=self.dls)
+                b.run()
+                res = b.results.cpu()
+                self._comp[key] = [b.compressed(i, res) for i in range(b.n)]
+            else:
+                b = self.dfl.StreamsBatch(self.src, self.offs, self.lens, dict_len=self.dls)
+                b.run(level=key)
+                self._comp[key] = [b.compressed(i) for i in range(b.n)]
+        return self._comp[key]
+
+    def parsed(self, key, i):
+        if (key, i) not in self._parsed:
+            p = dp.parse(self.comp(key)[i], history=self.history[i])
+            assert p.data == self.data[i], (key, i)
+            assert (p.end_bit + 7) // 8 == len(self.comp(key)[i]), (key, i)
+            self._parsed[key, i] = p
+        return self._parsed[key, i]
+
+    def one_stream(self, i, level):
+        dst, n = self.dfl.deflate_dev(self.src, level=level, length=self.lens[i], offset=self.offs[i], dict_len=self.dls[i])
+        return dst[:n].cpu().numpy().tobytes()
+
+
+@pytest.fixture(scope="module")
+def dev():
+    return Device()
+
+
+def _ranges(c, rows):
+    """the ranges of a cell that are judged on their own: the rows class ends every match at its segment's end"""
+    b = mc.segment_border(c) if rows else None
+    return [(c.at, b), (b, c.at + c.m)] if b else [(c.at, c.at + c.m)]
+
+
+def _distance_ok(c, d):
+    return d % c.D == 0 if c.near else d == c.D
+
+
+def _check_limits(dev, key):
+    """MAX_DIST and the first byte of dictionary + stream, over every stream of the batch; the too-far cells"""
+    bad = []
+    for i in range(len(dev.data)):
+        cov = mc.coverage(dev.parsed(key, i), 0, 0, len(dev.history[i]))
+        if cov.max_dist > mc.MAX_DIST or cov.min_reach < 0:
+            bad.append((i, cov))
+    for i, c in enumerate(dev.cells):
+        if c.too_far:
+            cov = mc.coverage(dev.parsed(key, i), c.at, c.at + c.m)
+            if cov.dists or cov.lits != c.m:
+                bad.append((c.name, cov))
+    assert not bad, bad
+
+
+def _rows_recall(c, p):
+    """[(literal bytes, allowance, distances)] per judged range, and whether all of it holds"""
+    out, ok = [], True
+    for lo, hi in _ranges(c, True):
+        cov = mc.coverage(p, lo, hi, len(c.history))
+        out.append((cov.lits, MIN_MATCH - 1, sorted(cov.dists)))
+        ok &= cov.lits <= MIN_MATCH - 1 and all(_distance_ok(c, d) for d in cov.dists)
+        ok &= bool(cov.dists) or hi - lo < MIN_MATCH
+    return out, ok
+
+
+@pytest.mark.parametrize("level", LEVELS)
+def test_rows_recall(dev, level):
+    bad, worst = [], (0, "")
+    for i, c in enumerate(dev.cells):
+        if c.too_far:
+            continue
+        got, ok = _rows_recall(c, dev.parsed(level, i))
+        worst = max(worst, (max(g[0] for g in got), c.name))
+        if not ok:
+            bad.append((c.name, got))
+    print("rows level %d: worst cell %s with %d literal bytes; %d cells miss" % (level, worst[1], worst[0], len(bad)))
+    for b in bad:
+        print("  MISS", b)
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("level", LEVELS)
+def test_rows_max_dist(dev, level):
+    _check_limits(dev, level)
+
+
+def test_rows_position_sweep_one_stream(dev):
+    """the position-sweep cells through deflate_dev, level 6: the same recall, and the bytes of the batch (the segment size
+    agrees at these sizes)"""
+    bad = []
+    for i, c in enumerate(dev.cells):
+        if c.sweep != "pos":
+            continue
+        comp = dev.one_stream(i, 6)
+        p = dp.parse(comp)
+        assert p.data == c.data
+        got, ok = _rows_recall(c, p)
+        if not ok or comp != dev.comp(6)[i]:
+            bad.append((c.name, got, comp == dev.comp(6)[i]))
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("level", LEVELS)
+def test_rows_candidate_budget(dev, level):
+    """every stream with k + 1 <= kLevelCand[level] candidates in the query's row, whichever slot holds the true one"""
+    kmax = min(LEVEL_CAND[level] - 1, ROW_ENTRIES - 1)
+    assert kmax == (0, 0, 1, 2, 5, 7, 7, 7, 7, 7)[level]
+    bad, seen = [], set()
+    for j, s in enumerate(dev.budget):
+        if s.k > kmax:
+            continue
+        seen.add(s.k)
+        cov = mc.coverage(dev.parsed(level, len(dev.cells) + j), s.query, s.query + 200)
+        if cov.lits or cov.dists != {s.dist}:
+            bad.append((s.name, s.dist, cov))
+    assert kmax in seen
+    assert not bad, bad
+
+
+def _quick_allowances(c):
+    """(the issue's allowance, the derived one): a 258-byte match that ends inside the range exposes up to 63 bytes, the
+    rest of its 64-position region, whose own speculative token starts inside the match and is dropped; so does a range
+    that begins 1..3 bytes behind a region's first byte in the far form: the region's first token is then the match from
+    the zeros in front of R, which starts inside the zero run's match.  3: a remainder below kLzMinMatch; 8: positions
+    whose head slot a colliding later string took (each costs one literal)."""
+    wide = 63 * -(-c.m // 258) + 3 + 8
+    front = 1 if not c.near and (len(c.history) + c.at) % mc.REGION in (1, 2, 3) else 0
+    return wide, 63 * (-(-c.m // 258) - 1 + front) + 3 + 8
+
+
+def test_quick_recall(dev):
+    bad, worst = [], (0, "")
+    for i, c in enumerate(dev.cells):
+        if c.too_far:
+            continue
+        cov = mc.coverage(dev.parsed("quick", i), c.at, c.at + c.m, len(c.history))
+        wide, tight = _quick_allowances(c)
+        assert tight <= wide
+        worst = max(worst, (cov.lits, c.name))
+        if cov.lits > min(wide, tight) or not all(_distance_ok(c, d) for d in cov.dists):
+            bad.append((c.name, cov, wide, tight))
+        elif cov.lits:
+            print("  quick %s: %d literal bytes (allowance %d / %d)" % (c.name, cov.lits, tight, wide))
+    print("quick: worst cell %s with %d literal bytes; %d cells miss" % (worst[1], worst[0], len(bad)))
+    for b in bad:
+        print("  MISS", b)
+    assert not bad, bad
+
+
+def test_quick_max_dist(dev):
+    _check_limits(dev, "quick")
+
+
+def test_output_is_a_function_of_the_input(dev):
+    """level 6: alone, alone again, inside a batch of 24 others, and through deflate_dev -- the same bytes"""
+    torch, dfl = dev.torch, dev.dfl
+    by_name = {c.name: c for c in dev.cells}
+    picks = [synth.silesia_like(300 << 10, seed=0xD37).tobytes(),
+             by_name["pos/m300-D32506-at130942-tail300"].data, by_name["len/m1024-D4096-at40000-tail300"].data,
+             by_name["dist/m300-D257-at40000-tail300"].data]
+    others = [c.data for c in dev.cells if c.sweep in ("tail",)][:24]
+    assert len(others) == 24
+
+    def run(streams):
+        host, offs, lens, _ = mc.pack([(b"", s) for s in streams])
+        src = torch.from_numpy(host).cuda()
+        b = dfl.StreamsBatch(src, offs, lens)
+        b.run(level=6)
+        return [b.compressed(i) for i in range(b.n)], src, offs
+
+    together = {}
+    for k, data in enumerate(picks):
+        first, src, offs = run([data])
+        again, _, _ = run([data])
+        mixed, _, _ = run(others[:5 * k + 3] + [data] + others[5 * k + 3:])
+        assert zlib.decompressobj(-15).decompress(first[0]) == data
+        assert again[0] == first[0], k
+        assert mixed[5 * k + 3] == first[0], k
+        dst, n = dfl.deflate_dev(src, level=6, length=len(data), offset=offs[0])
+        assert dst[:n].cpu().numpy().tobytes() == first[0], k
+        together[k] = mixed
+    assert together[0][:3] == together[1][:3]              # the others do not depend on their neighbours either
+
+
+def _size_classes():
+    out = {}
+    for k, kind in enumerate(synth.CLASSES):
+        part = synth.segment(kind, 256 << 10, np.random.default_rng([SIZE_SEED, k]))
+        out[kind] = np.concatenate([part, np.zeros((256 << 10) - part.size, dtype=np.uint8)]).tobytes()
+    return out
+
+
+def _zlib_size(data, level):
+    c = zlib.compressobj(level, zlib.DEFLATED, -15)
+    return len(c.compress(data) + c.flush())
+
+
+@pytest.mark.parametrize("which", ["rows-1", "rows-6", "rows-9", "quick-1"])
+def test_size_per_class_against_zlib(dev, which):
+    """the reference is CPython's zlib at the same level, never an earlier output of the device"""
+    kind, level = which.split("-")[0], int(which.split("-")[1])
+    classes = _size_classes()
+    host, offs, lens, _ = mc.pack([(b"", d) for d in classes.values()])
+    src = dev.torch.from_numpy(host).cuda()
+    if kind == "quick":
+        b = dev.dfl.QuickBatch(src, offs, lens)
+        b.run()
+        res = b.results.cpu()
+        comps = [b.compressed(i, res) for i in range(b.n)]
+    else:
+        b = dev.dfl.StreamsBatch(src, offs, lens)
+        b.run(level=level)
+        comps = [b.compressed(i) for i in range(b.n)]
+    got = {}
+    for (name, data), comp in zip(classes.items(), comps):
+        assert zlib.decompressobj(-15).decompress(comp) == data, name
+        got[name] = len(comp) / _zlib_size(data, level)
+    print("SIZE_RATIO %r: {%s}" % (which, ", ".join('"%s": %.4f' % kv for kv in got.items())))
+    over = {n: (r, SIZE_RATIO[which][n]) for n, r in got.items() if r > SIZE_RATIO[which][n] + 0.01}
+    assert not over, over

@@ -17,7 +17,9 @@
 // A batch is 1024 consecutive positions, one per lane.  Every lane reads its row BEFORE the batch is inserted (the
 // candidates in front of the batch, complete), the waves insert in position order, every lane reads its row again (the
 // candidates inside the batch), so what a lane sees never depends on how the waves were scheduled: the output is a
-// function of the input alone.
+// function of the input alone.  What the second read cannot show -- positions of the batch that later ones of the same
+// batch pushed out of the row, where a run or a repeat of a short period begins -- a probe of the 8 bytes in front of the
+// position finds (rows_compare).
 //
 // The parse is not deflate_medium's greedy/lazy heuristic (deflate_medium.c:187-277) but a shortest-path parse per
 // 64-position region (one wavefront): with the longest match known at EVERY position, cost[i] = min(literal + cost[i+1],
@@ -239,7 +241,7 @@ struct RowsFront {                      // what rows_front hands to rows_compare
     uint2    TA, TC;
     uint4    PA, PC;
     uint32_t mine[4];
-    uint32_t before, val, tag;
+    uint32_t w8, w4, val, tag;          // w8, w4: the bytes p - 8 .. p - 5 and p - 4 .. p - 1
     bool     can;
 };
 struct RowsMatch {                      // per lane: what a batch carries from its compares to its parse
@@ -261,12 +263,16 @@ __device__ __forceinline__ void rows_front(uint32_t n, uint32_t P, RowShared *sh
     uint32_t row;
     row_key(f.val, row, f.tag);
     ZR_STAMP(0);
-    // A. the row as it is in front of this batch, this lane's own 16 bytes, the bytes in front of them
+    // A. the row as it is in front of this batch, this lane's own 16 bytes, the eight bytes in front of them
     f.TA = *reinterpret_cast<const uint2 *>(&sh->tag[row * kRowEnt]);
     f.PA = *reinterpret_cast<const uint4 *>(&sh->pos[row * kRowEnt]);
 #pragma unroll
     for (int j = 0; j < 4; ++j) f.mine[j] = ring_u32(ring, pi + 4u * j);
-    f.before = ring_u32(ring, (pi - 1u) & (kRingBytes - 1u));
+    {                                                    // one 8-byte piece: where it wraps, the mirror continues it
+        const uint32_t b8 = (pi - 8u) & (kRingBytes - 1u);
+        f.w8 = ring_u32(ring, b8);
+        f.w4 = ring_u32(ring, b8 + 4u);
+    }
     rows_barrier();
     *cover_in = sh->cover;                               // written by the previous rows_finish in front of this barrier
     if (refresh) rows_refresh_costs(sh, t);              // its readers come behind the insert turns' barriers
@@ -326,8 +332,20 @@ __device__ __forceinline__ RowsMatch rows_compare(uint32_t n, uint32_t P, uint32
             }
         };
 
-        // a run (distance 1) first: every position of a run lands in ONE row, which keeps only the last few of them
-        if (p > P0 && f.before == f.val) consider(1u);
+        // A repeat of period 1..8 first, its nearest copy.  The rows are read once the whole batch is in them and a row keeps
+        // its last eight positions: every position of a run lands in ONE row, those of a period of d bytes in d rows, so
+        // where such a repeat begins the later positions of the batch have pushed out what the earlier ones need, and the
+        // row in front of the batch has nothing of it yet.  near: the smallest d in 1..8 with this position's four bytes
+        // at p - d (bytes p - 8 .. p + 3 lie in w8, w4, val), 0 = none.  The probe costs no budget.
+        uint32_t near = f.w8 == f.val ? 8u : 0u;
+        near = __builtin_amdgcn_alignbyte(f.w4, f.w8, 1) == f.val ? 7u : near;
+        near = __builtin_amdgcn_alignbyte(f.w4, f.w8, 2) == f.val ? 6u : near;
+        near = __builtin_amdgcn_alignbyte(f.w4, f.w8, 3) == f.val ? 5u : near;
+        near = f.w4 == f.val ? 4u : near;
+        near = __builtin_amdgcn_alignbyte(f.val, f.w4, 1) == f.val ? 3u : near;
+        near = __builtin_amdgcn_alignbyte(f.val, f.w4, 2) == f.val ? 2u : near;
+        near = __builtin_amdgcn_alignbyte(f.val, f.w4, 3) == f.val ? 1u : near;
+        if (near - 1u < dmax) consider(near);
         while (mC && !done && budget) {
             const uint32_t e = (uint32_t)__ffs((int)mC) - 1u;
             mC &= mC - 1u;
