@@ -11,6 +11,9 @@
 //           out: jobs starts keys res extra slots up_bytes res_words mirror_bytes device_bytes (part_tables)
 //   retry   in: limit_bytes nstreams, nstreams x (first n), rows, rows part_bytes, rows messages (result word 4)
 //           out: "again:" rows, "off:", "cap:", "total:" one number, "over:" streams (plan_retry)
+//   chainfull  in: i0 i1 rows, rows x (message, "ended on BFINAL", link) -- result words 4, 3, 6
+//           out: the row of the first full part on the chain from row i0, "end" (the chain ends without one) or "broken"
+//           (first_full_on_chain)
 //   segs    in: nstreams, per stream: produced dst ncopies, ncopies x (dst n); a copy's slot is its number over all streams
 //           out: "v:" per stream, "copies:" one "slot dst gstart n first" per copy, "segs:" the middle word of every triple,
 //                "seg_dst:", "seg_end:", "v_end:" one number (symbol_tables)
@@ -59,6 +62,19 @@ static int retry() {
     return 0;
 }
 
+static int chainfull() {
+    size_t i0, i1, rows;
+    if (!(std::cin >> i0 >> i1 >> rows)) return 2;
+    std::vector<uint32_t> res(8 * rows, 0);
+    for (size_t i = 0; i < rows; ++i) std::cin >> res[8 * i + 4] >> res[8 * i + 3] >> res[8 * i + 6];
+    if (!std::cin || i0 >= i1 || i1 > rows) return 2;
+    const size_t at = zr::first_full_on_chain(res.data(), i0, i1);
+    if (at == i1) printf("end\n");
+    else if (at > i1) printf("broken\n");
+    else printf("%zu\n", at);
+    return 0;
+}
+
 static int segs() {
     size_t ns;
     if (!(std::cin >> ns)) return 2;
@@ -95,7 +111,7 @@ static int segs() {
 }
 
 int main(int argc, char **argv) {
-    if (argc > 1) return !strcmp(argv[1], "layout") ? layout() : !strcmp(argv[1], "retry") ? retry() : !strcmp(argv[1], "segs") ? segs() : 2;
+    if (argc > 1) return !strcmp(argv[1], "layout") ? layout() : !strcmp(argv[1], "retry") ? retry() : !strcmp(argv[1], "chainfull") ? chainfull() : !strcmp(argv[1], "segs") ? segs() : 2;
     size_t rows, pbase, np;
     uint32_t window_len;
     uint64_t src_len;

@@ -22,6 +22,8 @@ and `segs` arguments):
   retry        a part that said "output full" (message 13) runs again with retry_cap = (1032 x its compressed bytes + 655360,
                rounded up to 8) symbols of room, the parts one behind the other; a stream whose parts want more than the
                limit in bytes (2 per symbol) is reported and left out
+  chainfull    a piece over that limit runs the full parts ON its chain again, one at a time: the first full part that following
+               the links from the stream's first part meets, "end" when the chain ends without one, "broken" otherwise
   symbol array streams one behind the other, each behind a gap of 32768 symbols, the first at 32768; a copy's dst is re-based
                to the array, gstart / first name the first copy of its segment; a segment's bytes end where the next segment
                of the same stream begins, the last one's where the stream's do"""
@@ -231,6 +233,34 @@ def test_retry_plan(driver):
     # no part full: nothing to run again
     got = rule(driver, "retry", [24 << 30, 2] + spans + [5] + part_bytes + [0, 0, STARVED, 0, 0])
     assert got == {"again": [], "off": [], "cap": [], "total": [0], "over": []}
+
+
+def test_the_first_full_part_on_the_chain(driver):
+    """a piece over its retry cap runs the full parts ON its chain again, one at a time: parts that no chain reaches (noise
+    candidates -- a stored block's payload may hold thousands of headers that promise 65535 bytes each) ask for nothing"""
+    none = 0xffffffff
+
+    def ask(i0, i1, rows):
+        out = subprocess.run([driver, "chainfull"], input=" ".join(str(x) for x in [i0, i1, len(rows)] + [v for r in rows for v in r]),
+                             capture_output=True, text=True, check=True).stdout.strip()
+        return out if out in ("end", "broken") else int(out)
+    ok, full, err = (lambda link: (0, 0, link)), (OUT_FULL, 0, none), (LITLEN_CODE, 0, none)
+    # the chain 0 -> 3 -> 5 -> 7 (BFINAL) among full decoys: it meets none of them
+    rows = [ok(3), full, full, ok(5), full, ok(7), full, (0, 1, none)]
+    assert ask(0, 8, rows) == "end"
+    assert ask(0, 8, rows[:5] + [(STARVED, 0, none)] + rows[6:]) == "end"          # a piece: the chain ends where the input does
+    # part 5 is full: found; run again (a message of its own now) the walk goes on to part 7
+    assert ask(0, 8, rows[:5] + [full] + rows[6:]) == 5
+    assert ask(0, 8, [full] + rows[1:]) == 0
+    assert ask(0, 8, rows[:7] + [full]) == 7
+    # a chain that breaks: a message, a link that goes back or stays, a link out of the stream, no link and no end
+    assert ask(0, 8, rows[:3] + [err] + rows[4:]) == "broken"
+    for link in (2, 3, 8, none):
+        assert ask(0, 8, rows[:3] + [ok(link)] + rows[4:]) == "broken", link
+    # rows [2, 6) of a launch's tables: links are rows of the tables
+    assert ask(2, 6, [full, full, ok(4), full, ok(5), (0, 1, none), full]) == "end"
+    assert ask(2, 6, [full, full, ok(4), full, ok(6), (0, 1, none), full]) == "broken"
+    assert ask(2, 6, [full, full, ok(3), full, ok(5), (0, 1, none), full]) == 3
 
 
 def test_symbol_tables_of_one_stream(driver):

@@ -784,7 +784,41 @@ static int pass_run(Workspace *ws, std::vector<PassStream> &ss, bool sub, bool b
     {
         std::vector<std::pair<size_t, size_t>> spans;
         for (size_t k : on) spans.emplace_back(ss[k].pbase, ss[k].starts.size());
-        const RetryPlan retry = plan_retry(res, spans, part_bytes.data(), pp ? piece_cap_retry(pp->q) : 24ull << 30);
+        RetryPlan retry = plan_retry(res, spans, part_bytes.data(), pp ? piece_cap_retry(pp->q) : 24ull << 30);
+        // A piece over its cap: most of what asks may be noise that no chain reaches (decoy stored headers in a stored block's
+        // payload, each promising 65535 bytes to a slot whose slack the piece bounds).  The full parts ON the chain run again
+        // one at a time, each found by following the links so far (first_full_on_chain), in one buffer of the cap's size,
+        // while turns and room last; the stream leaves as before when they do not, or when the chain breaks.
+        if (pp && !retry.over.empty()) {
+            retry.over.clear();
+            PassStream &s = ss[on[0]];
+            const size_t i0 = s.pbase, i1 = s.pbase + s.starts.size();
+            uint8_t *capp = nullptr;
+            uint64_t used = 0;
+            bool over = false;
+            for (int turn = 0;; ++turn) {
+                const size_t i = first_full_on_chain(res, i0, i1);
+                if (i == i1) break;
+                const uint64_t cap = i < i1 ? retry_cap(part_bytes[i]) : 0;
+                over = i > i1 || turn == kChainRetryTurns || (used + cap) * 2 > piece_cap_retry(pp->q) ||
+                       (!capp && scratch_reserve(ws, kScrLargeRetry, piece_cap_retry(pp->q), false, (void **)&capp) != ZNG_ROCM_OK);
+                if (over) break;
+                for (size_t k = 0; k < np; ++k) pj[k].out_cap = 0;
+                slot_ptr[i] = (uint16_t *)capp + used;
+                pj[i].out = (uint8_t *)slot_ptr[i];
+                pj[i].out_cap = cap;
+                used += cap;
+                ZR_HIP(hipMemcpyAsync(d_jobs, pj, np * sizeof(InflateJobDev), hipMemcpyHostToDevice, st));
+                if (int rc = launch_parts()) return rc;
+                // full again: its room goes by the bytes up to the next START, and a noise start a few bytes behind a genuine one
+                // makes that room small while the block runs on past it -- as in plan_retry's one rerun, such a stream leaves
+                if (res[8 * i + 4] == kMsgOutFull) {
+                    over = true;
+                    break;
+                }
+            }
+            if (over) retry.over.push_back(0);
+        }
         for (size_t o : retry.over) {
             if (pp) pp->halve = true;
             leave(ss[on[o]], pp ? "the piece's parts above a ratio of 64 need more scratch than its cap"
@@ -1400,7 +1434,15 @@ static int round_find(Workspace *ws, std::vector<PassStream> &ss, std::vector<st
     ZR_HIP(hipMemcpyAsync(n12, d_n, 8, hipMemcpyDeviceToHost, st));
     ZR_HIP(hipMemcpyAsync(h_good, d_good, (size_t)first * 8, hipMemcpyDeviceToHost, st));
     ZR_HIP(hipStreamSynchronize(st));
-    if (n12[0] > cap1 || n12[1] > cap2) return out("far more candidates in the round than deflate streams have");
+    if (n12[0] > cap1 || n12[1] > cap2) {
+        // One stream's payload can hold more places that pass for a block start than the whole round has room for (a stored
+        // block full of 00 00 ff ff).  That is that stream's trouble, not its neighbours': each half of the round on its own,
+        // down to the stream that has them -- which leaves, as it does in the one-stream call.
+        if (ns == 1) return out("far more candidates in the stream than a deflate stream has");
+        const std::vector<size_t> lower(which.begin(), which.begin() + ns / 2), upper(which.begin() + ns / 2, which.end());
+        if (int rc = round_find(ws, ss, good, lower, patterns, bytes, st)) return rc;
+        return round_find(ws, ss, good, upper, patterns, bytes, st);
+    }
     const uint32_t n2 = n12[1];
     std::vector<unsigned long long> rest;
     if (n2 > first) {

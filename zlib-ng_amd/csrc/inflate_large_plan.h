@@ -248,6 +248,28 @@ inline RetryPlan plan_retry(const uint32_t *res, const std::vector<std::pair<siz
     return r;
 }
 
+// A stream that is over that limit need not leave: a candidate that was noise is never reached, and what is never reached
+// needs no room (a stored block's payload may hold thousands of headers that promise 65535 bytes each, and every one of those
+// parts says kMsgOutFull).  What the CHAIN needs is found by following the links from the stream's first part, rows
+// [i0, i1) of the tables: the row of the first full part on it, i1 when the chain ends (BFINAL, or the input's end in a piece)
+// without one, ~0 when it breaks (a message, a bad link).  pass_run runs that one part again and asks once more.
+// This is a shorter statement of walk_chain, which stays the arbiter of what is delivered: it leaves out the FINAL fixed-code
+// sub-part's early end, `past` and the piece's symbol cap, so it may follow the links FARTHER than walk_chain will.  That is
+// safe: a full part found behind the place where walk_chain stops costs one rerun whose result nobody reads, never a wrong
+// byte; a full part walk_chain reaches is always met here first, because up to there both follow the same links.
+constexpr int kChainRetryTurns = 16;
+inline size_t first_full_on_chain(const uint32_t *res, size_t i0, size_t i1) {
+    for (size_t cur = i0;;) {
+        const uint32_t *r = &res[8 * cur];
+        if (r[4] == kMsgOutFull) return cur;
+        if (r[4] == kMsgStarved) return i1;
+        if (r[4] != kMsgNone) return ~(size_t)0;
+        if (r[3] == 1u) return i1;
+        if (r[6] <= cur || r[6] >= i1) return ~(size_t)0;
+        cur = r[6];
+    }
+}
+
 // ---- the chain from the stream's first part ---------------------------------------------------------------------------
 // Part 0 is genuine, the part that starts where it ended is therefore genuine too, ...; a candidate that was noise is never
 // reached.  Result words of a part (inflate_streams_kernel<PART>): r[0] symbols, r[1..2] the bit it ended on, r[3] = 1 when
