@@ -309,6 +309,25 @@ int    zng_rocm_deflate_strategy_block_dev(int level, int strategy, const uint8_
                                            uint32_t flags, uint8_t *d_out, size_t out_cap, size_t *out_len, void *stream);
 int    zng_rocm_deflate_strategy_streams_dev(int level, int strategy, const zng_rocm_stream_job *jobs, size_t njobs,
                                              size_t *out_lens, void *stream);
+/* The same two with deflateInit2's `windowBits`: the stream is one that a reader with a window of 1 << window_bits bytes can
+ * decode.  For such a reader a distance above its window is a hard error ("invalid distance too far back"), not a loss of ratio.
+ *   range     window_bits is 9..15 (deflate.c:317-318); anything else returns ZNG_ROCM_EINVAL with nothing launched or written.
+ *             8 exists for the zlib wrapper alone (deflate.c:319) and these raw calls have no format: they refuse it.
+ *   cap       no match reaches further back than MAX_DIST(s) = (1 << window_bits) - 262 (deflate.h:410-415): 250, 762, 1786, 3834,
+ *             7930, 16122 for 9..14.  The level's matcher runs in its window form (lz_rows_win_kernel: the cap and the priming
+ *             length are arguments; a segment enters the 1 << window_bits bytes in front of itself, nothing further back can be
+ *             referenced).  Z_RLE, Z_HUFFMAN_ONLY and level 0 write distance 1 or none and give the bytes they give at 15;
+ *             Z_FIXED uses the window form of the matcher.
+ *   15        exactly the bytes of the calls above, through the kernel they have always run (deflate.c:345: w_size 32768).
+ *   history   dict_len up to 32768 is still accepted; history further back than the cap is never referenced (deflate.c:479-484
+ *             keeps the last w_size bytes of a dictionary; what lies in front of them cannot be reached either way).
+ *   bound     zng_rocm_deflate_bound(in_len) holds at every window: the emitter stores a block whenever that is not larger
+ *             (trees.c:660-672), so fewer matches never cost more than the stored form the bound covers. */
+int    zng_rocm_deflate_window_block_dev(int level, int strategy, int window_bits, const uint8_t *d_in, size_t in_len,
+                                         uint32_t dict_len, uint32_t flags, uint8_t *d_out, size_t out_cap, size_t *out_len,
+                                         void *stream);
+int    zng_rocm_deflate_window_streams_dev(int level, int strategy, int window_bits, const zng_rocm_stream_job *jobs, size_t njobs,
+                                           size_t *out_lens, void *stream);
 
 /* ---- inflate: host bitstream decode -> token stream -> device copy resolution -------------
  * The split of slot `inflate_fast` (inffast_tpl.h:53-318): the sequential Huffman decode loop
@@ -596,6 +615,23 @@ int    zng_rocm_compress_members_dev(int format, int level, int strategy, const 
                                      uint8_t *d_dst, size_t dst_cap, size_t round_bytes, uint64_t *d_offsets, uint32_t *d_checks,
                                      void *stream);
 int    zng_rocm_compress_streams2_last_rounds(void);
+/* The two calls above with deflateInit2's `windowBits`, as zng_rocm_deflate_window_streams_dev:
+ *   window_bits  9..15; 8 is accepted for format 1 alone and taken as 9 (deflate.c:319, :322-323: "until 256-byte window bug
+ *                fixed"), so it gives the whole member 9 gives; formats 0 and 2 refuse it.  Anything else: ZNG_ROCM_EINVAL with
+ *                nothing launched or written.
+ *   zlib         CMF = 8 + ((window_bits - 8) << 4), FLEVEL by the rule above, FCHECK over the new CMF (deflate.c:870-885): 0x18..
+ *                for 9, 0x28.. for 10, ... 0x78.. for 15.  A reader opened with a smaller window answers "invalid window size"
+ *                (inflate.c:541-546).
+ *   gzip         has no window field (deflate.c:902-913): only the distances change.
+ *   data         levels 1..9: exactly the bytes zng_rocm_deflate_window_streams_dev writes for the same job list; level 0 as ever.
+ *   15           exactly the bytes of the calls above.
+ * Bounds, results, offsets, rounds and every other refusal are those of the calls above; zng_rocm_compress_streams2_bound holds
+ * at every window because the emitter stores a block whenever that is not larger (trees.c:660-672). */
+int    zng_rocm_compress_streams2_window_dev(int format, int level, int strategy, int window_bits, const zng_rocm_stream_job *jobs,
+                                             size_t njobs, size_t round_bytes, uint32_t *d_results, void *stream);
+int    zng_rocm_compress_members_window_dev(int format, int level, int strategy, int window_bits, const zng_rocm_stream_job *jobs,
+                                            size_t njobs, uint8_t *d_dst, size_t dst_cap, size_t round_bytes, uint64_t *d_offsets,
+                                            uint32_t *d_checks, void *stream);
 
 /* ---- one preset dictionary shared by many small device-resident streams -----------------------------------------------
  * deflateSetDictionary / inflateSetDictionary (deflate.c:456-512, inflate.c:1234-1260) for the many-stream calls above.  The
@@ -1133,6 +1169,13 @@ int    zng_rocm_hook_deflate_block(zng_rocm_hook *h, int level, const uint8_t *i
 int    zng_rocm_hook_deflate_block_strategy(zng_rocm_hook *h, int level, int strategy, const uint8_t *in, size_t in_len,
                                             uint32_t flags, int check, uint32_t *check_value, uint8_t *out, size_t out_cap,
                                             size_t *out_len);
+/* the same block for a stream opened with windowBits `window_bits` (9..15, as zng_rocm_deflate_window_block_dev; the reference
+ * has turned 8 into 9 before a hook sees it, deflate.c:322-323; anything else is ZNG_ROCM_EINVAL).  At 15 it gives the bytes of
+ * the call above.  The hook keeps 32 KiB of history whatever the window; deflateGetDictionary's at-most-w_size rule
+ * (deflate.c:523-527) is the adapter's (rocm_deflate.c) */
+int    zng_rocm_hook_deflate_block_window(zng_rocm_hook *h, int level, int strategy, int window_bits, const uint8_t *in,
+                                          size_t in_len, uint32_t flags, int check, uint32_t *check_value, uint8_t *out,
+                                          size_t out_cap, size_t *out_len);
 /* A complete raw deflate stream (or the rest of one) at `in`, continuing the history: returns 1 (Z_STREAM_END) with the
  * plaintext at *out (host memory owned by the hook, valid until its next call), *out_len, *in_used and the check of the
  * plaintext; -5 when the stream does not end inside in_len (nothing consumed: the adapter gathers more input);

@@ -53,10 +53,11 @@ void Z_INTERNAL PREFIX(archrocm_deflate_end)(PREFIX3(streamp) strm) {           
     memset(a, 0, sizeof *a);
 }
 
-/* what the device takes: every level, every strategy (default, filtered, Z_HUFFMAN_ONLY, Z_RLE, Z_FIXED --
- * zng_rocm_deflate_strategy_block_dev), the 32 KiB window its history is kept for */
+/* what the device takes: every level, every strategy (default, filtered, Z_HUFFMAN_ONLY, Z_RLE, Z_FIXED), every window
+ * deflateInit2 leaves in s->w_bits (9..15: it has turned 8 into 9, deflate.c:322-323) -- zng_rocm_deflate_window_block_dev.
+ * zlib-ng writes the zlib header itself from s->w_bits (deflate.c:870), so the window changes nothing else on the write path */
 static int params_ok(int level, unsigned w_bits, int strategy) {
-    return level >= 0 && level <= 9 && w_bits == 15 && strategy >= ROCM_Z_DEFAULT_STRATEGY && strategy <= ROCM_Z_FIXED;
+    return level >= 0 && level <= 9 && w_bits >= 9 && w_bits <= 15 && strategy >= ROCM_Z_DEFAULT_STRATEGY && strategy <= ROCM_Z_FIXED;
 }
 
 int Z_INTERNAL PREFIX(archrocm_can_deflate)(PREFIX3(streamp) strm) {
@@ -113,9 +114,9 @@ static int produce(PREFIX3(streamp) strm, deflate_state *s, arch_deflate_state *
     size_t clen = 0;
     int rc = ZNG_ROCM_ENODEV;
     if (!a->disabled)
-        rc = zng_rocm_hook_deflate_block_strategy(a->hook, s->level, s->strategy, a->in_buf, a->in_len,
-                                                  final ? 0u : ZNG_ROCM_BLOCK_NOT_FINAL, s->wrap, &cv, a->out_buf, a->out_cap,
-                                                  &clen);
+        rc = zng_rocm_hook_deflate_block_window(a->hook, s->level, s->strategy, (int)s->w_bits, a->in_buf, a->in_len,
+                                                final ? 0u : ZNG_ROCM_BLOCK_NOT_FINAL, s->wrap, &cv, a->out_buf, a->out_cap,
+                                                &clen);
     if (rc != ZNG_ROCM_OK) {                            /* degrade, never surface */
         a->disabled = 1;
         clen = stored_block(a->in_buf, a->in_len, final, a->out_buf);
@@ -185,8 +186,9 @@ int Z_INTERNAL PREFIX(archrocm_deflate)(PREFIX3(streamp) strm, int flush, block_
 
 /* DEFLATE_PARAMS_HOOK (deflate.c:649): level and strategy are read per block, and the Z_BLOCK flush deflateParams makes
  * in front of a change (deflate.c:651-660) has closed the device block on a byte boundary, so a change between settings
- * the device takes needs nothing; leaving them mid-stream (another window size) would need the history back in the
- * software window -- not supported */
+ * the device takes needs nothing.  deflateParams cannot change the window (s->w_bits is deflateInit2's for the stream's life),
+ * and every window and every level and strategy deflateParams accepts is one the device takes, so nothing leaves mid-stream;
+ * if something ever did, the history would have to go back into the software window -- not supported */
 int Z_INTERNAL PREFIX(archrocm_deflate_params)(PREFIX3(streamp) strm, int level, int strategy, int *flush) {
     deflate_state *s = (deflate_state *)strm->state;
     (void)flush;
@@ -212,9 +214,23 @@ int Z_INTERNAL PREFIX(archrocm_deflate_set_dictionary)(PREFIX3(streamp) strm, co
 
 int Z_INTERNAL PREFIX(archrocm_deflate_get_dictionary)(PREFIX3(streamp) strm, unsigned char *dictionary, unsigned *dict_length) {
     deflate_state *s = (deflate_state *)strm->state;
+    /* the reference returns at most w_size bytes, the tail (deflate.c:523-529), and the caller's buffer may be only that large;
+     * the hook keeps and hands back up to 32 KiB whatever the window: fetch into a buffer of our own, copy the tail */
+    const uint32_t w_size = 1u << s->w_bits;
     uint32_t len = 0;
-    if (zng_rocm_hook_get_history(s->arch.hook, dictionary, &len) != ZNG_ROCM_OK) return Z_STREAM_ERROR;
-    if (dict_length) *dict_length = len;
+    if (zng_rocm_hook_get_history(s->arch.hook, NULL, &len) != ZNG_ROCM_OK) return Z_STREAM_ERROR;
+    if (dictionary && len) {
+        uint8_t *tmp = (uint8_t *)arch_alloc(strm, len);
+        if (!tmp) return Z_STREAM_ERROR;
+        if (zng_rocm_hook_get_history(s->arch.hook, tmp, &len) != ZNG_ROCM_OK) {
+            arch_free(strm, tmp);
+            return Z_STREAM_ERROR;
+        }
+        const uint32_t give = len < w_size ? len : w_size;
+        memcpy(dictionary, tmp + (len - give), give);
+        arch_free(strm, tmp);
+    }
+    if (dict_length) *dict_length = len < w_size ? len : w_size;
     return Z_OK;
 }
 

@@ -30,6 +30,7 @@
 #include "compress_streams_plan.h"
 #include "deflate_blocks.h"
 #include "deflate_dev.h"
+#include "deflate_window_plan.h"
 #include "dict_dev.h"
 
 #include <mutex>
@@ -57,12 +58,13 @@ struct CsRound {                        // the arguments the kernels of a round 
     uint32_t      *checks;              // members: d_checks or null
     uint32_t      *results;             // streams2: d_results
     uint32_t       dict, dictid;        // 1: the calls with a shared preset dictionary, whose zlib header carries FDICT and this DICTID
+    int            window_bits;         // the stream's w_bits (deflate_window_plan.h): 15 but for the *_window_dev calls
 };
 
 // bytes of the member's header, and byte k of it
 __device__ __forceinline__ uint32_t cs_round_head(const CsRound &r) { return r.dict ? cs_dict_head_bytes(r.format) : cs_head_bytes(r.format); }
 __device__ __forceinline__ uint8_t cs_round_header_byte(const CsRound &r, uint32_t k) {
-    return r.dict ? cs_dict_header_byte(r.level, r.strategy, r.dictid, k) : cs_header_byte(r.format, r.level, r.strategy, k);
+    return r.dict ? cs_dict_header_byte(r.level, r.strategy, r.dictid, k) : cs_header_byte(r.format, r.level, r.strategy, k, r.window_bits);
 }
 
 __device__ __forceinline__ uint32_t cs_check_of(const CsRound &r, uint32_t i) { return r.check2[2 * i + (r.format == 2 ? 1 : 0)]; }
@@ -192,12 +194,18 @@ void cs_frame_kernel(CsRound r, const BlkJob *__restrict__ blk, const uint32_t *
 
 static thread_local int t_cs_rounds = 0;
 
-// with_dict: the calls with a shared preset dictionary (`dict` is every stream's history), else dict is null
+// with_dict: the calls with a shared preset dictionary (`dict` is every stream's history), else dict is null.  window_bits: as
+// the caller gave it (deflate_window_plan.h); the calls without a window say 15
 static int compress_streams_run(const char *who, bool members, int format, int level, int strategy, const zng_rocm_stream_job *jobs,
                                 size_t njobs, uint8_t *d_dst, size_t dst_cap, size_t round_bytes, uint64_t *d_offsets,
                                 uint32_t *d_checks, uint32_t *d_results, void *stream, bool with_dict = false,
-                                const zng_rocm_dict *dict = nullptr) {
+                                const zng_rocm_dict *dict = nullptr, int window_bits = kWinBitsMax) {
     t_cs_rounds = 0;
+    if (cs_format_ok(format) && win_check(format, window_bits)) {
+        set_error("%s: window_bits %d is outside 9..15 (8: the zlib format alone, deflate.c:319)", who, window_bits);
+        return ZNG_ROCM_EINVAL;
+    }
+    window_bits = cs_format_ok(format) ? win_effective(format, window_bits) : kWinBitsMax;
     const void *res = members ? (const void *)d_offsets : (const void *)d_results;
     int rc = with_dict ? cs_dict_call_check(format, level, strategy, dict, jobs, njobs, res)
                        : cs_call_check(format, level, strategy, jobs, njobs, res);
@@ -300,6 +308,7 @@ static int compress_streams_run(const char *who, bool members, int format, int l
         r.results = d_results;
         r.dict = with_dict ? 1u : 0u;
         r.dictid = with_dict ? dict->id : 0u;
+        r.window_bits = window_bits;
         hipLaunchKernelGGL(cs_check_args_kernel, dim3((r.nj + 255u) / 256u), dim3(256), 0, st, r, ctx()->tables, d_sa, d_fa);
         ZR_HIP(hipGetLastError());
         if ((rc = launch_checksum_batch_device(format != 2, format == 2, d_sa, d_fa, d_part, r.nj, d_chk, st))) return rc;
@@ -307,7 +316,7 @@ static int compress_streams_run(const char *who, bool members, int format, int l
         unsigned long long nblk = h_jobs[last - 1].blk0 + cs_stored_blocks(jobs[last - 1].in_len) - h_jobs[first].blk0;
         if (level) {
             if ((rc = with_dict ? deflate_rows_enqueue_streams_dict(level, strategy, dict, jobs + first, r.nj, seg_bytes, ws, st, &blocks)
-                                : deflate_rows_enqueue_streams(level, strategy, jobs + first, r.nj, seg_bytes, ws, st, &blocks))) {
+                                : deflate_rows_enqueue_streams(level, strategy, jobs + first, r.nj, seg_bytes, ws, st, &blocks, window_bits))) {
                 (void)host_tables_release(ws, st);
                 return rc;
             }
@@ -346,6 +355,21 @@ int zng_rocm_compress_members_dev(int format, int level, int strategy, const zng
                                   size_t dst_cap, size_t round_bytes, uint64_t *d_offsets, uint32_t *d_checks, void *stream) {
     return compress_streams_run("zng_rocm_compress_members_dev", true, format, level, strategy, jobs, njobs, d_dst, dst_cap,
                                 round_bytes, d_offsets, d_checks, nullptr, stream);
+}
+
+// The two calls above at deflateInit2's windowBits (deflate_window_plan.h): levels 1..9 run the window form of the matcher unless
+// window_bits is 15, the zlib header carries CINFO = w - 8
+int zng_rocm_compress_streams2_window_dev(int format, int level, int strategy, int window_bits, const zng_rocm_stream_job *jobs,
+                                          size_t njobs, size_t round_bytes, uint32_t *d_results, void *stream) {
+    return compress_streams_run("zng_rocm_compress_streams2_window_dev", false, format, level, strategy, jobs, njobs, nullptr, 0,
+                                round_bytes, nullptr, nullptr, d_results, stream, false, nullptr, window_bits);
+}
+
+int zng_rocm_compress_members_window_dev(int format, int level, int strategy, int window_bits, const zng_rocm_stream_job *jobs,
+                                         size_t njobs, uint8_t *d_dst, size_t dst_cap, size_t round_bytes, uint64_t *d_offsets,
+                                         uint32_t *d_checks, void *stream) {
+    return compress_streams_run("zng_rocm_compress_members_window_dev", true, format, level, strategy, jobs, njobs, d_dst, dst_cap,
+                                round_bytes, d_offsets, d_checks, nullptr, stream, false, nullptr, window_bits);
 }
 
 size_t zng_rocm_compress_streams2_dict_bound(size_t source_len, int format) { return (size_t)cs_dict_bound(source_len, format); }

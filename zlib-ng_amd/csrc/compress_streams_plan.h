@@ -39,7 +39,9 @@ ZR_HD uint32_t cs_head_bytes(int format) { return wrapper_head_bytes(format); }
 ZR_HD uint32_t cs_tail_bytes(int format) { return wrapper_tail_bytes(format); }
 ZR_HD uint32_t cs_zlib_flevel(int level, int strategy) { return wrapper_zlib_flevel(level, strategy); }
 ZR_HD uint32_t cs_gzip_xfl(int level, int strategy) { return wrapper_gzip_xfl(level, strategy); }
-ZR_HD uint8_t cs_header_byte(int format, int level, int strategy, uint32_t k) { return wrapper_header_byte(format, level, strategy, k); }
+ZR_HD uint8_t cs_header_byte(int format, int level, int strategy, uint32_t k, int window_bits = 15) {
+    return wrapper_header_byte(format, level, strategy, k, window_bits);
+}
 ZR_HD uint8_t cs_trailer_byte(int format, uint32_t k, uint32_t check, uint32_t n) { return wrapper_trailer_byte(format, k, check, n); }
 
 // ---- level 0 ------------------------------------------------------------------------------------------------------------

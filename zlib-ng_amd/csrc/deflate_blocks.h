@@ -50,9 +50,10 @@ int deflate_rows_enqueue_blocks(int level, const zng_rocm_stream_job *sjobs, siz
 // segments of seg_bytes, and the blocks of all segments of a stream follow one another in the table, in_stream[] counting on
 // through the stream.  seg_bytes is what deflate_rows_segment_bytes() gives for the plaintext of the caller's WHOLE call, so that
 // the blocks are those zng_rocm_deflate_strategy_streams_dev writes for the same job list (compress_streams.hip).
+// window_bits: the streams' w_bits, 9..15 (deflate_window_plan.h); below 15 the matcher runs its window form.
 uint32_t deflate_rows_segment_bytes(size_t total_in);
 int deflate_rows_enqueue_streams(int level, int strategy, const zng_rocm_stream_job *sjobs, size_t njobs, uint32_t seg_bytes,
-                                 Workspace *ws, hipStream_t st, RowsBlocks *blocks);
+                                 Workspace *ws, hipStream_t st, RowsBlocks *blocks, int window_bits = 15);
 // The same behind ONE shared preset dictionary (dict_dev.h): every stream's history is the object's window, through the
 // dictionary form of the matcher -- strategies 0, 1 and 4; no job has a dict_len of its own.  The bytes are those of the call
 // above over the window copied in front of every plaintext with dict_len = W.

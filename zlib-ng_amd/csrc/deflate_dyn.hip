@@ -15,6 +15,9 @@
 //        lz_rows_dict_kernel is the same body (deflate_rows_body.h) behind ONE shared preset dictionary: a stream's first
 //        segment loads the window and the row tables its priming leaves from the dictionary object (rows_dict_table_kernel
 //        builds them once) instead of entering up to 32 batches of history that lie in front of the plaintext.
+//        lz_rows_win_kernel is the same body once more for deflateInit2's windowBits 9..14: the distance cap (1 << w) - 262 and
+//        the priming length 1 << w are arguments, so a segment re-inserts 1 << w bytes instead of 32 KiB; windowBits 15 stays
+//        on lz_rows_kernel (deflate_window_plan.h holds the rules).
 //   K2 emit_dynamic_kernel one workgroup per segment = one dynamic-Huffman block: Huffman code lengths from K1's
 //        histogram (rank sort + two-queue merge, depth limit by frequency halving), canonical codes, the RLE-coded
 //        length header (trees.c send_all_trees equivalent), then the body bits assembled in an LDS tile.  Each segment
@@ -31,6 +34,7 @@
 #include "deflate_blocks.h"
 #include "deflate_dev.h"
 #include "deflate_rows.h"
+#include "deflate_window_plan.h"
 #include "dict_dev.h"
 
 #include <mutex>
@@ -92,6 +96,24 @@ void lz_rows_kernel(const SegJob *__restrict__ jobs, unsigned long long *__restr
     constexpr const uint8_t *dwin = nullptr;
     constexpr const uint4 *dtab = nullptr;
     constexpr uint32_t dW = 0u;
+    constexpr uint32_t wdist = kLzMaxDist, wprime = kPrime;
+#include "deflate_rows_body.h"
+}
+
+// The window form (windowBits 9..14, the zng_rocm_*_window_* calls): the same body with the distance cap and the priming
+// length of a smaller window as arguments -- wdist = (1 << w) - 262 = MAX_DIST(s) (deflate.h:410-415), wprime = 1 << w = w_size.
+// A reader with that window refuses a greater distance ("invalid distance too far back", inflate.c), so the cap is a matter
+// of validity, not of ratio.  Ring, rows and workgroup are those of lz_rows_kernel: one workgroup per CU.  windowBits 15 never
+// comes here (deflate_rows_enqueue): its bytes and its speed stay those of lz_rows_kernel by construction.
+__global__ __launch_bounds__(kRowBatch)
+void lz_rows_win_kernel(const SegJob *__restrict__ jobs, unsigned long long *__restrict__ bm_base, uint16_t *__restrict__ d16_base,
+                        uint32_t *__restrict__ hist_out, uint32_t max_cand, unsigned long long *__restrict__ stamp_out,
+                        uint32_t wdist, uint32_t wprime) {
+    __shared__ RowShared sh;
+    constexpr bool DICT = false;
+    constexpr const uint8_t *dwin = nullptr;
+    constexpr const uint4 *dtab = nullptr;
+    constexpr uint32_t dW = 0u;
 #include "deflate_rows_body.h"
 }
 
@@ -103,6 +125,7 @@ void lz_rows_dict_kernel(const SegJob *__restrict__ jobs, unsigned long long *__
                          const uint8_t *__restrict__ dwin, const uint4 *__restrict__ dtab, uint32_t dW) {
     __shared__ __attribute__((aligned(16))) RowShared sh;
     constexpr bool DICT = true;
+    constexpr uint32_t wdist = kLzMaxDist, wprime = kPrime;
 #include "deflate_rows_body.h"
 }
 
@@ -758,10 +781,15 @@ constexpr int kZHuffmanOnly = 2, kZRle = 3, kZFixed = 4;
 // cap_override: out_cap of job 0 when the caller's job struct cannot hold it (a single stream of >= 4 GiB of room).
 // keep: the caller places the blocks itself (deflate_blocks.h) -- K4 and the copy of the results are left out, *keep says where
 // the blocks are, and no job's out / out_cap is looked at.
-static int deflate_rows_enqueue(int level, int strategy, const zng_rocm_stream_job *sjobs, size_t njobs, const size_t *cap_override,
-                                uint32_t seg_bytes, Workspace *ws, hipStream_t st, unsigned long long **results,
-                                unsigned long long *d_results_copy = nullptr, RowsBlocks *keep = nullptr,
-                                const zng_rocm_dict *dobj = nullptr) {
+// window_bits: the streams' w_bits, 9..15, already checked (deflate_window_plan.h).  Below 15 the matcher is its window form;
+// Z_RLE and Z_HUFFMAN_ONLY write distance 1 or none and need nothing.  The dictionary form knows the 32 KiB window alone.
+static int deflate_rows_enqueue(int level, int strategy, int window_bits, const zng_rocm_stream_job *sjobs, size_t njobs,
+                                const size_t *cap_override, uint32_t seg_bytes, Workspace *ws, hipStream_t st,
+                                unsigned long long **results, unsigned long long *d_results_copy = nullptr,
+                                RowsBlocks *keep = nullptr, const zng_rocm_dict *dobj = nullptr) {
+    static_assert(kWinBatch == (uint32_t)kRowBatch && kWinPrimeMax == kPrime && kWinMinLookahead == kMinLookahead &&
+                  32768u - kWinMinLookahead == kLzMaxDist, "deflate_window_plan.h describes the matcher of deflate_rows.h");
+    if (win_effective(0, window_bits) == 0 || (dobj && win_form(window_bits))) return ZNG_ROCM_EINVAL;
     size_t nseg = 0;
     for (size_t s = 0; s < njobs; ++s) nseg += sjobs[s].in_len ? ((size_t)sjobs[s].in_len + seg_bytes - 1) / seg_bytes : 1;
     const size_t max_blk = nseg * kMaxSub;
@@ -860,6 +888,9 @@ static int deflate_rows_enqueue(int level, int strategy, const zng_rocm_stream_j
         ZR_LAUNCH_TRACED(rle_rows_kernel<true>, dim3((unsigned)nseg), dim3(kRleThreads), st, d_jobs, d_bm, d_d16, d_hist);
     else if (strategy == kZRle)
         ZR_LAUNCH_TRACED(rle_rows_kernel<false>, dim3((unsigned)nseg), dim3(kRleThreads), st, d_jobs, d_bm, d_d16, d_hist);
+    else if (win_form(window_bits))
+        ZR_LAUNCH_TRACED(lz_rows_win_kernel, dim3((unsigned)nseg), dim3(kRowBatch), st, d_jobs, d_bm, d_d16, d_hist, kLevelCand[level],
+                         g_rows_stamps, win_dist(window_bits), win_prime(window_bits));
     else if (dobj)
         ZR_LAUNCH_TRACED(lz_rows_dict_kernel, dim3((unsigned)nseg), dim3(kRowBatch), st, d_jobs, d_bm, d_d16, d_hist, kLevelCand[level],
                          g_rows_stamps, (const uint8_t *)dobj->d_window, (const uint4 *)dobj->d_rows, dobj->window);
@@ -891,15 +922,15 @@ static int deflate_rows_enqueue(int level, int strategy, const zng_rocm_stream_j
 int deflate_rows_enqueue_blocks(int level, const zng_rocm_stream_job *sjobs, size_t njobs, Workspace *ws, hipStream_t st,
                                 RowsBlocks *blocks) {
     unsigned long long *unused = nullptr;
-    return deflate_rows_enqueue(level, 0, sjobs, njobs, nullptr, kSegBytesMin, ws, st, &unused, nullptr, blocks);
+    return deflate_rows_enqueue(level, 0, kWinBitsMax, sjobs, njobs, nullptr, kSegBytesMin, ws, st, &unused, nullptr, blocks);
 }
 
 uint32_t deflate_rows_segment_bytes(size_t total_in) { return segment_bytes(total_in, ctx()->cus); }
 
 int deflate_rows_enqueue_streams(int level, int strategy, const zng_rocm_stream_job *sjobs, size_t njobs, uint32_t seg_bytes,
-                                 Workspace *ws, hipStream_t st, RowsBlocks *blocks) {
+                                 Workspace *ws, hipStream_t st, RowsBlocks *blocks, int window_bits) {
     unsigned long long *unused = nullptr;
-    return deflate_rows_enqueue(level, strategy, sjobs, njobs, nullptr, seg_bytes, ws, st, &unused, nullptr, blocks);
+    return deflate_rows_enqueue(level, strategy, window_bits, sjobs, njobs, nullptr, seg_bytes, ws, st, &unused, nullptr, blocks);
 }
 
 // the shared window of `dict` is every stream's history (strategies 0, 1 and 4: the matcher's dictionary form); a job's own
@@ -907,7 +938,7 @@ int deflate_rows_enqueue_streams(int level, int strategy, const zng_rocm_stream_
 int deflate_rows_enqueue_streams_dict(int level, int strategy, const zng_rocm_dict *dict, const zng_rocm_stream_job *sjobs,
                                       size_t njobs, uint32_t seg_bytes, Workspace *ws, hipStream_t st, RowsBlocks *blocks) {
     unsigned long long *unused = nullptr;
-    return deflate_rows_enqueue(level, strategy, sjobs, njobs, nullptr, seg_bytes, ws, st, &unused, nullptr, blocks, dict);
+    return deflate_rows_enqueue(level, strategy, kWinBitsMax, sjobs, njobs, nullptr, seg_bytes, ws, st, &unused, nullptr, blocks, dict);
 }
 
 int launch_rows_dict_table(const uint8_t *d_window, uint32_t W, void *d_tab, hipStream_t st) {
@@ -941,13 +972,20 @@ int zng_rocm_deflate_dev(int level, const uint8_t *d_in, size_t in_len, uint8_t 
 
 int zng_rocm_deflate_block_dev(int level, const uint8_t *d_in, size_t in_len, uint32_t dict_len, uint32_t flags,
                                uint8_t *d_out, size_t out_cap, size_t *out_len, void *stream) {
-    return zng_rocm_deflate_strategy_block_dev(level, 0, d_in, in_len, dict_len, flags, d_out, out_cap, out_len, stream);
+    return zng_rocm_deflate_window_block_dev(level, 0, kWinBitsMax, d_in, in_len, dict_len, flags, d_out, out_cap, out_len, stream);
 }
 
 // Level 0 is stored blocks whatever the strategy (deflate.c:1039-1043 tests the level first); Z_HUFFMAN_ONLY and Z_RLE
 // replace the matcher (deflate_rle.h), Z_FIXED restricts the block types to stored / static (emit_dynamic_kernel<true>).
 int zng_rocm_deflate_strategy_block_dev(int level, int strategy, const uint8_t *d_in, size_t in_len, uint32_t dict_len,
                                         uint32_t flags, uint8_t *d_out, size_t out_cap, size_t *out_len, void *stream) {
+    return zng_rocm_deflate_window_block_dev(level, strategy, kWinBitsMax, d_in, in_len, dict_len, flags, d_out, out_cap, out_len, stream);
+}
+
+// The same at deflateInit2's windowBits (deflate_window_plan.h: 9..15; a raw stream has no 8, deflate.c:319).  15 is the call
+// above: lz_rows_kernel, the same bytes.  Below it the matcher is lz_rows_win_kernel with MAX_DIST(s) = (1 << w) - 262 as its cap.
+int zng_rocm_deflate_window_block_dev(int level, int strategy, int window_bits, const uint8_t *d_in, size_t in_len, uint32_t dict_len,
+                                      uint32_t flags, uint8_t *d_out, size_t out_cap, size_t *out_len, void *stream) {
     if (!ctx()) {
         set_error("zng_rocm_init() has not succeeded");
         return ZNG_ROCM_ENODEV;
@@ -959,6 +997,10 @@ int zng_rocm_deflate_strategy_block_dev(int level, int strategy, const uint8_t *
     }
     if (strategy < 0 || strategy > kZFixed) {
         set_error("strategy %d is outside 0..4", strategy);
+        return ZNG_ROCM_EINVAL;
+    }
+    if (win_check(0, window_bits)) {
+        set_error("window_bits %d is outside 9..15", window_bits);
         return ZNG_ROCM_EINVAL;
     }
     if (dict_len > kPrime || (flags & ~(uint32_t)(ZNG_ROCM_BLOCK_NOT_FINAL | ZNG_ROCM_BLOCK_SYNC_FLUSH))) {
@@ -1012,7 +1054,7 @@ int zng_rocm_deflate_strategy_block_dev(int level, int strategy, const uint8_t *
     one.dict_len = dict_len;
     one.flags = flags;
     unsigned long long *res = nullptr;
-    if (int rc = deflate_rows_enqueue(level, strategy, &one, 1, &out_cap, (uint32_t)seg_bytes, ws, st, &res)) return rc;
+    if (int rc = deflate_rows_enqueue(level, strategy, window_bits, &one, 1, &out_cap, (uint32_t)seg_bytes, ws, st, &res)) return rc;
     ZR_HIP(hipStreamSynchronize(st));
     if (res[1]) {
         set_error("compressed size %llu exceeds out_cap", res[0]);
@@ -1051,7 +1093,7 @@ int zng_rocm_deflate_async_dev(int level, const uint8_t *d_in, size_t in_len, ui
     one.dict_len = dict_len;
     one.flags = flags;
     unsigned long long *res = nullptr;
-    return deflate_rows_enqueue(level, 0, &one, 1, &out_cap, segment_bytes(in_len, ctx()->cus), ws, st, &res,
+    return deflate_rows_enqueue(level, 0, kWinBitsMax, &one, 1, &out_cap, segment_bytes(in_len, ctx()->cus), ws, st, &res,
                                 (unsigned long long *)d_result);
 }
 
@@ -1065,12 +1107,22 @@ int zng_rocm_deflate_streams_dev(int level, const zng_rocm_stream_job *sjobs, si
 
 int zng_rocm_deflate_strategy_streams_dev(int level, int strategy, const zng_rocm_stream_job *sjobs, size_t njobs,
                                           size_t *out_lens, void *stream) {
+    return zng_rocm_deflate_window_streams_dev(level, strategy, kWinBitsMax, sjobs, njobs, out_lens, stream);
+}
+
+// the same at deflateInit2's windowBits, 9..15, as zng_rocm_deflate_window_block_dev
+int zng_rocm_deflate_window_streams_dev(int level, int strategy, int window_bits, const zng_rocm_stream_job *sjobs, size_t njobs,
+                                        size_t *out_lens, void *stream) {
     if (!ctx()) {
         set_error("zng_rocm_init() has not succeeded");
         return ZNG_ROCM_ENODEV;
     }
     if (strategy < 0 || strategy > kZFixed) {
         set_error("strategy %d is outside 0..4", strategy);
+        return ZNG_ROCM_EINVAL;
+    }
+    if (win_check(0, window_bits)) {
+        set_error("window_bits %d is outside 9..15", window_bits);
         return ZNG_ROCM_EINVAL;
     }
     if (!njobs) return ZNG_ROCM_OK;
@@ -1110,7 +1162,7 @@ int zng_rocm_deflate_strategy_streams_dev(int level, int strategy, const zng_roc
             ++last;
         }
         unsigned long long *res = nullptr;
-        if (int rc = deflate_rows_enqueue(level, strategy, sjobs + first, last - first, nullptr, seg_bytes, ws, st, &res)) return rc;
+        if (int rc = deflate_rows_enqueue(level, strategy, window_bits, sjobs + first, last - first, nullptr, seg_bytes, ws, st, &res)) return rc;
         ZR_HIP(hipStreamSynchronize(st));
         for (size_t s = first; s < last; ++s) {
             if (res[2 * (s - first) + 1]) {

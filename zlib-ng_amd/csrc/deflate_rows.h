@@ -285,8 +285,12 @@ __device__ __forceinline__ void rows_front(uint32_t n, uint32_t P, RowShared *sh
     f.PC = *reinterpret_cast<const uint4 *>(&sh->pos[row * kRowEnt]);
 }
 
+// wdist: the furthest a match may reach back, MAX_DIST(s) of the stream's window (deflate.h:410-415).  It is read HERE ONLY:
+// the candidates of the running batch (tC), the row in front of the batch (mA) and the near probe all go through dmax, and
+// nothing else produces a distance.  lz_rows_kernel and lz_rows_dict_kernel pass the compile-time kLzMaxDist, the window
+// form (lz_rows_win_kernel) its argument.
 __device__ __forceinline__ RowsMatch rows_compare(uint32_t n, uint32_t P, uint32_t P0, const RowShared *sh, int t,
-                                                  uint32_t max_cand, const RowsFront &f) {
+                                                  uint32_t max_cand, const RowsFront &f, const uint32_t wdist) {
     const uint8_t *ring = sh->ring;
     const uint32_t p = P + (uint32_t)t;
     const uint32_t pi = p & (kRingBytes - 1u);
@@ -294,7 +298,7 @@ __device__ __forceinline__ RowsMatch rows_compare(uint32_t n, uint32_t P, uint32
     uint32_t best = 3, dist = 0;                         // a match must reach WANT_MIN_MATCH to count
     if (f.can) {
         const uint32_t back = p - P0;                    // bytes of history the ring really holds
-        const uint32_t dmax = back < kLzMaxDist ? back : kLzMaxDist;
+        const uint32_t dmax = back < wdist ? back : wdist;
         uint32_t dC[4], dA[4];
         const uint32_t tC = (uint32_t)t < dmax ? (uint32_t)t : dmax;
         uint32_t mC = rows_candidates(f.TC, f.PC, f.tag, p, tC, dC);

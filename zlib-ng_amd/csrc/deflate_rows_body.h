@@ -12,6 +12,10 @@
 //                            tokens are those of lz_rows_kernel over the window copied in front of the plaintext.
 //   dwin, dtab, dW           the object's window (16-byte aligned, zero padded), its tables (pos | tag | cnt) and W; null / 0
 //                            without DICT
+//   wdist, wprime            the window: the furthest a match reaches back (MAX_DIST(s), deflate.h:410-415; read in rows_compare
+//                            alone) and the bytes of history a segment enters in front of itself.  lz_rows_kernel and
+//                            lz_rows_dict_kernel define them as the compile-time constants kLzMaxDist and kPrime; the window form
+//                            (lz_rows_win_kernel, windowBits 9..14) takes them as arguments: (1 << w) - 262 and 1 << w.
 // Textual sharing keeps lz_rows_kernel the very function it was: same arguments, same attributes, same code.
     const SegJob job = jobs[blockIdx.x];
     const uint8_t *in = job.in;
@@ -50,7 +54,7 @@
         sh.tot_l = sh.tot_d = 0;
     }
 
-    uint32_t P0 = job.seg_start > kPrime ? job.seg_start - kPrime : 0u;
+    uint32_t P0 = job.seg_start > wprime ? job.seg_start - wprime : 0u;
     P0 -= P0 % kRowBatch;
     const uint32_t first = job.seg_start - job.seg_start % kRowBatch;   // batch holding the segment's first byte
     unsigned long long *bm = bm_base + job.bm_off;
@@ -176,7 +180,7 @@
             if ((ph == 0) == parse_first) {
                 if (have_prev) CH = rows_parse(n, P_prev, &sh, t, prev);
             } else if (live) {
-                cur = rows_compare(n, P, P0, &sh, t, max_cand, f);      // P0: the lowest position the ring holds
+                cur = rows_compare(n, P, P0, &sh, t, max_cand, f, wdist);       // P0: the lowest position the ring holds
             }
         }
         if (have_prev) {

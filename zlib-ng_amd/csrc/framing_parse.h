@@ -44,10 +44,11 @@ ZR_HD uint32_t wrapper_zlib_flevel(int level, int strategy) {
 }
 ZR_HD uint32_t wrapper_gzip_xfl(int level, int strategy) { return level == 9 ? 2u : (strategy >= 2 || level < 2) ? 4u : 0u; }
 
-// byte k (0 .. wrapper_head_bytes - 1) of the header
-ZR_HD uint8_t wrapper_header_byte(int format, int level, int strategy, uint32_t k) {
+// byte k (0 .. wrapper_head_bytes - 1) of the header.  window_bits: the stream's w_bits, 9..15 (deflate.c:870: CINFO = w_bits - 8;
+// the writers without a window say nothing and mean 15); gzip has no window field
+ZR_HD uint8_t wrapper_header_byte(int format, int level, int strategy, uint32_t k, int window_bits = 15) {
     if (format == 1) {
-        uint32_t header = ((8u + (7u << 4)) << 8) | (wrapper_zlib_flevel(level, strategy) << 6);     // Z_DEFLATED, w_bits 15
+        uint32_t header = ((8u + ((uint32_t)(window_bits - 8) << 4)) << 8) | (wrapper_zlib_flevel(level, strategy) << 6);     // Z_DEFLATED, w_bits
         header += 31u - header % 31u;
         return (uint8_t)(header >> (k == 0u ? 8 : 0));
     }

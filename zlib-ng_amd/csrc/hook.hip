@@ -232,9 +232,17 @@ int zng_rocm_hook_deflate_block(zng_rocm_hook *h, int level, const uint8_t *in, 
 int zng_rocm_hook_deflate_block_strategy(zng_rocm_hook *h, int level, int strategy, const uint8_t *in, size_t in_len,
                                          uint32_t flags, int check, uint32_t *check_value, uint8_t *out, size_t out_cap,
                                          size_t *out_len) {
+    return zng_rocm_hook_deflate_block_window(h, level, strategy, 15, in, in_len, flags, check, check_value, out, out_cap, out_len);
+}
+
+// the same block at the stream's w_bits (9..15, zng_rocm_deflate_window_block_dev): the history the hook keeps is 32 KiB
+// whatever the window, the matcher reaches no further back than (1 << window_bits) - 262
+int zng_rocm_hook_deflate_block_window(zng_rocm_hook *h, int level, int strategy, int window_bits, const uint8_t *in, size_t in_len,
+                                       uint32_t flags, int check, uint32_t *check_value, uint8_t *out, size_t out_cap,
+                                       size_t *out_len) {
     if (stale(h)) return ZNG_ROCM_ENODEV;
     if (!out || !out_len || (in_len && !in) || (check && !check_value) || check < 0 || check > 2 || strategy < 0 ||
-        strategy > 4)
+        strategy > 4 || window_bits < 9 || window_bits > 15)
         return ZNG_ROCM_EINVAL;
     DeviceGuard dev;
     if (int rc = grow_device(&h->d_in, &h->in_cap, in_len, kHist)) return rc;
@@ -248,8 +256,8 @@ int zng_rocm_hook_deflate_block_strategy(zng_rocm_hook *h, int level, int strate
         ZR_HIP(hipMemcpyAsync(h->h_check, h->d_check, 4, hipMemcpyDeviceToHost, h->st));
     }
     size_t clen = 0;
-    if (int rc = zng_rocm_deflate_strategy_block_dev(level, strategy, h->d_in + kHist, in_len, h->hist_len, flags, h->d_out,
-                                                     h->out_cap, &clen, h->st))
+    if (int rc = zng_rocm_deflate_window_block_dev(level, strategy, window_bits, h->d_in + kHist, in_len, h->hist_len, flags, h->d_out,
+                                                   h->out_cap, &clen, h->st))
         return rc;
     if (clen > out_cap) {
         set_error("compressed block (%zu bytes) exceeds out_cap", clen);

@@ -174,9 +174,14 @@ class StreamsBatch:
             self.jobs[i].out_cap = self.bounds[i]
         self.out_lens = (C.c_size_t * self.n)()
 
-    def run(self, level=6, stream=None, strategy=0):
-        """strategy: zlib's (Z_DEFAULT_STRATEGY 0, Z_FILTERED 1, Z_HUFFMAN_ONLY 2, Z_RLE 3, Z_FIXED 4)"""
-        if strategy:
+    def run(self, level=6, stream=None, strategy=0, window_bits=15):
+        """strategy: zlib's (Z_DEFAULT_STRATEGY 0, Z_FILTERED 1, Z_HUFFMAN_ONLY 2, Z_RLE 3, Z_FIXED 4).  window_bits: deflateInit2's
+        windowBits, 9..15 -- no match reaches further back than (1 << window_bits) - 262 (zng_rocm_deflate_window_streams_dev)"""
+        if window_bits != 15:
+            rc = rocm.lib().zng_rocm_deflate_window_streams_dev(level, strategy, int(window_bits), C.byref(self.jobs), self.n,
+                                                                 C.byref(self.out_lens), rocm._stream_ptr(stream))
+            rocm._check(rc, "zng_rocm_deflate_window_streams_dev")
+        elif strategy:
             rc = rocm.lib().zng_rocm_deflate_strategy_streams_dev(level, strategy, C.byref(self.jobs), self.n,
                                                                    C.byref(self.out_lens), rocm._stream_ptr(stream))
             rocm._check(rc, "zng_rocm_deflate_strategy_streams_dev")
@@ -190,18 +195,23 @@ class StreamsBatch:
         return self.dst[o:o + int(self.out_lens[i])].cpu().numpy().tobytes()
 
 
-def deflate_dev(src, level=6, length=None, offset=0, stream=None, dict_len=0, flags=0, strategy=0):
+def deflate_dev(src, level=6, length=None, offset=0, stream=None, dict_len=0, flags=0, strategy=0, window_bits=15):
     """one large device-resident stream (or, with dict_len / flags, one BLOCK of a longer stream whose dict_len
     bytes of history sit in src in front of `offset`) -> (uint8 CUDA tensor with raw deflate, compressed length).
     level 0 = stored, 1 = single probe, 2..9 = chain walk.  strategy: zlib's (0 default, 1 Z_FILTERED, 2 Z_HUFFMAN_ONLY,
-    3 Z_RLE, 4 Z_FIXED; zng_rocm_deflate_strategy_block_dev)."""
+    3 Z_RLE, 4 Z_FIXED; zng_rocm_deflate_strategy_block_dev).  window_bits: deflateInit2's windowBits, 9..15
+    (zng_rocm_deflate_window_block_dev)."""
     import torch
     rocm._need_init()
     n = src.numel() - offset if length is None else length
     cap = deflate_bound(n)
     dst = torch.empty(cap, dtype=torch.uint8, device=src.device)
     out_len = C.c_size_t(0)
-    if strategy:
+    if window_bits != 15:
+        rc = rocm.lib().zng_rocm_deflate_window_block_dev(level, strategy, int(window_bits), rocm._dev_ptr(src, offset), n, dict_len,
+                                                          flags, rocm._dev_ptr(dst), cap, C.byref(out_len), rocm._stream_ptr(stream))
+        rocm._check(rc, "zng_rocm_deflate_window_block_dev")
+    elif strategy:
         rc = rocm.lib().zng_rocm_deflate_strategy_block_dev(level, strategy, rocm._dev_ptr(src, offset), n, dict_len, flags,
                                                             rocm._dev_ptr(dst), cap, C.byref(out_len), rocm._stream_ptr(stream))
         rocm._check(rc, "zng_rocm_deflate_strategy_block_dev")
@@ -277,21 +287,35 @@ def stream_jobs(srcs, dsts=None, dict_len=None, flags=None):
     return jobs
 
 
-def compress_streams2_dev(jobs, njobs, results, fmt, level=-1, strategy=0, round_bytes=0, stream=None):
+def compress_streams2_dev(jobs, njobs, results, fmt, level=-1, strategy=0, round_bytes=0, stream=None, window_bits=15):
     """zng_rocm_compress_streams2_dev: every job deflated at `level` (-1 = 6, 0..9) and `strategy` (0..4) and wrapped (fmt 0 raw,
     1 zlib, 2 gzip) into its own buffer; `results` an int32 CUDA tensor [njobs, 2] = {bytes written, check value}, valid once
-    `stream` has got there.  Returns the status (0, ZNG_ROCM_E*, -5)."""
+    `stream` has got there.  window_bits: deflateInit2's windowBits, 9..15 (8 for fmt 1: taken as 9);
+    zng_rocm_compress_streams2_window_dev when it is not 15.  Returns the status (0, ZNG_ROCM_E*, -5)."""
     rocm._need_init()
+    if window_bits != 15:
+        return rocm.lib().zng_rocm_compress_streams2_window_dev(int(fmt), int(level), int(strategy), int(window_bits), C.byref(jobs),
+                                                                int(njobs), int(round_bytes),
+                                                                rocm._dev_ptr(results) if results is not None else None,
+                                                                rocm._stream_ptr(stream))
     return rocm.lib().zng_rocm_compress_streams2_dev(int(fmt), int(level), int(strategy), C.byref(jobs), int(njobs), int(round_bytes),
                                                      rocm._dev_ptr(results) if results is not None else None, rocm._stream_ptr(stream))
 
 
-def compress_members_dev(jobs, njobs, dst, offsets, fmt, level=-1, strategy=0, round_bytes=0, checks=None, stream=None):
+def compress_members_dev(jobs, njobs, dst, offsets, fmt, level=-1, strategy=0, round_bytes=0, checks=None, stream=None,
+                         window_bits=15):
     """zng_rocm_compress_members_dev: the members back to back in the uint8 CUDA tensor `dst` (dst.numel() is dst_cap; None: no
     destination); `offsets` an int64 CUDA tensor of njobs + 1 (member starts, then the file's length -- above dst_cap when the
-    file did not fit), `checks` an int32 CUDA tensor of njobs or None.  Returns the status."""
+    file did not fit), `checks` an int32 CUDA tensor of njobs or None.  window_bits as compress_streams2_dev
+    (zng_rocm_compress_members_window_dev when it is not 15).  Returns the status."""
     rocm._need_init()
     cap = int(dst.numel()) if dst is not None else 0
+    if window_bits != 15:
+        return rocm.lib().zng_rocm_compress_members_window_dev(int(fmt), int(level), int(strategy), int(window_bits), C.byref(jobs),
+                                                               int(njobs), rocm._dev_ptr(dst) if cap else None, cap, int(round_bytes),
+                                                               rocm._dev_ptr(offsets) if offsets is not None else None,
+                                                               rocm._dev_ptr(checks) if checks is not None else None,
+                                                               rocm._stream_ptr(stream))
     return rocm.lib().zng_rocm_compress_members_dev(int(fmt), int(level), int(strategy), C.byref(jobs), int(njobs),
                                                     rocm._dev_ptr(dst) if cap else None, cap, int(round_bytes),
                                                     rocm._dev_ptr(offsets) if offsets is not None else None,

@@ -89,6 +89,9 @@ _PROTOS = {
     "zng_rocm_deflate_strategy_block_dev": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
                                                       C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]),
     "zng_rocm_deflate_strategy_streams_dev": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "zng_rocm_deflate_window_block_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
+                                                    C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]),
+    "zng_rocm_deflate_window_streams_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "zng_rocm_inflate_tokens_decode": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "zng_rocm_inflate_tokens_decode_window": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
     "zng_rocm_inflate_tokens_decode_blocks": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint32, C.c_void_p,
@@ -112,6 +115,10 @@ _PROTOS = {
     "zng_rocm_compress_members_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                                 C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "zng_rocm_compress_streams2_last_rounds": (C.c_int, []),
+    "zng_rocm_compress_streams2_window_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t,
+                                                        C.c_void_p, C.c_void_p]),
+    "zng_rocm_compress_members_window_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                       C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "zng_rocm_dict_create_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "zng_rocm_dict_destroy": (None, [C.c_void_p]),
     "zng_rocm_dict_id": (C.c_uint32, [C.c_void_p]),
@@ -211,6 +218,9 @@ _PROTOS = {
     "zng_rocm_hook_deflate_block_strategy": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_uint32,
                                                        C.c_int, C.POINTER(C.c_uint32), C.c_void_p, C.c_size_t,
                                                        C.POINTER(C.c_size_t)]),
+    "zng_rocm_hook_deflate_block_window": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_uint32,
+                                                     C.c_int, C.POINTER(C.c_uint32), C.c_void_p, C.c_size_t,
+                                                     C.POINTER(C.c_size_t)]),
     "zng_rocm_hook_inflate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_uint32),
                                         C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                         C.POINTER(C.c_char_p)]),
