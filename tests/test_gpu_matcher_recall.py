@@ -31,7 +31,7 @@ from gpu_common import product, torch_mod
 pytestmark = pytest.mark.gpu
 
 LEVELS = tuple(range(1, 10))
-LEVEL_CAND = (0, 1, 2, 3, 6, 8, 16, 16, 16, 16)     # kLevelCand, zlib-ng_amd/csrc/deflate_dyn.hip:745
+LEVEL_CAND = (0, 1, 2, 3, 6, 8, 16, 16, 16, 16)     # kLevelCand, zlib-ng_amd/csrc/deflate_dyn.hip:728
 ROW_ENTRIES = 8                                     # kRowEnt, deflate_rows.h:38: a row cannot hold more candidates
 MIN_MATCH = 4                                       # kLzMinMatch, deflate_lz.h:32
 

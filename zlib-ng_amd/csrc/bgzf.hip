@@ -304,7 +304,11 @@ int zng_rocm_bgzf_compress_dev(int level, const uint8_t *d_src, size_t src_len, 
                 kind = 1;
             } else {
                 std::lock_guard<std::mutex> use(ws->mu);
-                if (int rc = deflate_rows_enqueue_blocks(level, sj.data(), np, ws, st, &blocks)) return rc;
+                // every piece is short enough for one segment
+                const RowsRequest rq = {level, 0, kWinBitsMax, sj.data(), np, kSegBytesMin, nullptr, nullptr, kRowsOutKeep, nullptr};
+                RowsDone done;
+                if (int rc = deflate_rows_enqueue(rq, ws, st, &done)) return rc;
+                blocks = done.blocks;
                 lens = blocks.sizes;
                 kind = 2;
             }

@@ -315,11 +315,14 @@ static int compress_streams_run(const char *who, bool members, int format, int l
         RowsBlocks blocks = {nullptr, nullptr, nullptr, nullptr, 0};
         unsigned long long nblk = h_jobs[last - 1].blk0 + cs_stored_blocks(jobs[last - 1].in_len) - h_jobs[first].blk0;
         if (level) {
-            if ((rc = with_dict ? deflate_rows_enqueue_streams_dict(level, strategy, dict, jobs + first, r.nj, seg_bytes, ws, st, &blocks)
-                                : deflate_rows_enqueue_streams(level, strategy, jobs + first, r.nj, seg_bytes, ws, st, &blocks, window_bits))) {
+            const RowsRequest rq = {level, strategy, window_bits, jobs + first, r.nj, seg_bytes, nullptr, with_dict ? dict : nullptr,
+                                    kRowsOutKeep, nullptr};
+            RowsDone done;
+            if ((rc = deflate_rows_enqueue(rq, ws, st, &done))) {
                 (void)host_tables_release(ws, st);
                 return rc;
             }
+            blocks = done.blocks;
             r.sizes = blocks.sizes;
             nblk = blocks.nblk;
         }

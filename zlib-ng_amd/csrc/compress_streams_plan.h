@@ -14,6 +14,7 @@
 #include <stdint.h>
 
 #include "../../include/zng_rocm.h"
+#include "deflate_rows_plan.h" // the engine's bound, its dictionary limit, the round cut
 #include "framing_parse.h"     // the wrapper's rules
 #include "gf2.h"      // ZR_HD
 
@@ -21,7 +22,7 @@ namespace zr {
 
 constexpr uint32_t kCsMaxStored = 65535u;             // MAX_STORED: the most one stored block holds (deflate_stored.c:22)
 constexpr uint32_t kCsStoredHead = 5u;                // BFINAL/BTYPE byte, LEN, NLEN (RFC 1951 3.2.4)
-constexpr uint32_t kCsDictMax = 32768u;
+constexpr uint32_t kCsDictMax = kPrime;
 constexpr uint32_t kCsBlockFlags = ZNG_ROCM_BLOCK_NOT_FINAL | ZNG_ROCM_BLOCK_SYNC_FLUSH;
 constexpr uint64_t kCsRoundDefault = 4ull << 30;      // plaintext per round when the caller says 0
 constexpr int      kCsBufError = -5;                  // Z_BUF_ERROR
@@ -67,12 +68,8 @@ ZR_HD uint8_t cs_stored_byte(uint32_t k, uint32_t len, bool final_block) {
 }
 
 // ---- the bounds ---------------------------------------------------------------------------------------------------------
-// zng_rocm_deflate_bound: what the rows engine may write for n bytes cut into segments of 128 KiB, the smallest there are
-// (1032 bytes of block overhead per segment); covers the stored form
-inline uint64_t cs_deflate_bound(uint64_t n) {
-    const uint64_t nseg = n ? (n + (128u << 10) - 1u) / (128u << 10) : 1u;
-    return n + n / 8u + nseg * 1032u + 16u;
-}
+// zng_rocm_deflate_bound (deflate_rows_plan.h); covers the stored form
+inline uint64_t cs_deflate_bound(uint64_t n) { return rows_deflate_bound(n); }
 // zng_rocm_compress_bound: + ZLIB_WRAPLEN 6 / GZIP_WRAPLEN 18 (zutil.h:68-69)
 inline uint64_t cs_bound(uint64_t n, int format) { return cs_deflate_bound(n) + (format == 1 ? 6u : format == 2 ? 18u : 0u); }
 
@@ -156,10 +153,7 @@ inline int cs_dict_jobs_check(int format, const zng_rocm_stream_job *jobs, uint6
 // the round that begins at job `first` ends in front of the job returned: jobs are taken while their plaintext stays within
 // round_bytes (0 = 4 GiB); a job is never split, so a round has at least one job, however long
 inline uint64_t cs_round_end(const zng_rocm_stream_job *jobs, uint64_t njobs, uint64_t first, uint64_t round_bytes) {
-    const uint64_t room = round_bytes ? round_bytes : kCsRoundDefault;
-    uint64_t last = first, bytes = 0;
-    while (last < njobs && (last == first || bytes + jobs[last].in_len <= room)) bytes += jobs[last++].in_len;
-    return last;
+    return rows_round_end(jobs, njobs, first, round_bytes ? round_bytes : kCsRoundDefault, false);
 }
 inline uint64_t cs_rounds(const zng_rocm_stream_job *jobs, uint64_t njobs, uint64_t round_bytes) {
     uint64_t rounds = 0;

@@ -50,14 +50,13 @@ struct Partial {            // one per workgroup, written by the streaming kerne
 enum ScratchSlot {
     kScrQuickJobs = 0,      // device: StreamJobDev[] of zng_rocm_deflate_quick_dev
     kScrQuickJobsHost,      // pinned host mirror of the same (async H2D source)
-    kScrDynJobs,            // device: SegJob[] of zng_rocm_deflate_dev
-    kScrDynJobsHost,        // pinned
-    kScrDynSel,             // device: one 32-bit selector per input byte (level-6 class)
-    kScrDynSlots,           // device: per-segment output slots
-    kScrDynSegLen,          // device: u32 per segment
-    kScrDynSegLenHost,      // pinned
-    kScrDynDstOff,          // device: u64 per segment
-    kScrDynDstOffHost,      // pinned
+    kScrDynJobs,            // device: SegJob[] | BlkJob[] of the rows deflate engine (deflate_rows_plan.h sizes all of kScrDyn*)
+    kScrDynJobsHost,        // pinned: the same tables on their way up
+    kScrDynSel,             // device: the matcher's tokens, per segment a bitmap of token starts | a u16 distance per 4 positions
+    kScrDynSlots,           // device: one output slot per block
+    kScrDynSegLen,          // device: u32 length per block | the histogram snapshots of every segment
+    kScrDynSegLenHost,      // pinned: {compressed size, does-not-fit flag} per stream on their way down
+    kScrDynDstOff,          // device: u64 per block, the scan and each block's place in its stream | the sizes per stream
     kScrChunkList,          // device: work list of zng_rocm_chunkmemset_safe_dev (long / memmove-order copies)
     kScrInflate,            // device: tokens | segs | literals | symbols of the one-shot inflate
     kScrInflateHost,        // pinned token staging of the batched inflate

@@ -41,49 +41,14 @@
 
 namespace zr {
 
-struct SegJob {
-    const uint8_t *in;        // stream base (position 0)
-    uint8_t       *out;       // this segment's output slot (4-byte aligned)
-    uint8_t       *dst;       // the stream's output buffer (what K4 packs into)
-    uint64_t       dst_cap;
-    uint64_t       bm_off;    // this segment's token-start bitmap: u64 words from the scratch base
-    uint64_t       d16_off;   // this segment's match distances: u16 entries from the scratch base
-    uint32_t       seg_start, seg_end;
-    uint32_t       out_cap;
-    uint32_t       is_last;     // the block that carries BFINAL
-    uint32_t       first_seg;   // index of the first segment of this segment's stream
-    uint32_t       stream;      // row of the per-stream result table; 0x80000000 set on the stream's last segment
-};
-
-// BlkJob, one BLOCK of the output (K2 .. K4: the tokens of its segment that start in [blo, bhi)): deflate_blocks.h
-
-constexpr uint32_t kSegBytes = 512u << 10;     // plaintext per segment / per dynamic block: the largest, and ...
-constexpr uint32_t kSegBytesMin = 128u << 10;  // ... the smallest.  A segment is one workgroup and one CU holds one
-                                               // workgroup, so a stream is cut into at least ~2 segments per CU when
-                                               // it is long enough (each segment re-inserts the 32 KiB before it:
-                                               // 6 % extra work at 512 KiB, 25 % at 128 KiB)
-static uint32_t segment_bytes(size_t in_len, int cus) {
-    uint32_t seg = kSegBytes;
-    while (seg > kSegBytesMin && in_len / seg < 2u * (size_t)cus) seg >>= 1;
-    return seg;
-}
-constexpr uint32_t kPrime = 32768u;            // dictionary primed from the previous segment
-constexpr int      kHistWords = 320;           // 288 literal/length + 32 distance counts
+// SegJob (one segment: K1), BlkJob (one block: K2 .. K4), the segment and block sizes and the planner that fills both
+// tables: deflate_rows_plan.h
+static_assert(kRowsBatch == (uint32_t)kRowBatch, "deflate_rows_plan.h cuts at the batch of deflate_rows.h");
 static_assert(kDictRowBatch == (uint32_t)kRowBatch && kDictRowsPosBytes == sizeof(RowShared::pos) &&
               kDictRowsTagBytes == sizeof(RowShared::tag) && kDictRowsCntBytes == sizeof(RowShared::cnt) && kDictWindowMax == kPrime,
               "dict_plan.h describes the tables of deflate_rows.h");
-// A segment is written as several BLOCKS, one per kSubBytes of positions (counted from the segment's first batch): zlib's
-// blocks hold about as much (lit_bufsize 16384 symbols), the codes follow the data more closely, a block may be stored
-// (<= 65535 bytes), and -- what it was done for -- every block start is a place where a parallel inflater can cut the
-// stream (inflate_large.hip, inflate_threads.cpp): one block per 512 KiB segment gave a 256 MiB stream 434 parts.
-constexpr uint32_t kSubBatches = 60;
-constexpr uint32_t kSubBytes = kSubBatches * kRowBatch;          // 61440
-constexpr uint32_t kMaxSub = (kSegBytes + kRowBatch + kSubBytes - 1) / kSubBytes + 1;      // histogram snapshots per segment
-
-// scratch a segment of `bytes` plaintext bytes needs: bitmap words / distance entries (its first batch may start up to
-// one batch in front of the segment)
-static inline size_t seg_bm_words(uint32_t bytes) { return ((size_t)bytes + 2u * kRowBatch) / 64 + 2; }
-static inline size_t seg_d16_entries(uint32_t bytes) { return (((size_t)bytes + 2u * kRowBatch) / 4 + 8) & ~(size_t)3; }
+static_assert(kWinBatch == (uint32_t)kRowBatch && kWinPrimeMax == kPrime && kWinMinLookahead == kMinLookahead &&
+              32768u - kWinMinLookahead == kLzMaxDist, "deflate_window_plan.h describes the matcher of deflate_rows.h");
 
 // grid.x = segment.  The plaintext streams through the LDS ring one batch ahead of the parse: 256 lanes fetch the
 // next 1 KiB chunk into a register at the top of a batch and store it into the ring at the top of the next one, so
@@ -756,11 +721,6 @@ void stored_kernel(const uint8_t *__restrict__ in, size_t n, uint8_t *__restrict
     }
 }
 
-static inline size_t seg_slot_bytes(uint32_t n) {
-    // <= 9 bits per literal for an almost flat alphabet, + header (< 400 bytes) + trailer; 4-byte aligned
-    return (((size_t)n * 9 + 7) / 8 + 1024 + 3) & ~(size_t)3;
-}
-
 unsigned long long *g_rows_stamps = nullptr;      // ZR_ROWS_STAMPS builds: device buffer of phase time stamps
 
 // candidates looked at per position, per level: the row form of max_chain_length (deflate.c:142-168: 4, 6, 24, 32, 128
@@ -769,135 +729,62 @@ static const uint32_t kLevelCand[10] = {0, 1, 2, 3, 6, 8, 16, 16, 16, 16};
 
 }  // namespace zr
 
-#include "deflate_rle.h"      // K1 of Z_RLE / Z_HUFFMAN_ONLY: writes the scratch of SegJob / kMaxSub / kHistWords above
+#include "deflate_rle.h"      // K1 of Z_RLE / Z_HUFFMAN_ONLY: writes the scratch of SegJob / kMaxSub / kHistWords (deflate_rows_plan.h)
 
 namespace zr {
 
 // zlib-ng's strategy codes (zlib-ng.h.in); Z_FILTERED (1) runs as the default strategy, as it always has here
 constexpr int kZHuffmanOnly = 2, kZRle = 3, kZFixed = 4;
 
-// The launches of one round: `njobs` streams, all their segments in one job list.  Asynchronous on `st`; *results =
-// pinned host words {compressed size, does-not-fit flag} per stream, valid once the stream has been synchronised.
-// cap_override: out_cap of job 0 when the caller's job struct cannot hold it (a single stream of >= 4 GiB of room).
-// keep: the caller places the blocks itself (deflate_blocks.h) -- K4 and the copy of the results are left out, *keep says where
-// the blocks are, and no job's out / out_cap is looked at.
-// window_bits: the streams' w_bits, 9..15, already checked (deflate_window_plan.h).  Below 15 the matcher is its window form;
-// Z_RLE and Z_HUFFMAN_ONLY write distance 1 or none and need nothing.  The dictionary form knows the 32 KiB window alone.
-static int deflate_rows_enqueue(int level, int strategy, int window_bits, const zng_rocm_stream_job *sjobs, size_t njobs,
-                                const size_t *cap_override, uint32_t seg_bytes, Workspace *ws, hipStream_t st,
-                                unsigned long long **results, unsigned long long *d_results_copy = nullptr,
-                                RowsBlocks *keep = nullptr, const zng_rocm_dict *dobj = nullptr) {
-    static_assert(kWinBatch == (uint32_t)kRowBatch && kWinPrimeMax == kPrime && kWinMinLookahead == kMinLookahead &&
-                  32768u - kWinMinLookahead == kLzMaxDist, "deflate_window_plan.h describes the matcher of deflate_rows.h");
-    if (win_effective(0, window_bits) == 0 || (dobj && win_form(window_bits))) return ZNG_ROCM_EINVAL;
-    size_t nseg = 0;
-    for (size_t s = 0; s < njobs; ++s) nseg += sjobs[s].in_len ? ((size_t)sjobs[s].in_len + seg_bytes - 1) / seg_bytes : 1;
-    const size_t max_blk = nseg * kMaxSub;
-    SegJob *d_jobs = nullptr, *jobs = nullptr;
-    BlkJob *d_blk = nullptr, *blk = nullptr;
-    uint32_t *d_seg_len = nullptr, *d_hist = nullptr;
-    unsigned long long *d_scan = nullptr, *d_bm = nullptr, *d_res = nullptr, *h_res = nullptr;
-    uint16_t *d_d16 = nullptr;
-    uint8_t *d_slots = nullptr;
+static_assert(kRowsStrategyMax == kZFixed, "deflate_rows_plan.h checks the strategies this file launches");
+
+// The launches of one round (deflate_blocks.h): plan, count, reserve, fill, upload, K1 .. K4 by the request's output mode.
+// The dictionary form knows the 32 KiB window alone; Z_RLE and Z_HUFFMAN_ONLY write distance 1 or none and need no window form.
+int deflate_rows_enqueue(const RowsRequest &rq, Workspace *ws, hipStream_t st, RowsDone *done) {
+    if (win_effective(0, rq.window_bits) == 0 || (rq.dict && win_form(rq.window_bits))) return ZNG_ROCM_EINVAL;
+    const bool keep = rq.out == kRowsOutKeep;
+    const RowsPlan plan = {rq.jobs, rq.njobs, rq.seg_bytes, rq.dict ? rq.dict->window : 0u,
+                           keep ? kRowsCapKeep : (rq.one_cap ? kRowsCapOne : kRowsCapJob), rq.one_cap ? *rq.one_cap : 0ull};
+    const RowsCounts c = rows_plan_count(plan);
+    uint8_t *h_tab = nullptr, *d_tab = nullptr, *d_slots = nullptr;
+    uint32_t *d_seg_len = nullptr;
+    unsigned long long *d_scan = nullptr, *d_bm = nullptr, *h_res = nullptr;
     if (int rc = host_tables_acquire(ws)) return rc;
-    // pinned: SegJob[nseg] | BlkJob[max_blk]
-    const size_t seg_tab = (nseg * sizeof(SegJob) + 255) & ~(size_t)255;
-    if (int rc = scratch_reserve(ws, kScrDynJobsHost, seg_tab + max_blk * sizeof(BlkJob), true, (void **)&jobs)) return rc;
-    blk = reinterpret_cast<BlkJob *>(reinterpret_cast<uint8_t *>(jobs) + seg_tab);
-    if (int rc = scratch_reserve(ws, kScrDynSegLenHost, njobs * 2 * sizeof(unsigned long long), true, (void **)&h_res)) return rc;
-    if (int rc = scratch_reserve(ws, kScrDynJobs, seg_tab + max_blk * sizeof(BlkJob), false, (void **)&d_jobs)) return rc;
-    d_blk = reinterpret_cast<BlkJob *>(reinterpret_cast<uint8_t *>(d_jobs) + seg_tab);
-    if (int rc = scratch_reserve(ws, kScrDynSegLen, max_blk * sizeof(uint32_t) + 64 + nseg * (size_t)kMaxSub * kHistWords * sizeof(uint32_t), false, (void **)&d_seg_len))
-        return rc;
-    d_hist = d_seg_len + ((max_blk + 3) & ~(size_t)3);
-    if (int rc = scratch_reserve(ws, kScrDynDstOff, (2 * max_blk + 2 + 2 * njobs) * sizeof(unsigned long long), false, (void **)&d_scan))
-        return rc;
-    size_t slot_total = 0, bm_total = 0, d16_total = 0, k = 0, nb = 0;
-    for (size_t s = 0; s < njobs; ++s) {
-        const zng_rocm_stream_job &j = sjobs[s];
-        const uint32_t dict = dobj ? dobj->window : j.dict_len;      // (the shared window: no job has a dict_len of its own)
-        const bool final_block = (j.flags & ZNG_ROCM_BLOCK_NOT_FINAL) == 0;
-        const size_t n = j.in_len ? ((size_t)j.in_len + seg_bytes - 1) / seg_bytes : 1;
-        const size_t b0 = nb;
-        for (size_t i = 0; i < n; ++i, ++k) {
-            // positions count from the first dictionary byte: the segments' own 32 KiB priming reaches into it
-            const uint32_t a = dict + (uint32_t)(i * seg_bytes);
-            const uint32_t b = dict + (uint32_t)((i + 1) * (size_t)seg_bytes < j.in_len ? (i + 1) * (size_t)seg_bytes : j.in_len);
-            jobs[k].in = (const uint8_t *)((uintptr_t)j.in - dict);   // behind a shared window: never read below in + dict
-            jobs[k].out = nullptr;
-            jobs[k].dst = (uint8_t *)j.out;
-            jobs[k].dst_cap = 0;
-            jobs[k].seg_start = a;
-            jobs[k].seg_end = b;
-            jobs[k].out_cap = 0;
-            jobs[k].is_last = 0;
-            jobs[k].first_seg = 0;
-            jobs[k].stream = (uint32_t)s;
-            jobs[k].bm_off = bm_total;
-            jobs[k].d16_off = d16_total;
-            // the segment's blocks: one per kSubBytes of positions counted from its first batch (the matcher snapshots
-            // its histogram at the same places); a block without positions of its own is left out
-            const uint32_t first = a - a % kRowBatch;
-            const uint32_t nsub = b > first ? (b - first + kSubBytes - 1) / kSubBytes : 1u;
-            bool prev_written = false;
-            for (uint32_t sub = 0; sub < nsub; ++sub) {
-                const uint32_t p0 = first + sub * kSubBytes, p1 = p0 + kSubBytes;
-                const uint32_t blo = p0 > a ? p0 : a, bhi = p1 < b ? p1 : b;
-                if (blo >= bhi && !(b == a && sub + 1 == nsub)) {          // (an empty segment still gets its one block)
-                    prev_written = true;                                  // its snapshot exists all the same
-                    continue;
-                }
-                BlkJob &q = blk[nb++];
-                q.in = jobs[k].in;
-                q.dst = (uint8_t *)j.out;
-                q.dst_cap = keep ? ~0ull : (cap_override && s == 0 ? *cap_override : j.out_cap);
-                q.bm_off = bm_total;
-                q.d16_off = d16_total;
-                q.seg_start = a;
-                q.seg_end = b;
-                q.blo = blo;
-                q.bhi = bhi;
-                q.hist_idx = (uint32_t)(k * kMaxSub + sub);
-                q.hist_prev = sub > 0 && prev_written ? 1u : 0u;
-                q.out_cap = (uint32_t)seg_slot_bytes(bhi - blo + 258u);
-                q.is_last = 0;
-                q.first_seg = (uint32_t)b0;
-                q.stream = (uint32_t)s;
-                q.out = (uint8_t *)slot_total;            // offset for now
-                slot_total += q.out_cap;
-                prev_written = true;
-            }
-            bm_total += seg_bm_words(b - a);
-            d16_total += seg_d16_entries(b - a);
-        }
-        blk[nb - 1].stream |= 0x80000000u;               // the stream's last block ...
-        blk[nb - 1].is_last = final_block ? 1u : 0u;      // ... carries BFINAL
-    }
-    unsigned long long *d_excl = d_scan, *d_dst_off = d_scan + nb + 1;
-    d_res = d_dst_off + nb + 1;
-    if (int rc = scratch_reserve(ws, kScrDynSlots, slot_total, false, (void **)&d_slots)) return rc;
+    if (int rc = scratch_reserve(ws, kScrDynJobsHost, c.table_bytes, true, (void **)&h_tab)) return rc;
+    if (int rc = scratch_reserve(ws, kScrDynSegLenHost, c.sizes_bytes, true, (void **)&h_res)) return rc;
+    if (int rc = scratch_reserve(ws, kScrDynJobs, c.table_bytes, false, (void **)&d_tab)) return rc;
+    if (int rc = scratch_reserve(ws, kScrDynSegLen, c.len_hist_bytes, false, (void **)&d_seg_len)) return rc;
+    if (int rc = scratch_reserve(ws, kScrDynDstOff, c.scan_bytes, false, (void **)&d_scan)) return rc;
+    BlkJob *blk = reinterpret_cast<BlkJob *>(h_tab + c.seg_tab);
+    const RowsTotals t = rows_plan_fill(plan, reinterpret_cast<SegJob *>(h_tab), blk);
+    const size_t nseg = c.nseg, nb = t.nb;
+    if (int rc = scratch_reserve(ws, kScrDynSlots, t.slot_total, false, (void **)&d_slots)) return rc;
     // token scratch of the matcher: 1 bit + half a u16 per position (K1 -> K2)
-    if (int rc = scratch_reserve(ws, kScrDynSel, bm_total * sizeof(unsigned long long) + d16_total * sizeof(uint16_t), false, (void **)&d_bm))
+    if (int rc = scratch_reserve(ws, kScrDynSel, t.bm_total * sizeof(unsigned long long) + t.d16_total * sizeof(uint16_t), false, (void **)&d_bm))
         return rc;
-    d_d16 = reinterpret_cast<uint16_t *>(d_bm + bm_total);
     for (size_t i = 0; i < nb; ++i) blk[i].out = d_slots + (size_t)blk[i].out;
-    ZR_HIP(hipMemcpyAsync(d_jobs, jobs, seg_tab + nb * sizeof(BlkJob), hipMemcpyHostToDevice, st));
+    ZR_HIP(hipMemcpyAsync(d_tab, h_tab, c.seg_tab + nb * sizeof(BlkJob), hipMemcpyHostToDevice, st));
+    const SegJob *d_jobs = reinterpret_cast<const SegJob *>(d_tab);
+    const BlkJob *d_blk = reinterpret_cast<const BlkJob *>(d_tab + c.seg_tab);
+    uint32_t *d_hist = d_seg_len + c.hist_word;
+    uint16_t *d_d16 = reinterpret_cast<uint16_t *>(d_bm + t.bm_total);
+    unsigned long long *d_excl = d_scan, *d_dst_off = d_scan + nb + 1, *d_res = d_dst_off + nb + 1;
 
     // K1: the level's matcher, or the strategy's own front end (the same scratch either way)
-    if (strategy == kZHuffmanOnly)
+    if (rq.strategy == kZHuffmanOnly)
         ZR_LAUNCH_TRACED(rle_rows_kernel<true>, dim3((unsigned)nseg), dim3(kRleThreads), st, d_jobs, d_bm, d_d16, d_hist);
-    else if (strategy == kZRle)
+    else if (rq.strategy == kZRle)
         ZR_LAUNCH_TRACED(rle_rows_kernel<false>, dim3((unsigned)nseg), dim3(kRleThreads), st, d_jobs, d_bm, d_d16, d_hist);
-    else if (win_form(window_bits))
-        ZR_LAUNCH_TRACED(lz_rows_win_kernel, dim3((unsigned)nseg), dim3(kRowBatch), st, d_jobs, d_bm, d_d16, d_hist, kLevelCand[level],
-                         g_rows_stamps, win_dist(window_bits), win_prime(window_bits));
-    else if (dobj)
-        ZR_LAUNCH_TRACED(lz_rows_dict_kernel, dim3((unsigned)nseg), dim3(kRowBatch), st, d_jobs, d_bm, d_d16, d_hist, kLevelCand[level],
-                         g_rows_stamps, (const uint8_t *)dobj->d_window, (const uint4 *)dobj->d_rows, dobj->window);
+    else if (win_form(rq.window_bits))
+        ZR_LAUNCH_TRACED(lz_rows_win_kernel, dim3((unsigned)nseg), dim3(kRowBatch), st, d_jobs, d_bm, d_d16, d_hist, kLevelCand[rq.level],
+                         g_rows_stamps, win_dist(rq.window_bits), win_prime(rq.window_bits));
+    else if (rq.dict)
+        ZR_LAUNCH_TRACED(lz_rows_dict_kernel, dim3((unsigned)nseg), dim3(kRowBatch), st, d_jobs, d_bm, d_d16, d_hist, kLevelCand[rq.level],
+                         g_rows_stamps, (const uint8_t *)rq.dict->d_window, (const uint4 *)rq.dict->d_rows, rq.dict->window);
     else
-        ZR_LAUNCH_TRACED(lz_rows_kernel, dim3((unsigned)nseg), dim3(kRowBatch), st, d_jobs, d_bm, d_d16, d_hist, kLevelCand[level], g_rows_stamps);
+        ZR_LAUNCH_TRACED(lz_rows_kernel, dim3((unsigned)nseg), dim3(kRowBatch), st, d_jobs, d_bm, d_d16, d_hist, kLevelCand[rq.level], g_rows_stamps);
     ZR_HIP(hipGetLastError());
-    if (strategy == kZFixed)
+    if (rq.strategy == kZFixed)
         hipLaunchKernelGGL(emit_dynamic_kernel<true>, dim3((unsigned)nb), dim3(256), 0, st, d_blk, d_bm, d_d16, d_hist, d_seg_len);
     else
         hipLaunchKernelGGL(emit_dynamic_kernel<false>, dim3((unsigned)nb), dim3(256), 0, st, d_blk, d_bm, d_d16, d_hist, d_seg_len);
@@ -905,45 +792,82 @@ static int deflate_rows_enqueue(int level, int strategy, int window_bits, const 
     hipLaunchKernelGGL(segments_scan_kernel, dim3(1), dim3(1024), 0, st, d_blk, d_seg_len, (uint32_t)nb, d_excl, d_dst_off, d_res);
     ZR_HIP(hipGetLastError());
     if (keep) {
-        *keep = RowsBlocks{d_blk, d_seg_len, d_dst_off, d_res, nb};
+        done->blocks = RowsBlocks{d_blk, d_seg_len, d_dst_off, d_res, nb};
         return host_tables_release(ws, st);
     }
-    hipLaunchKernelGGL(gather_segments_kernel, dim3(njobs > 64 ? 2 : 4, (unsigned)nb), dim3(256), 0, st, d_blk, d_seg_len, d_dst_off);
+    hipLaunchKernelGGL(gather_segments_kernel, dim3(rq.njobs > 64 ? 2 : 4, (unsigned)nb), dim3(256), 0, st, d_blk, d_seg_len, d_dst_off);
     ZR_HIP(hipGetLastError());
-    if (d_results_copy)
-        ZR_HIP(hipMemcpyAsync(d_results_copy, d_res, njobs * 2 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
+    if (rq.out == kRowsOutDevice)
+        ZR_HIP(hipMemcpyAsync(rq.d_sizes, d_res, c.sizes_bytes, hipMemcpyDeviceToDevice, st));
     else
-        ZR_HIP(hipMemcpyAsync(h_res, d_res, njobs * 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        ZR_HIP(hipMemcpyAsync(h_res, d_res, c.sizes_bytes, hipMemcpyDeviceToHost, st));
     if (int rc = host_tables_release(ws, st)) return rc;
-    *results = h_res;
+    done->h_sizes = h_res;
     return ZNG_ROCM_OK;
-}
-
-int deflate_rows_enqueue_blocks(int level, const zng_rocm_stream_job *sjobs, size_t njobs, Workspace *ws, hipStream_t st,
-                                RowsBlocks *blocks) {
-    unsigned long long *unused = nullptr;
-    return deflate_rows_enqueue(level, 0, kWinBitsMax, sjobs, njobs, nullptr, kSegBytesMin, ws, st, &unused, nullptr, blocks);
 }
 
 uint32_t deflate_rows_segment_bytes(size_t total_in) { return segment_bytes(total_in, ctx()->cus); }
 
-int deflate_rows_enqueue_streams(int level, int strategy, const zng_rocm_stream_job *sjobs, size_t njobs, uint32_t seg_bytes,
-                                 Workspace *ws, hipStream_t st, RowsBlocks *blocks, int window_bits) {
-    unsigned long long *unused = nullptr;
-    return deflate_rows_enqueue(level, strategy, window_bits, sjobs, njobs, nullptr, seg_bytes, ws, st, &unused, nullptr, blocks);
-}
-
-// the shared window of `dict` is every stream's history (strategies 0, 1 and 4: the matcher's dictionary form); a job's own
-// dict_len is 0
-int deflate_rows_enqueue_streams_dict(int level, int strategy, const zng_rocm_dict *dict, const zng_rocm_stream_job *sjobs,
-                                      size_t njobs, uint32_t seg_bytes, Workspace *ws, hipStream_t st, RowsBlocks *blocks) {
-    unsigned long long *unused = nullptr;
-    return deflate_rows_enqueue(level, strategy, kWinBitsMax, sjobs, njobs, nullptr, seg_bytes, ws, st, &unused, nullptr, blocks, dict);
-}
-
 int launch_rows_dict_table(const uint8_t *d_window, uint32_t W, void *d_tab, hipStream_t st) {
     hipLaunchKernelGGL(rows_dict_table_kernel, dim3(1), dim3(kRowBatch), 0, st, d_window, W, (uint4 *)d_tab);
     ZR_HIP(hipGetLastError());
+    return ZNG_ROCM_OK;
+}
+
+// a refusal of the checks of deflate_rows_plan.h: its text, its status
+static int rows_refused(RowsEntry entry, RowsRefusal why, const uint64_t *job) {
+    if (job) set_error("job %llu: %s", (unsigned long long)*job, rows_refusal_text(entry, why));
+    else set_error("%s", rows_refusal_text(entry, why));
+    return rows_status(why);
+}
+
+// Level 0: stored blocks, no scratch, no host round trip
+static int stored_one_stream(const uint8_t *d_in, size_t in_len, uint32_t flags, uint8_t *d_out, size_t out_cap, size_t *out_len, hipStream_t st) {
+    const bool final_block = (flags & ZNG_ROCM_BLOCK_NOT_FINAL) == 0;
+    const size_t nblk = in_len ? (in_len + kMaxStored - 1) / kMaxStored : 1;
+    const bool marker = !final_block && (flags & ZNG_ROCM_BLOCK_SYNC_FLUSH);   // deflate.c:1064-1076
+    const size_t total0 = in_len + 5 * nblk + (marker ? 5 : 0);
+    if (total0 > out_cap) {
+        set_error("stored size %llu exceeds out_cap", (unsigned long long)total0);
+        return kRowsBufError;
+    }
+    const size_t pieces = (in_len + 15) / 16 + nblk;
+    unsigned grid = (unsigned)((pieces + 255) / 256);
+    if (grid > 65536u) grid = 65536u;
+    if (grid == 0) grid = 1;
+    ZR_LAUNCH_TRACED(stored_kernel, dim3(grid), dim3(256), st, d_in, in_len, d_out, final_block ? 1 : 0);
+    ZR_HIP(hipGetLastError());
+    if (marker) {
+        static const uint8_t empty_stored[5] = {0x00, 0x00, 0x00, 0xff, 0xff};
+        ZR_HIP(hipMemcpyAsync(d_out + in_len + 5 * nblk, empty_stored, 5, hipMemcpyHostToDevice, st));
+    }
+    ZR_HIP(hipStreamSynchronize(st));
+    *out_len = total0;
+    return ZNG_ROCM_OK;
+}
+
+// The one-stream calls behind their checks: level 0 as above, levels 1..9 as one request on the caller's stream.  Scratch is
+// keyed by that stream (context.h): concurrent callers on different streams share nothing.  d_result: where the sizes go on the
+// device (async), or null: the call waits for them and writes *out_len.
+static int rows_one_stream(int level, int strategy, int window_bits, const uint8_t *d_in, size_t in_len, uint32_t dict_len, uint32_t flags,
+                           uint8_t *d_out, size_t out_cap, size_t *out_len, uint64_t *d_result, hipStream_t st) {
+    DeviceGuard dev;
+    Workspace *ws = workspace_for(st);
+    if (!ws) return ZNG_ROCM_ENOMEM;
+    std::lock_guard<std::mutex> use(ws->mu);
+    if (level == 0) return stored_one_stream(d_in, in_len, flags, d_out, out_cap, out_len, st);
+    const zng_rocm_stream_job one = rows_one_job(d_in, d_out, in_len, dict_len, flags);
+    const RowsRequest rq = {level, strategy, window_bits, &one, 1, segment_bytes(in_len, ctx()->cus), &out_cap, nullptr,
+                            d_result ? kRowsOutDevice : kRowsOutHost, (unsigned long long *)d_result};
+    RowsDone done;
+    if (int rc = deflate_rows_enqueue(rq, ws, st, &done)) return rc;
+    if (d_result) return ZNG_ROCM_OK;
+    ZR_HIP(hipStreamSynchronize(st));
+    if (done.h_sizes[1]) {
+        set_error("compressed size %llu exceeds out_cap", done.h_sizes[0]);
+        return kRowsBufError;
+    }
+    *out_len = (size_t)done.h_sizes[0];
     return ZNG_ROCM_OK;
 }
 
@@ -959,11 +883,7 @@ extern "C" {
 void zng_rocm_debug_rows_stamps(void *d_buf) { g_rows_stamps = (unsigned long long *)d_buf; }
 #endif
 
-size_t zng_rocm_deflate_bound(size_t source_len) {
-    const size_t nseg = source_len ? (source_len + kSegBytesMin - 1) / kSegBytesMin : 1;     // the most there can be
-    // covers level 0 too: 5 bytes per 65535 (deflate_stored) is far below the n/8 term
-    return source_len + source_len / 8 + nseg * 1032 + 16;
-}
+size_t zng_rocm_deflate_bound(size_t source_len) { return (size_t)rows_deflate_bound(source_len); }
 
 int zng_rocm_deflate_dev(int level, const uint8_t *d_in, size_t in_len, uint8_t *d_out, size_t out_cap,
                          size_t *out_len, void *stream) {
@@ -990,78 +910,9 @@ int zng_rocm_deflate_window_block_dev(int level, int strategy, int window_bits, 
         set_error("zng_rocm_init() has not succeeded");
         return ZNG_ROCM_ENODEV;
     }
-    if (!out_len || !d_out || (!d_in && in_len)) return ZNG_ROCM_EINVAL;
-    if (level < 0 || level > 9) {
-        set_error("level %d is outside 0..9", level);
-        return ZNG_ROCM_EINVAL;
-    }
-    if (strategy < 0 || strategy > kZFixed) {
-        set_error("strategy %d is outside 0..4", strategy);
-        return ZNG_ROCM_EINVAL;
-    }
-    if (win_check(0, window_bits)) {
-        set_error("window_bits %d is outside 9..15", window_bits);
-        return ZNG_ROCM_EINVAL;
-    }
-    if (dict_len > kPrime || (flags & ~(uint32_t)(ZNG_ROCM_BLOCK_NOT_FINAL | ZNG_ROCM_BLOCK_SYNC_FLUSH))) {
-        set_error("dict_len above 32768 or unknown flags");
-        return ZNG_ROCM_EINVAL;
-    }
-    const bool final_block = (flags & ZNG_ROCM_BLOCK_NOT_FINAL) == 0;
-    if (in_len + dict_len >= (1ull << 32) - kSegBytes) {
-        set_error("streams of 4 GiB and more are not supported by the 32-bit position format");
-        return ZNG_ROCM_EINVAL;
-    }
-    if (out_cap < zng_rocm_deflate_bound(in_len)) {
-        set_error("out_cap below zng_rocm_deflate_bound()");
-        return -5;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    DeviceGuard dev;
-    // scratch is keyed by the caller's HIP stream (context.h): concurrent callers on different streams share nothing
-    Workspace *ws = workspace_for(st);
-    if (!ws) return ZNG_ROCM_ENOMEM;
-    std::lock_guard<std::mutex> use(ws->mu);
-    // max_chain_length per level, deflate.c:142-168
-    if (level == 0) {                                               // deflate_stored: no scratch, no host round trip
-        const size_t nblk = in_len ? (in_len + kMaxStored - 1) / kMaxStored : 1;
-        const bool marker = !final_block && (flags & ZNG_ROCM_BLOCK_SYNC_FLUSH);   // deflate.c:1064-1076
-        const size_t total0 = in_len + 5 * nblk + (marker ? 5 : 0);
-        if (total0 > out_cap) {
-            set_error("stored size %llu exceeds out_cap", (unsigned long long)total0);
-            return -5;
-        }
-        const size_t pieces = (in_len + 15) / 16 + nblk;
-        unsigned grid = (unsigned)((pieces + 255) / 256);
-        if (grid > 65536u) grid = 65536u;
-        if (grid == 0) grid = 1;
-        ZR_LAUNCH_TRACED(stored_kernel, dim3(grid), dim3(256), st, d_in, in_len, d_out, final_block ? 1 : 0);
-        ZR_HIP(hipGetLastError());
-        if (marker) {
-            static const uint8_t empty_stored[5] = {0x00, 0x00, 0x00, 0xff, 0xff};
-            ZR_HIP(hipMemcpyAsync(d_out + in_len + 5 * nblk, empty_stored, 5, hipMemcpyHostToDevice, st));
-        }
-        ZR_HIP(hipStreamSynchronize(st));
-        *out_len = total0;
-        return ZNG_ROCM_OK;
-    }
-    const size_t seg_bytes = segment_bytes(in_len, ctx()->cus);
-    zng_rocm_stream_job one;
-    one.in = d_in;
-    one.out = d_out;
-    one.in_len = (uint32_t)in_len;
-    one.out_cap = 0;
-    one.dict_len = dict_len;
-    one.flags = flags;
-    unsigned long long *res = nullptr;
-    if (int rc = deflate_rows_enqueue(level, strategy, window_bits, &one, 1, &out_cap, (uint32_t)seg_bytes, ws, st, &res)) return rc;
-    ZR_HIP(hipStreamSynchronize(st));
-    if (res[1]) {
-        set_error("compressed size %llu exceeds out_cap", res[0]);
-        return -5;
-    }
-    *out_len = (size_t)res[0];
-    return ZNG_ROCM_OK;
+    if (RowsRefusal why = rows_one_check(kRowsEntryBlock, level, strategy, window_bits, !out_len, d_in, d_out, in_len, dict_len, flags, out_cap))
+        return rows_refused(kRowsEntryBlock, why, nullptr);
+    return rows_one_stream(level, strategy, window_bits, d_in, in_len, dict_len, flags, d_out, out_cap, out_len, nullptr, (hipStream_t)stream);
 }
 
 // The same with NO synchronisation: everything -- matcher, block emitter, the scan that places the segments, the packing --
@@ -1073,33 +924,14 @@ int zng_rocm_deflate_async_dev(int level, const uint8_t *d_in, size_t in_len, ui
         set_error("zng_rocm_init() has not succeeded");
         return ZNG_ROCM_ENODEV;
     }
-    if (!d_result || !d_out || (!d_in && in_len) || level < 1 || level > 9 || dict_len > kPrime ||
-        (flags & ~(uint32_t)(ZNG_ROCM_BLOCK_NOT_FINAL | ZNG_ROCM_BLOCK_SYNC_FLUSH)) || in_len + dict_len >= (1ull << 32) - kSegBytes)
-        return ZNG_ROCM_EINVAL;
-    if (out_cap < zng_rocm_deflate_bound(in_len)) {
-        set_error("out_cap below zng_rocm_deflate_bound()");
-        return -5;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    DeviceGuard dev;
-    Workspace *ws = workspace_for(st);
-    if (!ws) return ZNG_ROCM_ENOMEM;
-    std::lock_guard<std::mutex> use(ws->mu);
-    zng_rocm_stream_job one;
-    one.in = d_in;
-    one.out = d_out;
-    one.in_len = (uint32_t)in_len;
-    one.out_cap = 0;
-    one.dict_len = dict_len;
-    one.flags = flags;
-    unsigned long long *res = nullptr;
-    return deflate_rows_enqueue(level, 0, kWinBitsMax, &one, 1, &out_cap, segment_bytes(in_len, ctx()->cus), ws, st, &res,
-                                (unsigned long long *)d_result);
+    if (RowsRefusal why = rows_one_check(kRowsEntryAsync, level, 0, kWinBitsMax, !d_result, d_in, d_out, in_len, dict_len, flags, out_cap))
+        return rows_refused(kRowsEntryAsync, why, nullptr);
+    return rows_one_stream(level, 0, kWinBitsMax, d_in, in_len, dict_len, flags, d_out, out_cap, nullptr, d_result, (hipStream_t)stream);
 }
 
 // Many independent streams at one of the chain levels (the reference's many-stream model, test/pigz/CMakeLists.txt:123-200,
 // at pigz's default level): every stream is cut into segments as in zng_rocm_deflate_block_dev and the segments of ALL
-// streams go through ONE set of launches per round (a round holds up to ~4 GiB of plaintext).  Synchronous, like
+// streams go through ONE set of launches per round (a round holds up to ~4 GiB of plaintext and history).  Synchronous, like
 // zng_rocm_deflate_block_dev; out_lens is a host array.
 int zng_rocm_deflate_streams_dev(int level, const zng_rocm_stream_job *sjobs, size_t njobs, size_t *out_lens, void *stream) {
     return zng_rocm_deflate_strategy_streams_dev(level, 0, sjobs, njobs, out_lens, stream);
@@ -1117,59 +949,30 @@ int zng_rocm_deflate_window_streams_dev(int level, int strategy, int window_bits
         set_error("zng_rocm_init() has not succeeded");
         return ZNG_ROCM_ENODEV;
     }
-    if (strategy < 0 || strategy > kZFixed) {
-        set_error("strategy %d is outside 0..4", strategy);
-        return ZNG_ROCM_EINVAL;
-    }
-    if (win_check(0, window_bits)) {
-        set_error("window_bits %d is outside 9..15", window_bits);
-        return ZNG_ROCM_EINVAL;
-    }
+    uint64_t bad = njobs;
+    if (RowsRefusal why = rows_streams_check(level, strategy, window_bits, sjobs, njobs, !out_lens, &bad))
+        return rows_refused(kRowsEntryStreams, why, bad < njobs ? &bad : nullptr);
     if (!njobs) return ZNG_ROCM_OK;
-    if (!sjobs || !out_lens) return ZNG_ROCM_EINVAL;
-    if (level < 1 || level > 9) {
-        set_error("level %d is outside 1..9 (level 0: zng_rocm_deflate_block_dev per stream)", level);
-        return ZNG_ROCM_EINVAL;
-    }
     size_t total_in = 0;
-    for (size_t i = 0; i < njobs; ++i) {
-        const zng_rocm_stream_job &j = sjobs[i];
-        if (!j.out || (j.in_len && !j.in) || (j.dict_len && !j.in) || j.dict_len > kPrime ||
-            (j.flags & ~(uint32_t)(ZNG_ROCM_BLOCK_NOT_FINAL | ZNG_ROCM_BLOCK_SYNC_FLUSH)) ||
-            (uint64_t)j.in_len + j.dict_len >= (1ull << 32) - kSegBytes) {
-            set_error("job %zu: null buffer, dict_len above 32768, unknown flags, or a stream of 4 GiB and more", i);
-            return ZNG_ROCM_EINVAL;
-        }
-        if (j.out_cap < zng_rocm_deflate_bound(j.in_len)) {
-            set_error("job %zu: out_cap below zng_rocm_deflate_bound()", i);
-            return -5;
-        }
-        total_in += j.in_len;
-    }
+    for (size_t i = 0; i < njobs; ++i) total_in += sjobs[i].in_len;
     hipStream_t st = (hipStream_t)stream;
     DeviceGuard dev;
     Workspace *ws = workspace_for(st);
     if (!ws) return ZNG_ROCM_ENOMEM;
     std::lock_guard<std::mutex> use(ws->mu);
     const uint32_t seg_bytes = segment_bytes(total_in, ctx()->cus);
-    constexpr size_t kRoundBytes = 4ull << 30;
-
-    size_t first = 0;
-    while (first < njobs) {
-        size_t last = first, bytes = 0;
-        while (last < njobs && (last == first || bytes + sjobs[last].in_len + sjobs[last].dict_len <= kRoundBytes)) {
-            bytes += sjobs[last].in_len + sjobs[last].dict_len;
-            ++last;
-        }
-        unsigned long long *res = nullptr;
-        if (int rc = deflate_rows_enqueue(level, strategy, window_bits, sjobs + first, last - first, nullptr, seg_bytes, ws, st, &res)) return rc;
+    for (size_t first = 0; first < njobs;) {
+        const size_t last = (size_t)rows_round_end(sjobs, njobs, first, kRowsRoundBytes, true);
+        const RowsRequest rq = {level, strategy, window_bits, sjobs + first, last - first, seg_bytes, nullptr, nullptr, kRowsOutHost, nullptr};
+        RowsDone done;
+        if (int rc = deflate_rows_enqueue(rq, ws, st, &done)) return rc;
         ZR_HIP(hipStreamSynchronize(st));
         for (size_t s = first; s < last; ++s) {
-            if (res[2 * (s - first) + 1]) {
-                set_error("job %zu: compressed size %llu exceeds out_cap", s, res[2 * (s - first)]);
-                return -5;
+            if (done.h_sizes[2 * (s - first) + 1]) {
+                set_error("job %zu: compressed size %llu exceeds out_cap", s, done.h_sizes[2 * (s - first)]);
+                return kRowsBufError;
             }
-            out_lens[s] = (size_t)res[2 * (s - first)];
+            out_lens[s] = (size_t)done.h_sizes[2 * (s - first)];
         }
         first = last;
     }
