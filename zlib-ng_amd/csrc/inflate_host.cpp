@@ -499,6 +499,10 @@ int decode_stream(const uint8_t *src, size_t src_len, uint64_t window_len, zng_r
             maybe_new_segment(o);
             push_token(o, 0x80000000u | ((len - 3) << 16) | (dist - 1));
             o.out_pos += len;
+            // a match that carried the segment past 32 KiB ends it: < 32 KiB + 258, as zng_rocm.h promises.  (Left open,
+            // the segment took the literal behind the match as well -- 32 KiB + 258 -- or, with a stored block behind
+            // it, the whole block: `room` there is unsigned.)
+            maybe_new_segment(o);
         }
     }
     t->status = Z_STREAM_END_;

@@ -118,6 +118,39 @@ def resolve_dev(dec, stream=None):
     return out[:n]
 
 
+def resolve_arrays_dev(tokens, literals, segs, out_len, window=None, sym_shift=0, out_shift=0, guard=64, stream=None):
+    """the device stage on raw arrays (numpy): tokens uint32, literals uint8, segs uint64 of (nsegs + 1) triples, as
+    include/zng_rocm.h defines them.  window=None: zng_rocm_inflate_resolve_dev; a bytes-like window (it may be empty):
+    zng_rocm_inflate_resolve_window_dev.  d_symbols starts `sym_shift` elements and d_out `out_shift` bytes into larger
+    tensors.  Returns the whole destination tensor: out_shift + out_len + guard bytes that were filled with 0xA5 before the
+    call, the plaintext at [out_shift, out_shift + out_len).  The arrays must be valid: this stage has no error channel."""
+    import numpy as np
+    import torch
+    rocm._need_init()
+    tokens = np.array(tokens, dtype=np.uint32)                      # copies: the caller's arrays may be read-only
+    literals = np.array(literals, dtype=np.uint8)
+    segs = np.array(segs, dtype=np.uint64).reshape(-1)
+    n, nsegs = int(out_len), segs.size // 3 - 1
+    dst = torch.full((int(out_shift) + n + int(guard),), 0xA5, dtype=torch.uint8, device="cuda")
+    d_tok = torch.from_numpy(tokens.view(np.int32)).cuda() if tokens.size else torch.zeros(1, dtype=torch.int32, device="cuda")
+    d_lit = torch.from_numpy(literals).cuda() if literals.size else torch.zeros(1, dtype=torch.uint8, device="cuda")
+    d_seg = torch.from_numpy(segs.view(np.int64)).cuda()
+    front = 0 if window is None else 32768
+    d_sym = torch.empty(int(sym_shift) + front + n + 8, dtype=torch.int16, device="cuda")
+    args = (rocm._dev_ptr(d_tok), tokens.size, rocm._dev_ptr(d_lit), literals.size, rocm._dev_ptr(d_seg), nsegs,
+            rocm._dev_ptr(d_sym, 2 * int(sym_shift)), rocm._dev_ptr(dst, int(out_shift)), n)
+    if window is None:
+        rocm._check(rocm.lib().zng_rocm_inflate_resolve_dev(*args, rocm._stream_ptr(stream)), "zng_rocm_inflate_resolve_dev")
+    else:
+        w = np.frombuffer(bytes(window), dtype=np.uint8)
+        d_win = torch.from_numpy(w.copy()).cuda() if w.size else None
+        rocm._check(rocm.lib().zng_rocm_inflate_resolve_window_dev(*args, rocm._dev_ptr(d_win) if w.size else None, w.size,
+                                                                   rocm._stream_ptr(stream)),
+                    "zng_rocm_inflate_resolve_window_dev")
+    torch.cuda.current_stream().synchronize()
+    return dst
+
+
 def inflate_raw(src, dst, stream=None):
     """one-shot: host bytes (or a HostStream, which saves the Python copy) in, plaintext into the CUDA tensor `dst`;
     returns (zlib status, bytes produced)"""
