@@ -1134,10 +1134,38 @@ int  zng_rocm_inflate_raw_threads(const uint8_t *src, size_t src_len, const uint
  *                  = plaintext bytes, *src_len = input bytes consumed.  Z_OK, Z_BUF_ERROR (destination too small),
  *                  Z_DATA_ERROR with the reference's message text in zng_rocm_last_error() ("incorrect header
  *                  check", "header crc mismatch" (gzip FHCRC, inflate.c:686-692), "incorrect data check",
- *                  "incorrect length check", decoder messages, incomplete stream). */
+ *                  "incorrect length check", decoder messages, incomplete stream).
+ * compress2_index_dev: compress2_dev that also hands back a zng_rocm_inflate_index (above) of the stream it writes -- taken from
+ *                  what the compressor knows, with no byte of the stream decoded and no plaintext-sized scratch.  The bytes at
+ *                  d_dst, *dst_len and the return value are compress2_dev's for the same d_src, src_len, level, format (level
+ *                  -1 and 0..9, formats 0/1/2), and so are the does-not-fit (-5), bad-level (-2) and ZNG_ROCM_ENODEV answers
+ *                  with their zng_rocm_last_error() texts.  span_bytes as zng_rocm_inflate_index_build_dev: 0 (= 1 MiB) or
+ *                  64 KiB .. 1 GiB; anything else, or out == NULL, is ZNG_ROCM_EINVAL before any other check, with nothing
+ *                  launched, no device byte written, *dst_len untouched and *out = NULL (when out is given); after that the
+ *                  checks run in compress2_dev's order.  An index exists only on return 0; on every other return *out = NULL
+ *                  and *dst_len is untouched.  Its head is {format, header_len = 0 / 2 / 10, src_end = *dst_len, plain_len =
+ *                  src_len, span_bytes}; it is an ordinary index for _read_dev, _points, _plain_len, _export (blob version
+ *                  1), _import_dev and _destroy.
+ *                  The points: every block of the stream is a candidate {bit of the file where it begins, plaintext offset of
+ *                  its first byte}, in stream order.  Levels 1..9: one kernel behind the compressor's own, one thread per
+ *                  block of the engine (a block per 61440 positions, each ending on a byte boundary), writes the block's byte
+ *                  in the deflate data and the first byte it codes -- its first position if a token starts there, otherwise
+ *                  the next token start -- and these 16 bytes per block come down with the compressed size, before the
+ *                  windows are gathered.  Level 0: stored block j is {8 * (header_len + 65540 * j), 65535 * j}, worked out on
+ *                  the host.  Point 0 is {8 * header_len, 0, 0}; walking the candidates, one becomes a point when its out_off
+ *                  is at least span_bytes past the last point and in front of src_len.  The windows, min(32768, out_off)
+ *                  bytes each, are gathered from the PLAINTEXT d_src into memory the index owns.
+ *                  THE BOUND no decode-built index gives: neighbouring candidates are at most 61440 + 257 plaintext bytes
+ *                  apart (65535 at level 0), so for every k   out_off[k + 1] - out_off[k] < span_bytes + 65536   and
+ *                  plain_len - out_off[last] < span_bytes + 65536: a read never decodes more than that in front of its range,
+ *                  however well the data compresses.
+ *                  At most one host synchronisation more than compress2_dev makes (the window gather's).  Synchronous.  One
+ *                  stream below 4 GiB, strategy 0, windowBits 15, as compress2_dev. */
 size_t zng_rocm_compress_bound(size_t source_len, int format);
 int    zng_rocm_compress2_dev(uint8_t *d_dst, size_t *dst_len, const uint8_t *d_src, size_t src_len, int level,
                               int format, void *stream);
+int    zng_rocm_compress2_index_dev(uint8_t *d_dst, size_t *dst_len, const uint8_t *d_src, size_t src_len, int level, int format,
+                                    uint64_t span_bytes, zng_rocm_inflate_index **out, void *stream);
 int    zng_rocm_uncompress2_dev(uint8_t *d_dst, size_t *dst_len, const uint8_t *src, size_t *src_len, int format,
                                 void *stream);
 

@@ -57,6 +57,8 @@ enum ScratchSlot {
     kScrDynSegLen,          // device: u32 length per block | the histogram snapshots of every segment
     kScrDynSegLenHost,      // pinned: {compressed size, does-not-fit flag} per stream on their way down
     kScrDynDstOff,          // device: u64 per block, the scan and each block's place in its stream | the sizes per stream
+    kScrDynPoints,          // device: {place in the stream, first plaintext byte} per block (rows_block_points_kernel)
+    kScrDynPointsHost,      // pinned: the same rows on their way down
     kScrChunkList,          // device: work list of zng_rocm_chunkmemset_safe_dev (long / memmove-order copies)
     kScrInflate,            // device: tokens | segs | literals | symbols of the one-shot inflate
     kScrInflateHost,        // pinned token staging of the batched inflate

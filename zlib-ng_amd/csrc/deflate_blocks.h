@@ -8,6 +8,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "../../include/zng_rocm.h"
 #include "deflate_rows_plan.h"      // BlkJob
 
@@ -17,13 +19,15 @@ struct Workspace;
 
 // The blocks of one round, still in their slots (scratch of the workspace: valid until the next call on the same HIP stream
 // that uses the rows engine).  Block k belongs to stream blk[k].stream & 0x7fffffff, holds seg_len[k] bytes at blk[k].out and
-// begins at byte in_stream[k] of its stream's deflate data; sizes[2 * s] is the whole length of stream s.
+// begins at byte in_stream[k] of its stream's deflate data; sizes[2 * s] is the whole length of stream s.  bm_base: the token-start
+// bitmaps blk[k].bm_off counts from (what rows_block_points_kernel reads).
 struct RowsBlocks {
     const BlkJob             *blk;
     const uint32_t           *seg_len;
     const unsigned long long *in_stream;
     const unsigned long long *sizes;
     size_t                    nblk;
+    const unsigned long long *bm_base;
 };
 
 // One round through the engine, levels 1..9: the streams of `jobs` (in / in_len / dict_len / flags of each), every stream cut
@@ -52,9 +56,15 @@ struct RowsRequest {
 };
 struct RowsDone {
     unsigned long long *h_sizes;     // kRowsOutHost: valid once the stream has been synchronised
-    RowsBlocks          blocks;      // kRowsOutKeep
+    RowsBlocks          blocks;      // every mode: the block table (the slots' bytes are the caller's to place only in kRowsOutKeep)
 };
 uint32_t deflate_rows_segment_bytes(size_t total_in);
 int deflate_rows_enqueue(const RowsRequest &rq, Workspace *ws, hipStream_t st, RowsDone *done);
+
+// zng_rocm_deflate_dev(level, ...) -- its checks, its texts, its bytes, its one synchronisation -- that also hands back, at levels
+// 1..9, one row {byte of the block in the deflate data, plaintext offset of its first byte} per block (rows_block_points_kernel
+// behind the engine's kernels, read back with the sizes: deflate_index_plan.h).  Level 0 leaves `rows` empty: its blocks are closed form.
+int deflate_rows_points_dev(int level, const uint8_t *d_in, size_t in_len, uint8_t *d_out, size_t out_cap, size_t *out_len,
+                            std::vector<uint64_t> &rows, hipStream_t st);
 
 }  // namespace zr

@@ -26,6 +26,8 @@
 //   K3 segments_scan_kernel: the segments' places in the output (a one-block scan, per stream), the compressed sizes,
 //        the out_cap check -- on the device, so the call has no synchronisation before its last kernel;
 //   K4 gather_segments_kernel packs the segments back to back.
+//   rows_block_points_kernel (zng_rocm_compress2_index_dev alone, behind K3): per block its byte in the stream and the first
+//        plaintext byte it codes -- what an access point of a zng_rocm_inflate_index needs, without decoding anything.
 //
 // Per segment the block type is chosen as zng_tr_flush_block does (trees.c:660-719): stored if that is not larger,
 // else static if not larger than dynamic.  Not bit-identical to the reference's stream (different parse, one block
@@ -671,6 +673,31 @@ void segments_scan_kernel(const BlkJob *__restrict__ jobs, const uint32_t *__res
     }
 }
 
+// Behind K3, for zng_rocm_compress2_index_dev alone: what every block start needs to become an access point of a
+// zng_rocm_inflate_index (deflate_index_plan.h), while the token scratch is still there.  One thread per block:
+//   rows[2 * k]     = dst_off[k], the block's byte in its stream's deflate data (every block ends on a byte boundary)
+//   rows[2 * k + 1] = the position of the first byte the block codes -- `lo` exactly as emit_dynamic_kernel finds it: blo if a
+//                     token starts there, else the next token start of the segment, never past the block's last byte + 1
+__global__ __launch_bounds__(256)
+void rows_block_points_kernel(const BlkJob *__restrict__ jobs, const unsigned long long *__restrict__ bm_base,
+                              const unsigned long long *__restrict__ dst_off, uint32_t nblk, unsigned long long *__restrict__ rows) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nblk) return;
+    const BlkJob &job = jobs[k];
+    const uint32_t first = job.seg_start - job.seg_start % kRowBatch;
+    const unsigned long long *bm = bm_base + job.bm_off;
+    const uint32_t hi_rel = job.seg_end - first;
+    uint32_t lo = job.blo, hi = job.bhi;
+    if (lo < hi) {
+        const uint32_t r0 = lo - first;
+        lo = ((bm[r0 >> 6] >> (r0 & 63u)) & 1ull) ? lo : first + next_start_rel(bm, r0, hi_rel);
+        hi = first + next_start_rel(bm, job.bhi - 1u - first, hi_rel);
+        if (lo > hi) lo = hi;
+    }
+    rows[2 * k] = dst_off[k];
+    rows[2 * k + 1] = lo;
+}
+
 // K4: pack the segments back to back (byte granular); a stream that does not fit its buffer is cut at the buffer's end
 // (K3 has flagged it)
 __global__ __launch_bounds__(256)
@@ -791,10 +818,8 @@ int deflate_rows_enqueue(const RowsRequest &rq, Workspace *ws, hipStream_t st, R
     ZR_HIP(hipGetLastError());
     hipLaunchKernelGGL(segments_scan_kernel, dim3(1), dim3(1024), 0, st, d_blk, d_seg_len, (uint32_t)nb, d_excl, d_dst_off, d_res);
     ZR_HIP(hipGetLastError());
-    if (keep) {
-        done->blocks = RowsBlocks{d_blk, d_seg_len, d_dst_off, d_res, nb};
-        return host_tables_release(ws, st);
-    }
+    done->blocks = RowsBlocks{d_blk, d_seg_len, d_dst_off, d_res, nb, d_bm};
+    if (keep) return host_tables_release(ws, st);
     hipLaunchKernelGGL(gather_segments_kernel, dim3(rq.njobs > 64 ? 2 : 4, (unsigned)nb), dim3(256), 0, st, d_blk, d_seg_len, d_dst_off);
     ZR_HIP(hipGetLastError());
     if (rq.out == kRowsOutDevice)
@@ -848,9 +873,11 @@ static int stored_one_stream(const uint8_t *d_in, size_t in_len, uint32_t flags,
 
 // The one-stream calls behind their checks: level 0 as above, levels 1..9 as one request on the caller's stream.  Scratch is
 // keyed by that stream (context.h): concurrent callers on different streams share nothing.  d_result: where the sizes go on the
-// device (async), or null: the call waits for them and writes *out_len.
+// device (async), or null: the call waits for them and writes *out_len.  points (the waiting form, levels 1..9): receives
+// rows_block_points_kernel's two words per block, which come down with the sizes in front of the same one synchronisation.
 static int rows_one_stream(int level, int strategy, int window_bits, const uint8_t *d_in, size_t in_len, uint32_t dict_len, uint32_t flags,
-                           uint8_t *d_out, size_t out_cap, size_t *out_len, uint64_t *d_result, hipStream_t st) {
+                           uint8_t *d_out, size_t out_cap, size_t *out_len, uint64_t *d_result, hipStream_t st,
+                           std::vector<uint64_t> *points = nullptr) {
     DeviceGuard dev;
     Workspace *ws = workspace_for(st);
     if (!ws) return ZNG_ROCM_ENOMEM;
@@ -862,13 +889,38 @@ static int rows_one_stream(int level, int strategy, int window_bits, const uint8
     RowsDone done;
     if (int rc = deflate_rows_enqueue(rq, ws, st, &done)) return rc;
     if (d_result) return ZNG_ROCM_OK;
+    unsigned long long *h_rows = nullptr;
+    const size_t nb = done.blocks.nblk;
+    if (points) {
+        unsigned long long *d_rows = nullptr;
+        if (int rc = scratch_reserve(ws, kScrDynPoints, nb * 2 * sizeof(unsigned long long), false, (void **)&d_rows)) return rc;
+        if (int rc = scratch_reserve(ws, kScrDynPointsHost, nb * 2 * sizeof(unsigned long long), true, (void **)&h_rows)) return rc;
+        hipLaunchKernelGGL(rows_block_points_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, done.blocks.blk, done.blocks.bm_base,
+                           done.blocks.in_stream, (uint32_t)nb, d_rows);
+        ZR_HIP(hipGetLastError());
+        ZR_HIP(hipMemcpyAsync(h_rows, d_rows, nb * 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    }
     ZR_HIP(hipStreamSynchronize(st));
     if (done.h_sizes[1]) {
         set_error("compressed size %llu exceeds out_cap", done.h_sizes[0]);
         return kRowsBufError;
     }
     *out_len = (size_t)done.h_sizes[0];
+    if (points) points->assign(h_rows, h_rows + 2 * nb);
     return ZNG_ROCM_OK;
+}
+
+// deflate_blocks.h: zng_rocm_deflate_dev behind the same checks, with the rows of its blocks
+int deflate_rows_points_dev(int level, const uint8_t *d_in, size_t in_len, uint8_t *d_out, size_t out_cap, size_t *out_len,
+                            std::vector<uint64_t> &rows, hipStream_t st) {
+    rows.clear();
+    if (!ctx()) {
+        set_error("zng_rocm_init() has not succeeded");
+        return ZNG_ROCM_ENODEV;
+    }
+    if (RowsRefusal why = rows_one_check(kRowsEntryBlock, level, 0, kWinBitsMax, !out_len, d_in, d_out, in_len, 0, 0, out_cap))
+        return rows_refused(kRowsEntryBlock, why, nullptr);
+    return rows_one_stream(level, 0, kWinBitsMax, d_in, in_len, 0, 0, d_out, out_cap, out_len, nullptr, st, &rows);
 }
 
 }  // namespace zr

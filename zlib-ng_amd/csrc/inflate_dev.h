@@ -81,6 +81,14 @@ struct IndexSink {
 };
 IndexSink *inflate_index_sink();
 void inflate_index_sink_set(IndexSink *sink);
+// inflate_index.hip: the index of a stream whose block starts are known -- to the build above from its decode, to
+// zng_rocm_compress2_index_dev (oneshot.hip) from the compressor.  cands: {bit of the file, plaintext offset} in stream order
+// (inflate_index_plan.h: index_select thins them to head.span_bytes); d_plain: the plaintext the windows are gathered from.
+// `who` names the call in the error text.  Returns 0 with *out set, or an error with *out untouched.
+struct IndexHead;
+struct IndexCand;
+int inflate_index_from_cands(const char *who, const IndexHead &head, const IndexCand *cands, size_t ncands, const uint8_t *d_plain,
+                             hipStream_t st, zng_rocm_inflate_index **out);
 void inflate_large_forget_parts();       // the part counters of the calling thread back to 0 ("the sequential decoder did it")
 void inflate_large_reset_counters();     // all of the calling thread's last_* counters: nothing ran
 

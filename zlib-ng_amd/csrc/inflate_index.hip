@@ -8,6 +8,8 @@
 //   index_select             the candidates at least span_bytes apart become the access points
 //   index_windows_kernel     one workgroup per point moves the min(32768, out_off) bytes in front of it out of d_dst into
 //                            memory the index owns (bgzf_copy.h: d_dst has whatever alignment the caller gave it)
+//   (the last two steps are inflate_index_from_cands, which zng_rocm_compress2_index_dev -- oneshot.hip -- shares: its
+//   candidates come from the compressor's block table and its windows from the plaintext it compressed, nothing is decoded)
 //
 // zng_rocm_inflate_index_read_dev, per round of the plan
 //   jobs, span table and slices go up in one copy
@@ -94,6 +96,48 @@ const char *range_msg(const IndexRangeOut &o) {
 
 }  // namespace
 
+// inflate_dev.h: candidates -> points (index_select) -> the index object -> its windows, gathered by index_windows_kernel from the
+// plaintext at d_plain (bgzf_copy.h: whatever alignment the caller gave it).  Synchronises `st` when there is a window to gather.
+int inflate_index_from_cands(const char *who, const IndexHead &head, const IndexCand *cands, size_t ncands, const uint8_t *d_plain,
+                             hipStream_t st, zng_rocm_inflate_index **out) {
+    std::vector<zng_rocm_access_point> pts;
+    index_select(cands, ncands, head.span_bytes, head.plain_len, head.header_len, pts);
+    DeviceGuard dev;
+    zng_rocm_inflate_index *idx = nullptr;
+    if (int e = index_new(head, pts, &idx)) return e;
+    const size_t n = idx->pts.size();
+    if (n > 1) {
+        Workspace *ws = workspace_for(st);
+        int e = ws ? ZNG_ROCM_OK : ZNG_ROCM_ENOMEM;
+        IndexMove *d_moves = nullptr, *h_moves = nullptr;
+        if (!e) {
+            std::lock_guard<std::mutex> use(ws->mu);
+            e = scratch_reserve(ws, kScrIndexRead, n * sizeof(IndexMove), false, (void **)&d_moves);
+            if (!e) e = host_tables_acquire(ws);
+            if (!e) e = scratch_reserve(ws, kScrIndexReadHost, n * sizeof(IndexMove), true, (void **)&h_moves);
+            if (!e) {
+                for (size_t k = 0; k < n; ++k) {
+                    const zng_rocm_access_point &p = idx->pts[k];
+                    h_moves[k] = IndexMove{d_plain + (p.out_off - p.window_len), idx->d_windows + idx->woff[k], p.window_len, 0u, 0u, 0u};
+                }
+                if (hipMemcpyAsync(d_moves, h_moves, n * sizeof(IndexMove), hipMemcpyHostToDevice, st) != hipSuccess) e = ZNG_ROCM_EHIP;
+            }
+            if (!e) e = host_tables_release(ws, st);
+        }
+        if (!e) {
+            hipLaunchKernelGGL(index_windows_kernel, dim3((unsigned)(n < (1u << 20) ? n : (1u << 20))), dim3(256), 0, st, d_moves, (uint32_t)n);
+            if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) e = ZNG_ROCM_EHIP;
+        }
+        if (e) {
+            set_error("%s: gathering the windows failed", who);
+            zng_rocm_inflate_index_destroy(idx);
+            return e;
+        }
+    }
+    *out = idx;
+    return ZNG_ROCM_OK;
+}
+
 }  // namespace zr
 
 using namespace zr;
@@ -142,42 +186,9 @@ int zng_rocm_inflate_index_build_dev(int format, const uint8_t *d_src, size_t sr
     const uint64_t plain_len = *out_len;
     std::vector<IndexCand> cands(sink.cands.size());
     for (size_t i = 0; i < cands.size(); ++i) cands[i] = IndexCand{sink.cands[i].first + 8 * sink.header_len, sink.cands[i].second};
-    std::vector<zng_rocm_access_point> pts;
-    index_select(cands.data(), cands.size(), span, plain_len, sink.header_len, pts);
-    DeviceGuard dev;
-    zng_rocm_inflate_index *idx = nullptr;
-    if (int e = index_new(IndexHead{(uint32_t)format, sink.header_len, (uint64_t)*in_used, plain_len, span}, pts, &idx)) return e;
-    const size_t n = idx->pts.size();
-    if (n > 1) {
-        hipStream_t st = (hipStream_t)stream;
-        Workspace *ws = workspace_for(st);
-        int e = ws ? ZNG_ROCM_OK : ZNG_ROCM_ENOMEM;
-        IndexMove *d_moves = nullptr, *h_moves = nullptr;
-        if (!e) {
-            std::lock_guard<std::mutex> use(ws->mu);
-            e = scratch_reserve(ws, kScrIndexRead, n * sizeof(IndexMove), false, (void **)&d_moves);
-            if (!e) e = host_tables_acquire(ws);
-            if (!e) e = scratch_reserve(ws, kScrIndexReadHost, n * sizeof(IndexMove), true, (void **)&h_moves);
-            if (!e) {
-                for (size_t k = 0; k < n; ++k) {
-                    const zng_rocm_access_point &p = idx->pts[k];
-                    h_moves[k] = IndexMove{d_dst + (p.out_off - p.window_len), idx->d_windows + idx->woff[k], p.window_len, 0u, 0u, 0u};
-                }
-                if (hipMemcpyAsync(d_moves, h_moves, n * sizeof(IndexMove), hipMemcpyHostToDevice, st) != hipSuccess) e = ZNG_ROCM_EHIP;
-            }
-            if (!e) e = host_tables_release(ws, st);
-        }
-        if (!e) {
-            hipLaunchKernelGGL(index_windows_kernel, dim3((unsigned)(n < (1u << 20) ? n : (1u << 20))), dim3(256), 0, st, d_moves, (uint32_t)n);
-            if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) e = ZNG_ROCM_EHIP;
-        }
-        if (e) {
-            set_error("zng_rocm_inflate_index_build_dev: gathering the windows failed");
-            zng_rocm_inflate_index_destroy(idx);
-            return e;
-        }
-    }
-    *out = idx;
+    if (int e = inflate_index_from_cands("zng_rocm_inflate_index_build_dev", IndexHead{(uint32_t)format, sink.header_len, (uint64_t)*in_used, plain_len, span},
+                                         cands.data(), cands.size(), d_dst, (hipStream_t)stream, out))
+        return e;
     return 1;
 }
 

@@ -26,6 +26,22 @@ def compress2_dev(src, level=-1, fmt=ZLIB, length=None, stream=None):
     return dst, dlen.value
 
 
+def compress2_index_dev(src, level=-1, fmt=ZLIB, span_bytes=0, length=None, stream=None):
+    """zng_rocm_compress2_index_dev: device plaintext -> (device tensor, compressed length, InflateIndex of that stream); the
+    tensor and the length are compress2_dev's, the index comes from the compressor's own block table, with nothing decoded"""
+    import torch
+    from .inflate import InflateIndex
+    rocm._need_init()
+    n = src.numel() if length is None else length
+    cap = compress_bound(n, fmt)
+    dst = torch.empty(cap, dtype=torch.uint8, device=src.device)
+    dlen, h = C.c_size_t(cap), C.c_void_p(None)
+    rc = rocm.lib().zng_rocm_compress2_index_dev(rocm._dev_ptr(dst), C.byref(dlen), rocm._dev_ptr(src) if n else None, n, level, fmt,
+                                                 int(span_bytes), C.byref(h), rocm._stream_ptr(stream))
+    rocm._check(rc, "zng_rocm_compress2_index_dev")
+    return dst, dlen.value, InflateIndex(h.value)
+
+
 def uncompress2_dev(src_bytes, dst, fmt=ZLIB, stream=None):
     """host stream -> plaintext in the CUDA tensor dst; returns (zlib status, produced, consumed, message)"""
     rocm._need_init()

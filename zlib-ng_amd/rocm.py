@@ -145,6 +145,8 @@ _PROTOS = {
     "zng_rocm_compress_bound": (C.c_size_t, [C.c_size_t, C.c_int]),
     "zng_rocm_compress2_dev": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t, C.c_int, C.c_int,
                                          C.c_void_p]),
+    "zng_rocm_compress2_index_dev": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t, C.c_int, C.c_int,
+                                               C.c_uint64, C.POINTER(C.c_void_p), C.c_void_p]),
     "zng_rocm_uncompress2_dev": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.c_void_p, C.POINTER(C.c_size_t),
                                            C.c_int, C.c_void_p]),
     "zng_rocm_deflate_async_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
