@@ -1185,6 +1185,16 @@ int    zng_rocm_hook_reset(zng_rocm_hook *h);                             /* for
 int    zng_rocm_hook_set_history(zng_rocm_hook *h, const uint8_t *dict, uint32_t len);
 /* deflateGetDictionary / inflateGetDictionary (deflate.c:521-545, inflate.c:1195-1212): dict may be NULL (length only) */
 int    zng_rocm_hook_get_history(zng_rocm_hook *h, uint8_t *dict, uint32_t *len);
+/* deflateCopy / inflateCopy (deflate.c:1131-1181, inflate.c:1379-1413): both memcpy the state block, which is enough for
+ * DFLTCC's plain-data arch block and not for one that owns a hook.  *out = a new hook with a HIP stream, check words and
+ * staging of its own and the source's history, copied device to device behind everything already enqueued on the source's
+ * stream and complete when the call returns: source and clone share nothing and may be used and destroyed in either order.
+ * The clone has the default block room, not what the source's buffers have grown to (they grow on first use, as any
+ * hook's).  The plaintext the source's last zng_rocm_hook_inflate* call handed out is NOT part of the clone: it is hook
+ * memory, valid until the next call, and whoever copies a stream with some of it undelivered copies it himself
+ * (rocm_inflate.c).  ZNG_ROCM_EINVAL for a null argument, ZNG_ROCM_ENODEV before zng_rocm_init() or for a source from before
+ * a zng_rocm_shutdown(), ZNG_ROCM_ENOMEM / ZNG_ROCM_EHIP otherwise; *out = NULL on every failure, the source untouched always. */
+int    zng_rocm_hook_clone(const zng_rocm_hook *src, zng_rocm_hook **out);
 size_t zng_rocm_hook_deflate_bound(size_t in_len);
 /* One block of the stream: `in` (host) is compressed at `level` (0..9, as zng_rocm_deflate_block_dev) against the
  * history, the block lands at `out` (host, out_cap >= zng_rocm_hook_deflate_bound(in_len)) and always ends on a byte

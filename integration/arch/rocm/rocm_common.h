@@ -27,8 +27,9 @@ typedef struct {
     uint8_t *in_buf;            /* the carry: compressed bytes from the start of the first incomplete block on */
     size_t   in_len, in_cap;
     unsigned carry_bit;         /* bit of in_buf[0] at which that block starts (0..7) */
-    const uint8_t *out;         /* plaintext (memory of the hook) next_out has not had room for yet */
+    const uint8_t *out;         /* plaintext (memory of the hook, or out_own) next_out has not had room for yet */
     size_t   out_pos, out_len;
+    uint8_t *out_own;           /* set by inflateCopy only: the source's undelivered plaintext, copied out of ITS hook's memory */
     uint32_t check;             /* check value of the plaintext so far, handed to state->check once the stream is delivered */
     const char *msg;            /* bad: the reference's text, reported once the blocks in front of the error are delivered */
     int      used, done, bad, disabled;

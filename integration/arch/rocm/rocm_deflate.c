@@ -53,6 +53,42 @@ void Z_INTERNAL PREFIX(archrocm_deflate_end)(PREFIX3(streamp) strm) {           
     memset(a, 0, sizeof *a);
 }
 
+/* DEFLATE_COPY_HOOK, in deflateCopy() behind the memcpy of the state block (deflate.c:1149-1152): at that point dest's
+ * arch block is source's, pointer for pointer.  Nothing of it may stay: two streams would compress into one device history
+ * through one staging buffer, and the second deflateEnd would release what the first already has.  The gathered input and
+ * the bytes next_out still owes are copied with dest's zalloc, the hook is cloned (history device to device).  A device
+ * that cannot give the clone does not fail the copy: dest continues `disabled` without a hook, produce() writes stored
+ * blocks, which need no history -- what a device failure mid-stream gets.  Only a failed zalloc is an error, and then dest's
+ * block is zeroed first, so the deflateEnd(dest) that follows in deflateCopy finds nothing to release.  source is only read. */
+int Z_INTERNAL PREFIX(archrocm_deflate_copy)(PREFIX3(streamp) dest, PREFIX3(streamp) source) {
+    const arch_deflate_state *sa = &((deflate_state *)source->state)->arch;
+    arch_deflate_state *da = &((deflate_state *)dest->state)->arch;
+    const size_t owed = sa->out_len - sa->out_pos;
+    memset(da, 0, sizeof *da);
+    if (sa->in_len) {
+        if (!(da->in_buf = (uint8_t *)arch_alloc(dest, sa->in_len))) return Z_MEM_ERROR;
+        memcpy(da->in_buf, sa->in_buf, sa->in_len);
+        da->in_len = da->in_cap = sa->in_len;
+    }
+    if (owed) {
+        if (!(da->out_buf = (uint8_t *)arch_alloc(dest, owed))) {
+            arch_free(dest, da->in_buf);
+            memset(da, 0, sizeof *da);
+            return Z_MEM_ERROR;
+        }
+        memcpy(da->out_buf, sa->out_buf + sa->out_pos, owed);
+        da->out_len = da->out_cap = owed;
+    }
+    da->used = sa->used;
+    da->finished = sa->finished;
+    da->disabled = sa->disabled;
+    if (sa->hook && !sa->disabled && zng_rocm_hook_clone(sa->hook, &da->hook) != ZNG_ROCM_OK) {
+        da->hook = NULL;
+        da->disabled = 1;
+    }
+    return Z_OK;
+}
+
 /* what the device takes: every level, every strategy (default, filtered, Z_HUFFMAN_ONLY, Z_RLE, Z_FIXED), every window
  * deflateInit2 leaves in s->w_bits (9..15: it has turned 8 into 9, deflate.c:322-323) -- zng_rocm_deflate_window_block_dev.
  * zlib-ng writes the zlib header itself from s->w_bits (deflate.c:870), so the window changes nothing else on the write path */

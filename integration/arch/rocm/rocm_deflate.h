@@ -1,6 +1,10 @@
 /* arch/rocm/rocm_deflate.h -- the hook block deflate.c includes instead of its defaults when ROCM_DEFLATE is defined
- * (deflate.c:72-106; precedent arch/s390/dfltcc_deflate.h:17-56).  One addition the reference does not have yet:
- * DEFLATE_END_HOOK, invoked from deflateEnd() before free_deflate() -- DFLTCC owns no resources, a GPU backend does.
+ * (deflate.c:72-106; precedent arch/s390/dfltcc_deflate.h:17-56).  Two additions the reference does not have yet:
+ * DEFLATE_END_HOOK, invoked from deflateEnd() before free_deflate() -- DFLTCC owns no resources, a GPU backend does;
+ * DEFLATE_COPY_HOOK, invoked from deflateCopy() behind the memcpy of the state block, as soon as the copy has an allocation
+ * record of its own (deflate.c:1152) and in front of every later failure path (:1158) -- that memcpy is all DFLTCC's plain-data
+ * block needs, ours holds owning pointers.  On a value other than Z_OK deflateCopy calls deflateEnd(dest) and returns it
+ * (INTEGRATION.md section 6).
  * Function names carry `archrocm_`, not `rocm_`: under the native API PREFIX() prepends `zng_`, and `zng_rocm_*` is the name space of
  * libzng_rocm's own entry points (a `zng_rocm_deflate_bound` here would shadow the library's).
  */
@@ -23,6 +27,7 @@ _Static_assert(ROCM_Z_DEFAULT_STRATEGY == Z_DEFAULT_STRATEGY && ROCM_Z_FILTERED 
 
 void Z_INTERNAL PREFIX(archrocm_reset_deflate_state)(PREFIX3(streamp) strm);
 void Z_INTERNAL PREFIX(archrocm_deflate_end)(PREFIX3(streamp) strm);
+int  Z_INTERNAL PREFIX(archrocm_deflate_copy)(PREFIX3(streamp) dest, PREFIX3(streamp) source);
 int  Z_INTERNAL PREFIX(archrocm_can_deflate)(PREFIX3(streamp) strm);
 int  Z_INTERNAL PREFIX(archrocm_deflate)(PREFIX3(streamp) strm, int flush, block_state *result);
 int  Z_INTERNAL PREFIX(archrocm_deflate_params)(PREFIX3(streamp) strm, int level, int strategy, int *flush);
@@ -43,6 +48,7 @@ size_t Z_INTERNAL PREFIX(archrocm_deflate_bound)(size_t source_len);
     } while (0)
 #define DEFLATE_RESET_KEEP_HOOK PREFIX(archrocm_reset_deflate_state)
 #define DEFLATE_END_HOOK PREFIX(archrocm_deflate_end)
+#define DEFLATE_COPY_HOOK PREFIX(archrocm_deflate_copy)
 #define DEFLATE_PARAMS_HOOK(strm, level, strategy, hook_flush) \
     do { \
         int err = PREFIX(archrocm_deflate_params)((strm), (level), (strategy), (hook_flush)); \

@@ -39,7 +39,8 @@ void Z_INTERNAL PREFIX(archrocm_reset_inflate_state)(PREFIX3(streamp) strm) {   
     arch_inflate_state *a = &((struct inflate_state *)strm->state)->arch;
     a->in_len = a->out_pos = a->out_len = 0;
     a->carry_bit = 0;
-    a->out = NULL;
+    arch_free(strm, a->out_own);
+    a->out = a->out_own = NULL;
     a->msg = NULL;
     a->used = a->done = a->bad = 0;
     if (a->hook && zng_rocm_hook_reset(a->hook) != ZNG_ROCM_OK) a->disabled = 1;
@@ -49,7 +50,48 @@ void Z_INTERNAL PREFIX(archrocm_inflate_end)(PREFIX3(streamp) strm) {           
     arch_inflate_state *a = &((struct inflate_state *)strm->state)->arch;
     zng_rocm_hook_destroy(a->hook);
     arch_free(strm, a->in_buf);
+    arch_free(strm, a->out_own);
     memset(a, 0, sizeof *a);
+}
+
+/* INFLATE_COPY_HOOK, in inflateCopy() behind the memcpy of the state block (inflate.c:1398-1406): dest's arch block is
+ * source's, pointer for pointer, and none of the pointers may stay (one hook, one carry, and `out` inside the SOURCE's
+ * hook, which its next decode overwrites).  The carry is copied with dest's zalloc, the hook is cloned (history device to
+ * device), and plaintext next_out has not had room for moves into out_own, memory dest owns until it is delivered.  A
+ * stream whose history is on the device cannot continue without it, so unlike deflateCopy every failure is Z_MEM_ERROR,
+ * with dest's block zeroed first: the inflateEnd(dest) that follows in inflateCopy finds nothing to release.  source is
+ * only read. */
+int Z_INTERNAL PREFIX(archrocm_inflate_copy)(PREFIX3(streamp) dest, PREFIX3(streamp) source) {
+    const arch_inflate_state *sa = &((struct inflate_state *)source->state)->arch;
+    arch_inflate_state *da = &((struct inflate_state *)dest->state)->arch;
+    const size_t owed = sa->out_len - sa->out_pos;
+    memset(da, 0, sizeof *da);
+    if (sa->in_len) {
+        if (!(da->in_buf = (uint8_t *)arch_alloc(dest, sa->in_len))) goto fail;
+        memcpy(da->in_buf, sa->in_buf, sa->in_len);
+        da->in_len = da->in_cap = sa->in_len;
+    }
+    da->carry_bit = sa->carry_bit;
+    if (owed) {
+        if (!(da->out_own = (uint8_t *)arch_alloc(dest, owed))) goto fail;
+        memcpy(da->out_own, sa->out + sa->out_pos, owed);
+        da->out = da->out_own;
+        da->out_len = owed;
+    }
+    da->check = sa->check;
+    da->msg = sa->msg;
+    da->used = sa->used;
+    da->done = sa->done;
+    da->bad = sa->bad;
+    da->disabled = sa->disabled;
+    /* (a disabled stream never comes back to its hook, archrocm_can_inflate: it needs none) */
+    if (sa->hook && !sa->disabled && zng_rocm_hook_clone(sa->hook, &da->hook) != ZNG_ROCM_OK) goto fail;
+    return Z_OK;
+fail:
+    arch_free(dest, da->in_buf);
+    arch_free(dest, da->out_own);
+    memset(da, 0, sizeof *da);
+    return Z_MEM_ERROR;
 }
 
 int Z_INTERNAL PREFIX(archrocm_can_inflate)(PREFIX3(streamp) strm) {
@@ -150,6 +192,8 @@ rocm_inflate_action Z_INTERNAL PREFIX(archrocm_inflate)(PREFIX3(streamp) strm, i
     const char *msg = NULL;
     const int rc = zng_rocm_hook_inflate_blocks(a->hook, a->in_buf, total, a->carry_bit, kind, &cv, &out, &out_len, &end_bit, &msg);
     if (rc == 1 || rc == 0 || (rc == Z_DATA_ERROR && msg)) {     /* (-3 without a text: a refused argument) */
+        arch_free(strm, a->out_own);                    /* (a copy's inherited plaintext: all delivered, or no input is taken) */
+        a->out_own = NULL;
         a->out = out;
         a->out_pos = 0;
         a->out_len = out_len;

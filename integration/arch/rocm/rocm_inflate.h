@@ -1,6 +1,9 @@
 /* arch/rocm/rocm_inflate.h -- the hook block inflate_p.h includes instead of its defaults when ROCM_INFLATE is defined
- * (inflate_p.h:11-41; precedent arch/s390/dfltcc_inflate.h:21-65).  One addition the reference does not have yet:
- * INFLATE_END_HOOK, invoked from inflateEnd() before free_inflate(). */
+ * (inflate_p.h:11-41; precedent arch/s390/dfltcc_inflate.h:21-65).  Two additions the reference does not have yet:
+ * INFLATE_END_HOOK, invoked from inflateEnd() before free_inflate(), and INFLATE_COPY_HOOK, invoked from inflateCopy()
+ * behind the memcpy of the state block, as soon as the copy has an allocation record of its own (inflate.c:1406) and
+ * dest->state points at it; on a value other than Z_OK inflateCopy calls inflateEnd(dest) and returns it (INTEGRATION.md
+ * section 6). */
 #ifndef ROCM_INFLATE_H_
 #define ROCM_INFLATE_H_
 #include "rocm_common.h"
@@ -13,6 +16,7 @@ typedef enum {
 
 void Z_INTERNAL PREFIX(archrocm_reset_inflate_state)(PREFIX3(streamp) strm);
 void Z_INTERNAL PREFIX(archrocm_inflate_end)(PREFIX3(streamp) strm);
+int  Z_INTERNAL PREFIX(archrocm_inflate_copy)(PREFIX3(streamp) dest, PREFIX3(streamp) source);
 int  Z_INTERNAL PREFIX(archrocm_can_inflate)(PREFIX3(streamp) strm);
 rocm_inflate_action Z_INTERNAL PREFIX(archrocm_inflate)(PREFIX3(streamp) strm, int flush, int *ret);
 int  Z_INTERNAL PREFIX(archrocm_was_inflate_used)(PREFIX3(streamp) strm);
@@ -22,6 +26,7 @@ int  Z_INTERNAL PREFIX(archrocm_inflate_get_dictionary)(PREFIX3(streamp) strm, u
 
 #define INFLATE_RESET_KEEP_HOOK PREFIX(archrocm_reset_inflate_state)
 #define INFLATE_END_HOOK PREFIX(archrocm_inflate_end)
+#define INFLATE_COPY_HOOK PREFIX(archrocm_inflate_copy)
 #define INFLATE_PRIME_HOOK(strm, bits, value) \
     do { if (PREFIX(archrocm_inflate_disable)((strm))) return Z_STREAM_ERROR; } while (0)
 #define INFLATE_TYPEDO_HOOK(strm, flush) \

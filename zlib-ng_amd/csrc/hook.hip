@@ -192,6 +192,34 @@ void zng_rocm_hook_destroy(zng_rocm_hook *h) {
     delete h;
 }
 
+// deflateCopy / inflateCopy (deflate.c:1131-1181, inflate.c:1379-1413) for a stream whose history the device holds: a new
+// hook with the source's history and nothing else of it.  The history is read on the SOURCE's stream, so the copy stands
+// behind whatever that stream still has in flight, and the call waits for it: afterwards the two share nothing.
+int zng_rocm_hook_clone(const zng_rocm_hook *src, zng_rocm_hook **out) {
+    if (!out) return ZNG_ROCM_EINVAL;
+    *out = nullptr;
+    if (!src) return ZNG_ROCM_EINVAL;
+    if (stale(src)) {
+        set_error("zng_rocm_hook_clone: no context, or a hook from before zng_rocm_shutdown()");
+        return ZNG_ROCM_ENODEV;
+    }
+    zng_rocm_hook *h = nullptr;
+    if (int rc = zng_rocm_hook_create(&h, 0)) return rc;           // the default block room, not what src has grown to
+    if (src->hist_len) {
+        DeviceGuard dev;
+        const size_t at = kHist - src->hist_len;
+        if (hipMemcpyAsync(h->d_in + at, src->d_in + at, src->hist_len, hipMemcpyDeviceToDevice, src->st) != hipSuccess ||
+            hipStreamSynchronize(src->st) != hipSuccess) {
+            set_error("zng_rocm_hook_clone: history copy failed");
+            zng_rocm_hook_destroy(h);
+            return ZNG_ROCM_EHIP;
+        }
+    }
+    h->hist_len = src->hist_len;
+    *out = h;
+    return ZNG_ROCM_OK;
+}
+
 int zng_rocm_hook_reset(zng_rocm_hook *h) {
     if (stale(h)) return ZNG_ROCM_ENODEV;
     h->hist_len = 0;

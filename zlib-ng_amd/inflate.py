@@ -83,6 +83,20 @@ class InflateHook:
         buf = C.create_string_buffer(data, max(len(data), 1))
         rocm._check(self.lib.zng_rocm_hook_set_history(self.h, C.addressof(buf), len(data)), "zng_rocm_hook_set_history")
 
+    def get_history(self):
+        n = C.c_uint32(0)
+        buf = C.create_string_buffer(32768)
+        rocm._check(self.lib.zng_rocm_hook_get_history(self.h, C.addressof(buf), C.byref(n)), "zng_rocm_hook_get_history")
+        return buf.raw[:n.value]
+
+    def clone(self):
+        """zng_rocm_hook_clone: a second hook with this one's history and nothing else of it (inflateCopy / deflateCopy)"""
+        other = InflateHook.__new__(InflateHook)
+        other.lib = self.lib
+        other.h = C.c_void_p()
+        rocm._check(self.lib.zng_rocm_hook_clone(self.h, C.byref(other.h)), "zng_rocm_hook_clone")
+        return other
+
     def inflate_blocks(self, data, start_bit=0, check=0, check_value=0):
         """zng_rocm_hook_inflate_blocks on host bytes `data` (the stream from the byte that holds bit start_bit on):
         returns (status, plaintext bytes, end_bit, check value, message)"""

@@ -214,6 +214,7 @@ _PROTOS = {
     "zng_rocm_hook_reset": (C.c_int, [C.c_void_p]),
     "zng_rocm_hook_set_history": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "zng_rocm_hook_get_history": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
+    "zng_rocm_hook_clone": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "zng_rocm_hook_deflate_bound": (C.c_size_t, [C.c_size_t]),
     "zng_rocm_hook_deflate_block": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_uint32, C.c_int,
                                               C.POINTER(C.c_uint32), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
