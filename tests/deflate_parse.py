@@ -283,3 +283,21 @@ def parse(stream, history=b"", strict=True):
         if b.final:
             break
     return Parsed(blocks, bytes(out[hist_len:]), blocks[-1].end)
+
+
+def data_blocks(p):
+    """the blocks that carry data (or the one block of an empty input), without the design's additions: the empty stored
+    block that byte-aligns every non-stored block, and the final empty static block"""
+    blocks = p.blocks
+    assert blocks[-1].final and blocks[-1].btype == STATIC and blocks[-1].nbytes == 0 and blocks[-1].end - blocks[-1].start == 10
+    out, k = [], 0
+    while k < len(blocks) - 1:
+        b = blocks[k]
+        assert b.start % 8 == 0, "every data block starts on a byte"
+        out.append(b)
+        k += 1
+        if b.btype != STORED:
+            m = blocks[k]
+            assert m.btype == STORED and m.nbytes == 0 and not m.final, "the byte-aligning empty stored block"
+            k += 1
+    return out

@@ -87,24 +87,6 @@ def _sets(b):
     return {"lit": (b.lit_hist, b.lit_lens), "dist": (b.dist_hist, b.dist_lens), "cl": (b.cl_hist, b.cl_lens)}
 
 
-def _data_blocks(p):
-    """the blocks that carry data (or the one block of an empty input), without the design's additions: the empty stored
-    block that byte-aligns every non-stored block, and the final empty static block"""
-    blocks = p.blocks
-    assert blocks[-1].final and blocks[-1].btype == dp.STATIC and blocks[-1].nbytes == 0 and blocks[-1].end - blocks[-1].start == 10
-    out, k = [], 0
-    while k < len(blocks) - 1:
-        b = blocks[k]
-        assert b.start % 8 == 0, "every data block starts on a byte"
-        out.append(b)
-        k += 1
-        if b.btype != dp.STORED:
-            m = blocks[k]
-            assert m.btype == dp.STORED and m.nbytes == 0 and not m.final, "the byte-aligning empty stored block"
-            k += 1
-    return out
-
-
 @pytest.mark.parametrize("case,path", _params())
 def test_round_trip(outs, case, path):
     comp = outs.comp[case.name, path]
@@ -124,7 +106,7 @@ def test_round_trip(outs, case, path):
 @pytest.mark.parametrize("case,path", _params())
 def test_code_sets(outs, case, path):
     """complete, within the limits, a code for every symbol that occurs and for no other, the smallest HLIT / HDIST / HCLEN"""
-    for b in _data_blocks(outs.parsed(case.name, path)):
+    for b in dp.data_blocks(outs.parsed(case.name, path)):
         if b.btype != dp.DYNAMIC:
             continue
         assert b.states == {"cl": "complete", "lit": "complete", "dist": "complete"}
@@ -145,7 +127,7 @@ def test_code_sets(outs, case, path):
 def test_optimal_below_the_limit(outs, case, path):
     """where the limit cannot bind, sum f * len over the block's own histogram is the Huffman optimum, exactly"""
     checked = 0
-    for b in _data_blocks(outs.parsed(case.name, path)):
+    for b in dp.data_blocks(outs.parsed(case.name, path)):
         if b.btype != dp.DYNAMIC:
             continue
         for which, (hist, lens) in _sets(b).items():
@@ -158,7 +140,7 @@ def test_optimal_below_the_limit(outs, case, path):
 
 def _deep_block(p, case, which):
     """the block the case was built for: the one whose histogram is deepest"""
-    blocks = [b for b in _data_blocks(p) if b.btype == dp.DYNAMIC]
+    blocks = [b for b in dp.data_blocks(p) if b.btype == dp.DYNAMIC]
     assert blocks, "no dynamic block"
     return max(blocks, key=lambda b: hm.min_max_depth(_sets(b)[which][0]))
 
@@ -199,7 +181,7 @@ def test_cost_above_the_limit(outs, case, which, path):
 @pytest.mark.parametrize("case,which,path", _EXACT)
 def test_cost_at_the_limit(outs, case, which, path):
     """depth exactly at the limit: nothing may be halved, the cost is the unrestricted optimum"""
-    blocks = _data_blocks(outs.parsed(case.name, path))
+    blocks = dp.data_blocks(outs.parsed(case.name, path))
     assert len(blocks) == 1 and blocks[0].btype == dp.DYNAMIC
     hist, lens = _sets(blocks[0])[which]
     assert hist == (case.hist if which == "lit" else case.cl_hist)
@@ -220,7 +202,7 @@ def test_block_type_choice(outs, case, path):
     match (Z_HUFFMAN_ONLY, fixed_tie) and an upper bound of the matcher's tokens' size elsewhere."""
     comp = outs.comp[case.name, path]
     p = outs.parsed(case.name, path)
-    data_blocks = _data_blocks(p)
+    data_blocks = dp.data_blocks(p)
     for b in data_blocks:
         size = (b.end - b.start + 7) // 8
         stored = hm.stored_lenb(b.nbytes)
@@ -258,16 +240,16 @@ def test_block_type_choice(outs, case, path):
 
 @pytest.mark.parametrize("path", PATHS)
 def test_mixed_has_every_block_type(outs, path):
-    types = {b.btype for b in _data_blocks(outs.parsed("mixed/default", path))}
+    types = {b.btype for b in dp.data_blocks(outs.parsed("mixed/default", path))}
     assert dp.STORED in types and dp.DYNAMIC in types
-    assert {b.btype for b in _data_blocks(outs.parsed("fixed_tie/22", path))} == {dp.STATIC}
+    assert {b.btype for b in dp.data_blocks(outs.parsed("fixed_tie/22", path))} == {dp.STATIC}
 
 
 @pytest.mark.parametrize("path", PATHS)
 def test_crafted_edges_are_reached(outs, path):
     """the matcher and the front ends did produce what each edge case was built for"""
     def only(name):
-        blocks = [b for b in _data_blocks(outs.parsed(name, path)) if b.btype == dp.DYNAMIC]
+        blocks = [b for b in dp.data_blocks(outs.parsed(name, path)) if b.btype == dp.DYNAMIC]
         assert len(blocks) == 1, name
         return blocks[0]
     b = only("dist_one")                                       # one distance code: a second one is forced, one bit each
@@ -298,7 +280,7 @@ def test_blocks_differ(outs, path):
     """every block's lengths are non-zero on its own alphabet only: a block's histogram is the difference of two cumulative
     snapshots, and the first block of a segment has nothing to subtract"""
     case = ec.by_name("blocks_differ")
-    blocks = _data_blocks(outs.parsed(case.name, path))
+    blocks = dp.data_blocks(outs.parsed(case.name, path))
     assert [(b.out_start, b.out_end) for b in blocks] == [(lo, hi) for lo, hi, _, _ in case.extra["alphabets"]]
     for b, (lo, hi, a0, b0) in zip(blocks, case.extra["alphabets"]):
         assert b.btype == dp.DYNAMIC
