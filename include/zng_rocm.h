@@ -1023,6 +1023,81 @@ int    zng_rocm_bgzf_read_last_rounds(void);
 int    zng_rocm_bgzf_voffset(const zng_rocm_gzip_member *members, size_t nmembers, uint64_t uoff, uint64_t *voff);
 int    zng_rocm_bgzf_uoffset(const zng_rocm_gzip_member *members, size_t nmembers, uint64_t voff, uint64_t *uoff);
 
+/* ---- gzip header FIELDS of device-resident members: set on write, get on read -------------------------------------------
+ * deflateSetHeader and inflateGetHeader (zlib-ng.h.in:127-141 the zng_gz_header, :796-816, :1020-1055): what deflate.c:922-1023
+ * writes in front of a member -- FTEXT, MTIME, OS, the FEXTRA subfields, FNAME, FCOMMENT, the FHCRC -- and inflate.c:556-700 reads
+ * back, for the members zng_rocm_compress_members_dev writes and zng_rocm_gunzip_members_dev / zng_rocm_bgzf_index_dev find.
+ *
+ * zng_rocm_gzip_header: one member's fields; everything it points to is HOST memory and is copied before a call returns.
+ *   FLG = text ? 1 : 0 + hcrc ? 2 : 0 + (extra != NULL) ? 4 : 0 + (name != NULL) ? 8 : 0 + (comment != NULL) ? 16 : 0 (deflate.c:927-932)
+ *   then MTIME little endian, XFL by level and strategy as the canonical header (deflate.c:939-940), os & 0xff, XLEN and the extra
+ *   bytes, name and its 0, comment and its 0, and with hcrc the low 16 bits of the CRC-32 of everything in front (deflate.c:1005-1016).
+ * Refused: extra_len above 65535 (the reference writes extra_len & 0xffff as XLEN and still copies extra_len bytes, deflate.c:
+ * 947-949: a header no reader follows); extra == NULL with extra_len != 0; a name or a comment of more than 65535 bytes without
+ * its terminator (the library's own limit, zlib has none: a header is at most 196621 bytes); reserved != 0.
+ * zng_rocm_gzip_header_bytes: the header's length without rendering it; NULL: the canonical 10 bytes; 0 for a refused header.
+ * zng_rocm_gzip_header_write: the header into buf[0, cap) on the HOST, no device needed (works before zng_rocm_init and without a
+ *   GPU).  level -1 or 0..9 and strategy 0..4 give XFL; NULL: the canonical header.  Returns the bytes written, 0 for a refused
+ *   header, level or strategy or when cap is too small (nothing written).
+ *
+ * zng_rocm_compress_streams2_header_dev / zng_rocm_compress_members_header_dev: zng_rocm_compress_streams2_window_dev(2, ...) /
+ * zng_rocm_compress_members_window_dev(2, ...) with `heads`, a HOST array of njobs headers (copied internally, as jobs): member i
+ * is the rendered heads[i], then exactly the deflate data those calls write for the same job list, level, strategy and window,
+ * then CRC-32 and ISIZE.  gzip only.  heads == NULL: exactly those calls, bytes, results and refusals.  Per-job buffers need
+ * out_cap >= zng_rocm_compress_streams2_bound(in_len, 2) - 10 + zng_rocm_gzip_header_bytes(&heads[i]) (less: -5, nothing launched;
+ * a bound that does not fit 32 bits: ZNG_ROCM_EINVAL).  A refused header is ZNG_ROCM_EINVAL for the call with nothing launched or
+ * written.  Result words, d_offsets, d_checks, rounds and the dst_cap rule -- no byte at or behind d_dst + dst_cap is written, a
+ * cut inside a header included -- are those of the calls above, and the calls stay asynchronous: the host renders every header
+ * into one pinned blob that goes up with the job table. */
+typedef struct zng_rocm_gzip_header {   /* zng_gz_header for one member; everything it points to is HOST memory */
+    uint32_t time, os, text, hcrc;      /* os written as os & 0xff; text / hcrc: non-zero = set */
+    const uint8_t *extra;               /* NULL: no FEXTRA; non-NULL with extra_len 0: an empty field (XLEN 0) */
+    const char    *name;                /* zero-terminated; NULL: no FNAME */
+    const char    *comment;             /* zero-terminated; NULL: no FCOMMENT */
+    uint32_t extra_len, reserved;       /* <= 65535; 0 */
+} zng_rocm_gzip_header;
+size_t zng_rocm_gzip_header_bytes(const zng_rocm_gzip_header *h);
+size_t zng_rocm_gzip_header_write(const zng_rocm_gzip_header *h, int level, int strategy, uint8_t *buf, size_t cap);
+int    zng_rocm_compress_streams2_header_dev(int level, int strategy, int window_bits, const zng_rocm_stream_job *jobs,
+                                             const zng_rocm_gzip_header *heads, size_t njobs, size_t round_bytes,
+                                             uint32_t *d_results, void *stream);
+int    zng_rocm_compress_members_header_dev(int level, int strategy, int window_bits, const zng_rocm_stream_job *jobs,
+                                            const zng_rocm_gzip_header *heads, size_t njobs, uint8_t *d_dst, size_t dst_cap,
+                                            size_t round_bytes, uint64_t *d_offsets, uint32_t *d_checks, void *stream);
+/* The read side (inflateGetHeader, inflate.c:556-700).  status, msg and header_len of a row are what
+ * zng_rocm_wrapper_parse(2, member, ...) says about the same bytes -- one text of rules (a bad FHCRC: -3, "header crc mismatch");
+ * the other fields are filled for status 0 and are 0 otherwise.
+ * zng_rocm_gzip_header_parse: one member in HOST memory, no device needed.  Returns the row's status, or ZNG_ROCM_EINVAL for a
+ *   null row or a null src with a length (the row, if any, then holds status ZNG_ROCM_EINVAL and zeros); text_off is 0.
+ * zng_rocm_gzip_headers_dev: the headers of `nmembers` members of the device-resident file d_src[0, src_len).
+ *   members     HOST array; only src_off and src_len are read: the table zng_rocm_gunzip_members_dev or zng_rocm_bgzf_index_dev
+ *               hands back, or one built from the d_offsets of the writers above
+ *   rows        HOST array of nmembers
+ *   text        HOST buffer of text_cap bytes (NULL with text_cap 0): for the members with status 0, in member order, the extra
+ *               bytes, the name and a 0, the comment and a 0 -- the fields the member has; rows[i].text_off is where member i's
+ *               begin (a running sum, also for members that put nothing there).  *text_need, always set, is the total; with
+ *               text_cap < *text_need the rows are delivered, `text` is untouched and the call returns -5.
+ *   A header is followed as far as its member reaches: the 4 KiB the header kernel of zng_rocm_gunzip_members_dev is shown are no
+ *   limit here.  One wavefront per member walks the rules, the FHCRC goes through the many-message checksum pass, one workgroup
+ *   scans the lengths, one workgroup per member gathers its fields.  Synchronous, with at most two device-to-host copies (the
+ *   rows, the text).  A member that does not lie inside src_len, more than 2^31 - 1 members, or a null pointer with a non-zero
+ *   count is ZNG_ROCM_EINVAL with nothing launched or written (but *text_need = 0); nmembers == 0 returns 0; before
+ *   zng_rocm_init an accepted call returns ZNG_ROCM_ENODEV.  The header kernel and the checksum pass fetch aligned 16-byte
+ *   lines: up to 15 bytes on either side of a member inside the same line are read (never used). */
+typedef struct zng_rocm_gzip_header_row {
+    int32_t     status;                       /* 0 / -3 / -5: zng_rocm_wrapper_parse(2, member)'s return for the same bytes */
+    uint32_t    flg;                          /* the FLG byte (status 0) */
+    const char *msg;                          /* that call's text (static storage), NULL unless -3 */
+    uint64_t    header_len;
+    uint32_t    time, xflags, os, text, hcrc, extra_len;
+    uint64_t    name_len, comment_len;        /* without the terminator */
+    uint64_t    extra_off, name_off, comment_off;   /* in d_src, counted from the FILE's first byte; 0 when the field is absent */
+    uint64_t    text_off;                     /* where this member's fields begin in `text` */
+} zng_rocm_gzip_header_row;
+int    zng_rocm_gzip_header_parse(const uint8_t *src, size_t src_len, zng_rocm_gzip_header_row *row);
+int    zng_rocm_gzip_headers_dev(const uint8_t *d_src, size_t src_len, const zng_rocm_gzip_member *members, size_t nmembers,
+                                 zng_rocm_gzip_header_row *rows, uint8_t *text, size_t text_cap, size_t *text_need, void *stream);
+
 /* ---- random access into ONE plain stream: raw deflate, zlib or gzip (what zran.c and indexed_gzip do on a CPU) -------------
  * A BGZF file offers random access by construction; every other stream -- a plain .gz, a zlib stream, raw deflate, what
  * zng_rocm_compress2_dev or zng_rocm_deflate_dev write -- needs an INDEX: access points {in_bit, out_off, window_len}, each a

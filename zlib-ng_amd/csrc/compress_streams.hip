@@ -23,6 +23,11 @@
 // zng_rocm_compress_streams2_dict_dev / zng_rocm_compress_members_dict_dev are the same calls with one shared preset dictionary
 // (dict.hip) as every stream's history: the rows engine runs its dictionary form (lz_rows_dict_kernel), and the zlib member
 // begins with the 6-byte FDICT header -- CMF FLG, the DICTID -- instead of the 2-byte one.
+//
+// zng_rocm_compress_streams2_header_dev / zng_rocm_compress_members_header_dev are the gzip calls with deflateSetHeader's fields
+// per member (gzip_header_plan.h): the host renders every header into one pinned blob that goes up behind the job table in the
+// same copy, the scan adds each job's own header length, and the frame kernel moves the header from the blob (bgzf_copy.h) instead
+// of computing its 10 bytes.  The kernels are templates over that: the calls without headers run the instructions they always had.
 #include "checksum_args.h"
 #include "context.h"
 
@@ -32,16 +37,20 @@
 #include "deflate_dev.h"
 #include "deflate_window_plan.h"
 #include "dict_dev.h"
+#include "gzip_header_plan.h"
 
 #include <mutex>
+#include <vector>
 
 namespace zr {
 
 struct CsJob {                          // one row per job of the whole call
     const uint8_t *in;
     uint8_t       *out;                 // streams2: the member's buffer
-    uint32_t       in_len, out_cap, flags, pad;
+    uint32_t       in_len, out_cap, flags;
+    uint32_t       head_len;            // the *_header_dev calls: bytes of the member's rendered header (else 0, not read)
     unsigned long long blk0;            // level 0: stored blocks of the jobs in front of this one
+    unsigned long long head_off;        // ... and where it begins in CsRound::blob
 };
 
 struct CsRound {                        // the arguments the kernels of a round share
@@ -59,12 +68,19 @@ struct CsRound {                        // the arguments the kernels of a round 
     uint32_t      *results;             // streams2: d_results
     uint32_t       dict, dictid;        // 1: the calls with a shared preset dictionary, whose zlib header carries FDICT and this DICTID
     int            window_bits;         // the stream's w_bits (deflate_window_plan.h): 15 but for the *_window_dev calls
+    const uint8_t *blob;                // the *_header_dev calls: every member's rendered header, else null
 };
 
 // bytes of the member's header, and byte k of it
 __device__ __forceinline__ uint32_t cs_round_head(const CsRound &r) { return r.dict ? cs_dict_head_bytes(r.format) : cs_head_bytes(r.format); }
 __device__ __forceinline__ uint8_t cs_round_header_byte(const CsRound &r, uint32_t k) {
     return r.dict ? cs_dict_header_byte(r.level, r.strategy, r.dictid, k) : cs_header_byte(r.format, r.level, r.strategy, k, r.window_bits);
+}
+
+// kHeads (the *_header_dev calls): the job's own header, whose bytes are in the blob
+template <bool kHeads>
+__device__ __forceinline__ uint32_t cs_job_head(const CsRound &r, const CsJob &j) {
+    return kHeads ? j.head_len : cs_round_head(r);
 }
 
 __device__ __forceinline__ uint32_t cs_check_of(const CsRound &r, uint32_t i) { return r.check2[2 * i + (r.format == 2 ? 1 : 0)]; }
@@ -96,16 +112,18 @@ void cs_check_args_kernel(CsRound r, const DeviceTables *__restrict__ tabs, Stre
     fill_check_descriptor(j.in, j.in_len, tabs, r.format == 2 ? 0 : 1, r.format == 2 ? 1 : 0, sa + i, fa + i);
 }
 
+template <bool kHeads>
 __global__ __launch_bounds__(1024)
 void cs_scan_kernel(CsRound r, unsigned long long *__restrict__ file_off) {
     __shared__ unsigned long long wave_sum[16];
     __shared__ unsigned long long carry;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const uint32_t wrap = cs_round_head(r) + cs_tail_bytes(r.format);
+    const uint32_t tail = cs_tail_bytes(r.format);
     if (!r.members) {                                    // every member in its own buffer: nothing to place
         for (uint32_t i = (uint32_t)t; i < r.nj; i += 1024u) {
             const unsigned long long g = r.first + i;
-            r.results[2 * g] = (uint32_t)(cs_stream_bytes(r, i, r.jobs[g]) + wrap);
+            const CsJob j = r.jobs[g];
+            r.results[2 * g] = (uint32_t)(cs_stream_bytes(r, i, j) + cs_job_head<kHeads>(r, j) + tail);
             r.results[2 * g + 1] = cs_check_of(r, i);
         }
         return;
@@ -115,7 +133,11 @@ void cs_scan_kernel(CsRound r, unsigned long long *__restrict__ file_off) {
     for (uint32_t base = 0; base < r.nj; base += 1024u) {
         const uint32_t i = base + (uint32_t)t;
         const bool live = i < r.nj;
-        const unsigned long long v = live ? cs_stream_bytes(r, i, r.jobs[r.first + i]) + wrap : 0ull;
+        unsigned long long v = 0ull;
+        if (live) {
+            const CsJob j = r.jobs[r.first + i];
+            v = cs_stream_bytes(r, i, j) + cs_job_head<kHeads>(r, j) + tail;
+        }
         unsigned long long incl = v;
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
@@ -146,11 +168,12 @@ __device__ __forceinline__ void cs_put(const CsPlace &p, unsigned long long at, 
 
 // Work item w < nj is member w of the round; work item nj + k is block k: of the rows engine (blk / seg_len / in_stream), or at
 // level 0 stored block jobs[first].blk0 + k of the call.
+template <bool kHeads>
 __global__ __launch_bounds__(256)
 void cs_frame_kernel(CsRound r, const BlkJob *__restrict__ blk, const uint32_t *__restrict__ seg_len,
                      const unsigned long long *__restrict__ in_stream, unsigned long long nblk) {
     const int t = threadIdx.x;
-    const uint32_t head = cs_round_head(r), tail = cs_tail_bytes(r.format);
+    const uint32_t tail = cs_tail_bytes(r.format);
     const unsigned long long items = (unsigned long long)r.nj + nblk;
     for (unsigned long long w = blockIdx.x; w < items; w += gridDim.x) {
         if (w < r.nj) {
@@ -159,7 +182,9 @@ void cs_frame_kernel(CsRound r, const BlkJob *__restrict__ blk, const uint32_t *
             const CsJob j = r.jobs[g];
             const CsPlace p = cs_place(r, g, j);
             const unsigned long long body = cs_stream_bytes(r, i, j);
-            if (t < (int)head) cs_put(p, p.at + t, cs_round_header_byte(r, (uint32_t)t));
+            const uint32_t head = cs_job_head<kHeads>(r, j);
+            if (kHeads) bgzf_copy(p.base, p.at, p.cap, r.blob + j.head_off, head, t);       // up to kGhMaxBytes: a loop
+            if (!kHeads && t < (int)head) cs_put(p, p.at + t, cs_round_header_byte(r, (uint32_t)t));
             else if (t >= 32 && t < 32 + (int)tail)
                 cs_put(p, p.at + head + body + (t - 32), cs_trailer_byte(r.format, (uint32_t)t - 32u, cs_check_of(r, i), j.in_len));
             else if (r.level == 0 && cs_stored_marker(j.flags) && t >= 64 && t < 64 + (int)kCsStoredHead)
@@ -168,8 +193,9 @@ void cs_frame_kernel(CsRound r, const BlkJob *__restrict__ blk, const uint32_t *
             const unsigned long long k = w - r.nj;
             const uint32_t s = blk[k].stream & 0x7fffffffu;
             const unsigned long long g = r.first + s;
-            const CsPlace p = cs_place(r, g, r.jobs[g]);
-            bgzf_copy(p.base, p.at + head + in_stream[k], p.cap, blk[k].out, seg_len[k], t);
+            const CsJob j = r.jobs[g];
+            const CsPlace p = cs_place(r, g, j);
+            bgzf_copy(p.base, p.at + cs_job_head<kHeads>(r, j) + in_stream[k], p.cap, blk[k].out, seg_len[k], t);
         } else {
             // the job that holds this stored block: the last one of the round whose blk0 is not behind it
             const unsigned long long b_call = r.jobs[r.first].blk0 + (w - r.nj);
@@ -185,7 +211,7 @@ void cs_frame_kernel(CsRound r, const BlkJob *__restrict__ blk, const uint32_t *
             const unsigned long long b = b_call - j.blk0;
             const uint32_t len = cs_stored_block_len(j.in_len, b);
             const bool final_block = b + 1u == cs_stored_blocks(j.in_len) && !(j.flags & ZNG_ROCM_BLOCK_NOT_FINAL);
-            const unsigned long long at = p.at + head + b * (kCsMaxStored + kCsStoredHead);
+            const unsigned long long at = p.at + cs_job_head<kHeads>(r, j) + b * (kCsMaxStored + kCsStoredHead);
             if (t < (int)kCsStoredHead) cs_put(p, at + t, cs_stored_byte((uint32_t)t, len, final_block));
             bgzf_copy(p.base, at + kCsStoredHead, p.cap, j.in + b * kCsMaxStored, len, t);
         }
@@ -195,11 +221,13 @@ void cs_frame_kernel(CsRound r, const BlkJob *__restrict__ blk, const uint32_t *
 static thread_local int t_cs_rounds = 0;
 
 // with_dict: the calls with a shared preset dictionary (`dict` is every stream's history), else dict is null.  window_bits: as
-// the caller gave it (deflate_window_plan.h); the calls without a window say 15
+// the caller gave it (deflate_window_plan.h); the calls without a window say 15.  heads: the *_header_dev calls (format 2), one
+// header per job, else null
 static int compress_streams_run(const char *who, bool members, int format, int level, int strategy, const zng_rocm_stream_job *jobs,
                                 size_t njobs, uint8_t *d_dst, size_t dst_cap, size_t round_bytes, uint64_t *d_offsets,
                                 uint32_t *d_checks, uint32_t *d_results, void *stream, bool with_dict = false,
-                                const zng_rocm_dict *dict = nullptr, int window_bits = kWinBitsMax) {
+                                const zng_rocm_dict *dict = nullptr, int window_bits = kWinBitsMax,
+                                const zng_rocm_gzip_header *heads = nullptr) {
     t_cs_rounds = 0;
     if (cs_format_ok(format) && win_check(format, window_bits)) {
         set_error("%s: window_bits %d is outside 9..15 (8: the zlib format alone, deflate.c:319)", who, window_bits);
@@ -229,6 +257,26 @@ static int compress_streams_run(const char *who, bool members, int format, int l
                       "bound that does not fit 32 bits", who, (unsigned long long)bad);
         return rc;
     }
+    // the *_header_dev calls: every header's lengths, the first refusal in job order
+    std::vector<GhLens> lens(heads ? njobs : 0);
+    size_t blob_bytes = 0;
+    for (size_t i = 0; heads && i < njobs; ++i) {
+        if (gh_check(&heads[i], &lens[i])) {
+            set_error("%s: header %zu: extra_len above 65535 or without extra, a name or comment of more than 65535 bytes, or reserved "
+                      "not 0", who, i);
+            return ZNG_ROCM_EINVAL;
+        }
+        const uint64_t bound = cs_bound(jobs[i].in_len, format) - cs_head_bytes(format) + gh_bytes(&heads[i], lens[i]);
+        if (!members && bound > 0xffffffffull) {
+            set_error("%s: job %zu: a bound that does not fit 32 bits", who, i);
+            return ZNG_ROCM_EINVAL;
+        }
+        if (!members && jobs[i].out_cap < bound) {
+            set_error("%s: job %zu: out_cap below zng_rocm_compress_streams2_bound() - 10 + zng_rocm_gzip_header_bytes()", who, i);
+            return kCsBufError;
+        }
+        blob_bytes += gh_bytes(&heads[i], lens[i]);
+    }
     if (!njobs) return ZNG_ROCM_OK;
     if (!ctx()) {
         set_error("zng_rocm_init() has not succeeded");
@@ -254,14 +302,16 @@ static int compress_streams_run(const char *who, bool members, int format, int l
     if (!ws) return ZNG_ROCM_ENOMEM;
     std::lock_guard<std::mutex> use(ws->mu);
 
-    // device: file offset | job table | {Adler-32, CRC-32} per job of a round (every part 16-byte aligned)
+    // device: file offset | job table | the *_header_dev calls: the rendered headers | {Adler-32, CRC-32} per job of a round
+    // (every part 16-byte aligned); pinned: job table | headers, as they stand on the device: one copy takes both up
     auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    const size_t o_jobs = 16, o_chk = o_jobs + up16(njobs * sizeof(CsJob)), total = o_chk + np_max * 2 * sizeof(uint32_t);
+    const size_t tab_bytes = njobs * sizeof(CsJob), o_jobs = 16, o_blob = o_jobs + up16(tab_bytes), o_chk = o_blob + up16(blob_bytes);
+    const size_t total = o_chk + np_max * 2 * sizeof(uint32_t), up_bytes = heads ? up16(tab_bytes) + blob_bytes : tab_bytes;
     uint8_t *d = nullptr, *d_msg = nullptr;
     Partial *d_part = nullptr;
     CsJob *h_jobs = nullptr;
     if ((rc = scratch_reserve(ws, kScrCompressStreams, total, false, (void **)&d))) return rc;
-    if ((rc = scratch_reserve(ws, kScrCompressStreamsHost, njobs * sizeof(CsJob), true, (void **)&h_jobs))) return rc;
+    if ((rc = scratch_reserve(ws, kScrCompressStreamsHost, up_bytes, true, (void **)&h_jobs))) return rc;
     if ((rc = scratch_reserve(ws, kScrCheckMessages, np_max * (sizeof(StreamArgs) + sizeof(FinalArgs)), false, (void **)&d_msg))) return rc;
     if ((rc = scratch_reserve(ws, kScrCheckPartials, np_max * sizeof(Partial), false, (void **)&d_part))) return rc;
     unsigned long long *d_file_off = reinterpret_cast<unsigned long long *>(d);
@@ -278,11 +328,19 @@ static int compress_streams_run(const char *who, bool members, int format, int l
         h_jobs[i].in_len = jobs[i].in_len;
         h_jobs[i].out_cap = jobs[i].out_cap;
         h_jobs[i].flags = jobs[i].flags;
-        h_jobs[i].pad = 0;
+        h_jobs[i].head_len = 0;
         h_jobs[i].blk0 = blk0;
+        h_jobs[i].head_off = 0;
         blk0 += cs_stored_blocks(jobs[i].in_len);
     }
-    ZR_HIP(hipMemcpyAsync(d_jobs, h_jobs, njobs * sizeof(CsJob), hipMemcpyHostToDevice, st));
+    uint8_t *h_blob = reinterpret_cast<uint8_t *>(h_jobs) + up16(tab_bytes);
+    for (size_t i = 0, at = 0; heads && i < njobs; ++i) {
+        gh_render(&heads[i], lens[i], level, strategy, h_blob + at);
+        h_jobs[i].head_len = gh_bytes(&heads[i], lens[i]);
+        h_jobs[i].head_off = at;
+        at += h_jobs[i].head_len;
+    }
+    ZR_HIP(hipMemcpyAsync(d_jobs, h_jobs, up_bytes, hipMemcpyHostToDevice, st));
     // the engine records the event that guards the pinned tables behind its own copy, later on this stream; without it, here
     if (level == 0 && (rc = host_tables_release(ws, st))) return rc;
     if (members) ZR_HIP(hipMemsetAsync(d_file_off, 0, sizeof(unsigned long long), st));
@@ -309,6 +367,7 @@ static int compress_streams_run(const char *who, bool members, int format, int l
         r.dict = with_dict ? 1u : 0u;
         r.dictid = with_dict ? dict->id : 0u;
         r.window_bits = window_bits;
+        r.blob = heads ? d + o_blob : nullptr;
         hipLaunchKernelGGL(cs_check_args_kernel, dim3((r.nj + 255u) / 256u), dim3(256), 0, st, r, ctx()->tables, d_sa, d_fa);
         ZR_HIP(hipGetLastError());
         if ((rc = launch_checksum_batch_device(format != 2, format == 2, d_sa, d_fa, d_part, r.nj, d_chk, st))) return rc;
@@ -326,11 +385,15 @@ static int compress_streams_run(const char *who, bool members, int format, int l
             r.sizes = blocks.sizes;
             nblk = blocks.nblk;
         }
-        hipLaunchKernelGGL(cs_scan_kernel, dim3(1), dim3(1024), 0, st, r, d_file_off);
+        if (heads) hipLaunchKernelGGL(cs_scan_kernel<true>, dim3(1), dim3(1024), 0, st, r, d_file_off);
+        else hipLaunchKernelGGL(cs_scan_kernel<false>, dim3(1), dim3(1024), 0, st, r, d_file_off);
         ZR_HIP(hipGetLastError());
         const unsigned long long items = (unsigned long long)r.nj + nblk;
         const unsigned grid = (unsigned)(items < (1u << 20) ? items : (1u << 20));
-        ZR_LAUNCH_TRACED(cs_frame_kernel, dim3(grid), dim3(256), st, r, blocks.blk, blocks.seg_len, blocks.in_stream, nblk);
+        if (heads)
+            ZR_LAUNCH_TRACED(cs_frame_kernel<true>, dim3(grid), dim3(256), st, r, blocks.blk, blocks.seg_len, blocks.in_stream, nblk);
+        else
+            ZR_LAUNCH_TRACED(cs_frame_kernel<false>, dim3(grid), dim3(256), st, r, blocks.blk, blocks.seg_len, blocks.in_stream, nblk);
         ZR_HIP(hipGetLastError());
         first = last;
     }
@@ -373,6 +436,21 @@ int zng_rocm_compress_members_window_dev(int format, int level, int strategy, in
                                          uint32_t *d_checks, void *stream) {
     return compress_streams_run("zng_rocm_compress_members_window_dev", true, format, level, strategy, jobs, njobs, d_dst, dst_cap,
                                 round_bytes, d_offsets, d_checks, nullptr, stream, false, nullptr, window_bits);
+}
+
+// The gzip calls above with deflateSetHeader's fields per member (deflate.c:922-1023; gzip_header_plan.h); heads == NULL: those calls
+int zng_rocm_compress_streams2_header_dev(int level, int strategy, int window_bits, const zng_rocm_stream_job *jobs,
+                                          const zng_rocm_gzip_header *heads, size_t njobs, size_t round_bytes, uint32_t *d_results,
+                                          void *stream) {
+    return compress_streams_run("zng_rocm_compress_streams2_header_dev", false, 2, level, strategy, jobs, njobs, nullptr, 0, round_bytes,
+                                nullptr, nullptr, d_results, stream, false, nullptr, window_bits, heads);
+}
+
+int zng_rocm_compress_members_header_dev(int level, int strategy, int window_bits, const zng_rocm_stream_job *jobs,
+                                         const zng_rocm_gzip_header *heads, size_t njobs, uint8_t *d_dst, size_t dst_cap,
+                                         size_t round_bytes, uint64_t *d_offsets, uint32_t *d_checks, void *stream) {
+    return compress_streams_run("zng_rocm_compress_members_header_dev", true, 2, level, strategy, jobs, njobs, d_dst, dst_cap,
+                                round_bytes, d_offsets, d_checks, nullptr, stream, false, nullptr, window_bits, heads);
 }
 
 size_t zng_rocm_compress_streams2_dict_bound(size_t source_len, int format) { return (size_t)cs_dict_bound(source_len, format); }

@@ -95,10 +95,14 @@ enum ScratchSlot {
     kScrIndexRead,          // device: the engine's results | jobs | span table | slices | the edge spans' slots
                             //   (zng_rocm_inflate_index_read_dev); the window moves of zng_rocm_inflate_index_build_dev
     kScrIndexReadHost,      // pinned: jobs | span table | slices on their way up | the results on their way down
-    kScrCompressStreams,    // device: file offset | job table of the whole call | a round's check values
-                            //   (zng_rocm_compress_streams2_dev, zng_rocm_compress_members_dev)
-    kScrCompressStreamsHost, // pinned: the job table on its way up
+    kScrCompressStreams,    // device: file offset | job table of the whole call | the rendered gzip headers of the *_header_dev
+                            //   calls | a round's check values (zng_rocm_compress_streams2_dev, zng_rocm_compress_members_dev)
+    kScrCompressStreamsHost, // pinned: the job table and the headers on their way up
     kScrSizes,              // device: the sizing rows of zng_rocm_uncompress_packed_dev (4 words per job)
+    kScrGzipHeader,         // device: rows | text bytes needed | header jobs | descriptors, partials and CRC-32 of the FHCRC pass
+                            //   (zng_rocm_gzip_headers_dev)
+    kScrGzipHeaderHost,     // pinned: the header jobs on their way up | the rows on their way down
+    kScrGzipHeaderText,     // device: the gathered fields
     kScrCount
 };
 

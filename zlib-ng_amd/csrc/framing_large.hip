@@ -67,44 +67,6 @@ struct CutArgs {                                         // up to kCutJobs messa
     uint32_t n, base;                                    // messages in this launch; index of the first one in the call
 };
 
-// the member's bytes as a wavefront reaches them: every lane calls with the same arguments
-struct WaveBytes {
-    const uint8_t *src;
-    __device__ uint32_t byte(uint64_t pos) const { return src[pos]; }
-    __device__ uint64_t find_zero(uint64_t from, uint64_t n) const {
-        const uint32_t lane = threadIdx.x & 63u;
-        const uintptr_t base = (uintptr_t)src, lo = base + from, hi = base + n;
-        // aligned 16-byte lines: the first and the last reach up to 15 bytes outside [lo, hi) inside their own line (read,
-        // never used -- as the checksum kernels read around an unaligned message; include/zng_rocm.h says so to callers)
-        for (uintptr_t a = lo & ~(uintptr_t)15; a < hi; a += 4u * 64u * 16u) {
-            uint4 v[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const uintptr_t mine = a + ((uintptr_t)u * 64u + lane) * 16u;
-                v[u] = mine < hi ? *reinterpret_cast<const uint4 *>(mine) : make_uint4(~0u, ~0u, ~0u, ~0u);
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const uintptr_t mine = a + ((uintptr_t)u * 64u + lane) * 16u;
-                const uint32_t w[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-                uint32_t zmask = 0;                      // bit k: byte k of my line is zero and belongs to [lo, hi)
-#pragma unroll
-                for (int k = 0; k < 16; ++k) {
-                    const uintptr_t at = mine + k;
-                    if (((w[k >> 2] >> (8 * (k & 3))) & 0xffu) == 0u && at >= lo && at < hi) zmask |= 1u << k;
-                }
-                const unsigned long long vote = __ballot(zmask != 0u);
-                if (vote) {
-                    const int first = __ffsll((long long)vote) - 1;
-                    const uint32_t m = (uint32_t)__shfl((int)zmask, first, 64);
-                    return (uint64_t)(a + ((uintptr_t)u * 64u + first) * 16u + (uint32_t)(__ffs((int)m) - 1) - base);
-                }
-            }
-        }
-        return n;
-    }
-};
-
 // one wavefront per member
 __global__ __launch_bounds__(64)
 void large_header_kernel(const HeadJob *__restrict__ jobs, uint32_t njobs, int format, const DeviceTables *__restrict__ tabs,
@@ -227,23 +189,6 @@ void large_trailer_kernel(const TrailJob *__restrict__ jobs, const uint32_t *__r
 }
 
 namespace {
-
-// CRC-32 of a gzip header on the host, without the device context (zng_rocm_wrapper_parse works before zng_rocm_init)
-uint32_t host_crc32(const uint8_t *p, size_t n) {
-    static const struct Table {
-        uint32_t t[256];
-        Table() {
-            for (uint32_t i = 0; i < 256; ++i) {
-                uint32_t c = i;
-                for (int k = 0; k < 8; ++k) c = (c >> 1) ^ (kCrcPoly & (0u - (c & 1u)));
-                t[i] = c;
-            }
-        }
-    } tab;
-    uint32_t c = 0xffffffffu;
-    for (size_t i = 0; i < n; ++i) c = tab.t[(c ^ p[i]) & 0xffu] ^ (c >> 8);
-    return ~c;
-}
 
 size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
@@ -592,7 +537,7 @@ int zng_rocm_wrapper_parse(int format, const uint8_t *src, size_t src_len, zng_r
     if (msg) *msg = nullptr;
     if (format < 0 || format > 2 || (!src && src_len) || !info) return ZNG_ROCM_EINVAL;
     WrapperHead h = wrapper_parse_rules(format, HostBytes{src}, src_len);
-    if (h.status == 0 && h.hcrc && (host_crc32(src, (size_t)h.header_len - 2) & 0xffffu) != h.hcrc_stored) {
+    if (h.status == 0 && h.hcrc && (wrapper_host_crc32(src, (size_t)h.header_len - 2) & 0xffffu) != h.hcrc_stored) {
         h.status = -3;
         h.msg = kWrapHeaderCrc;
     }

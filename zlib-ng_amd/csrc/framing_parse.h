@@ -15,6 +15,7 @@
 //   wrapper_header_byte, wrapper_trailer_byte   the canonical header and trailer of the writers, by format, level and strategy
 //   wrapper_dict_head_bytes, wrapper_dict_header_byte   the 6-byte zlib header with FDICT and the DICTID
 //   wrapper_le32, wrapper_be32, wrapper_head_bytes, wrapper_tail_bytes   the 32-bit fields and the canonical sizes
+//   wrapper_host_crc32       the FHCRC's CRC-32 for the host-only callers
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -199,7 +200,25 @@ struct HostBytes {
     }
 };
 
-// What a caller that holds the whole member and no dictionary makes of its header.  msg (InflateMsg): kMsgNone -- the deflate
+// CRC-32 of a gzip header on the host, without the device context (zng_rocm_wrapper_parse and the header writer of
+// gzip_header_plan.h work before zng_rocm_init)
+inline uint32_t wrapper_host_crc32(const uint8_t *p, size_t n) {
+    static const struct Table {
+        uint32_t t[256];
+        Table() {
+            for (uint32_t i = 0; i < 256; ++i) {
+                uint32_t c = i;
+                for (int k = 0; k < 8; ++k) c = (c >> 1) ^ (kCrcPoly & (0u - (c & 1u)));
+                t[i] = c;
+            }
+        }
+    } tab;
+    uint32_t c = 0xffffffffu;
+    for (size_t i = 0; i < n; ++i) c = tab.t[(c ^ p[i]) & 0xffu] ^ (c >> 8);
+    return ~c;
+}
+
+// What a caller that holds the whole member and no dictionary makes of its header. msg (InflateMsg): kMsgNone -- the deflate
 // data begins at header_len; kMsgStarved -- the member ends inside its header; kMsgNeedDict -- a zlib header with FDICT
 // (Z_NEED_DICT, a data error for the one-shot caller, uncompr.c:70-75); else the header's fault, with the rules' own id in
 // wrap_msg (zng_rocm_uncompress2_dev tells unknown flag bits apart).  byte_tab: the 256 entries of the CRC-32 byte table

@@ -322,6 +322,71 @@ def compress_members_dev(jobs, njobs, dst, offsets, fmt, level=-1, strategy=0, r
                                                     rocm._dev_ptr(checks) if checks is not None else None, rocm._stream_ptr(stream))
 
 
+class GzipHeader(C.Structure):
+    """zng_rocm_gzip_header: deflateSetHeader's fields for one member; make() builds one from Python values"""
+    _fields_ = [("time", C.c_uint32), ("os", C.c_uint32), ("text", C.c_uint32), ("hcrc", C.c_uint32), ("extra", C.c_void_p),
+                ("name", C.c_void_p), ("comment", C.c_void_p), ("extra_len", C.c_uint32), ("reserved", C.c_uint32)]
+
+    @classmethod
+    def make(cls, time=0, os=3, text=False, hcrc=False, extra=None, name=None, comment=None):
+        """extra / name / comment: bytes or None (the field is absent); name and comment without their terminator"""
+        h = cls(int(time), int(os), int(bool(text)), int(bool(hcrc)), None, None, None, 0, 0)
+        h.set_fields(extra, name, comment)
+        return h
+
+    def set_fields(self, extra, name, comment):
+        self._keep = [None if v is None else C.create_string_buffer(bytes(v), len(v) + 1) for v in (extra, name, comment)]
+        self.extra, self.name, self.comment = (None if k is None else C.addressof(k) for k in self._keep)
+        self.extra_len = 0 if extra is None else len(extra)
+
+
+def gzip_headers(heads):
+    """a ctypes array of zng_rocm_gzip_header from GzipHeader objects (their buffers stay alive with the array)"""
+    arr = (GzipHeader * max(len(heads), 1))()
+    arr._keep = list(heads)
+    for i, h in enumerate(heads):
+        C.memmove(C.byref(arr, i * C.sizeof(GzipHeader)), C.byref(h), C.sizeof(GzipHeader))
+    return arr
+
+
+def gzip_header_bytes(head):
+    """zng_rocm_gzip_header_bytes: the rendered length of a GzipHeader (None: the canonical 10 bytes); 0 for a refused one"""
+    return int(rocm.lib().zng_rocm_gzip_header_bytes(C.byref(head) if head is not None else None))
+
+
+def gzip_header_write(head, level=-1, strategy=0):
+    """zng_rocm_gzip_header_write: the header bytes deflate.c:923-1020 write for these fields, on the host (no device needed);
+    b"" for a refused header, level or strategy"""
+    n = gzip_header_bytes(head)
+    buf = (C.c_uint8 * max(n, 1))()
+    got = rocm.lib().zng_rocm_gzip_header_write(C.byref(head) if head is not None else None, int(level), int(strategy), buf, n)
+    return bytes(buf)[:got]
+
+
+def compress_streams2_header_dev(jobs, heads, njobs, results, level=-1, strategy=0, round_bytes=0, stream=None, window_bits=15):
+    """zng_rocm_compress_streams2_header_dev: compress_streams2_dev(fmt 2) with a gzip header per member; `heads` a gzip_headers()
+    array or None (exactly the call without headers).  Returns the status."""
+    rocm._need_init()
+    return rocm.lib().zng_rocm_compress_streams2_header_dev(int(level), int(strategy), int(window_bits), C.byref(jobs),
+                                                            C.byref(heads) if heads is not None else None, int(njobs),
+                                                            int(round_bytes), rocm._dev_ptr(results) if results is not None else None,
+                                                            rocm._stream_ptr(stream))
+
+
+def compress_members_header_dev(jobs, heads, njobs, dst, offsets, level=-1, strategy=0, round_bytes=0, checks=None, stream=None,
+                                window_bits=15):
+    """zng_rocm_compress_members_header_dev: compress_members_dev(fmt 2) with a gzip header per member -- name, mtime, comment,
+    FEXTRA subfields, header CRC (deflateSetHeader) --; `heads` a gzip_headers() array or None.  Returns the status."""
+    rocm._need_init()
+    cap = int(dst.numel()) if dst is not None else 0
+    return rocm.lib().zng_rocm_compress_members_header_dev(int(level), int(strategy), int(window_bits), C.byref(jobs),
+                                                           C.byref(heads) if heads is not None else None, int(njobs),
+                                                           rocm._dev_ptr(dst) if cap else None, cap, int(round_bytes),
+                                                           rocm._dev_ptr(offsets) if offsets is not None else None,
+                                                           rocm._dev_ptr(checks) if checks is not None else None,
+                                                           rocm._stream_ptr(stream))
+
+
 def compress_streams2_dict_bound(n, fmt):
     return rocm.lib().zng_rocm_compress_streams2_dict_bound(int(n), int(fmt))
 

@@ -119,6 +119,15 @@ _PROTOS = {
                                                         C.c_void_p, C.c_void_p]),
     "zng_rocm_compress_members_window_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
                                                        C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "zng_rocm_gzip_header_bytes": (C.c_size_t, [C.c_void_p]),
+    "zng_rocm_gzip_header_write": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
+    "zng_rocm_compress_streams2_header_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                                        C.c_void_p, C.c_void_p]),
+    "zng_rocm_compress_members_header_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                       C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "zng_rocm_gzip_header_parse": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "zng_rocm_gzip_headers_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
+                                            C.POINTER(C.c_size_t), C.c_void_p]),
     "zng_rocm_dict_create_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "zng_rocm_dict_destroy": (None, [C.c_void_p]),
     "zng_rocm_dict_id": (C.c_uint32, [C.c_void_p]),
