@@ -17,6 +17,12 @@
 //   segs    in: nstreams, per stream: produced dst ncopies, ncopies x (dst n); a copy's slot is its number over all streams
 //           out: "v:" per stream, "copies:" one "slot dst gstart n first" per copy, "segs:" the middle word of every triple,
 //                "seg_dst:", "seg_end:", "v_end:" one number (symbol_tables)
+//   finder  in: ns, ns scanned lengths, nsurvivors, the survivors (64-bit words as the kernels write them: bit position, tag
+//               in bits 40-61, marks in bits 62 and 63)
+//           out: "plan:" item_bytes cap1 cap2 first nitems share, "items:" one "stream lo hi" per item (find_plan),
+//                "patterns_first:" per stream (patterns_first of its length), then one "list:" per stream with its survivors,
+//                sorted (find_demux; the first half of the survivors is given as the run that came back with the counts, the
+//                second as the rest)
 #include <cstdio>
 #include <cstring>
 #include <iostream>
@@ -110,8 +116,34 @@ static int segs() {
     return 0;
 }
 
+static int finder() {
+    size_t ns, n;
+    if (!(std::cin >> ns)) return 2;
+    std::vector<uint64_t> lens(ns);
+    for (auto &x : lens) std::cin >> x;
+    if (!(std::cin >> n)) return 2;
+    std::vector<unsigned long long> got(n);
+    for (auto &x : got) std::cin >> x;
+    if (!std::cin) return 2;
+    const zr::FindPlan p = zr::find_plan(lens.data(), ns);
+    std::vector<zr::FindItemDev> items(p.nitems + 1, zr::FindItemDev{~0ull, ~0ull, ~0u, ~0u});      // (one more: nothing is written there)
+    zr::find_items(lens.data(), ns, p.share, items.data());
+    if (items.back().stream != ~0u) return 3;
+    items.pop_back();
+    printf("plan: %llu %u %u %u %zu %llu\nitems:", (unsigned long long)p.item_bytes, p.cap1, p.cap2, p.first, p.nitems, (unsigned long long)p.share);
+    for (const zr::FindItemDev &it : items) printf(" %u %llu %llu", it.stream, it.lo, it.hi);
+    printf("\npatterns_first:");
+    for (uint64_t len : lens) printf(" %u", zr::patterns_first((size_t)len));
+    printf("\n");
+    for (const auto &list : zr::find_demux(got.data(), n / 2, got.data() + n / 2, n - n / 2, ns))
+        line("list:", std::vector<uint64_t>(list.begin(), list.end()));
+    return 0;
+}
+
 int main(int argc, char **argv) {
-    if (argc > 1) return !strcmp(argv[1], "layout") ? layout() : !strcmp(argv[1], "retry") ? retry() : !strcmp(argv[1], "chainfull") ? chainfull() : !strcmp(argv[1], "segs") ? segs() : 2;
+    if (argc > 1)
+        return !strcmp(argv[1], "layout") ? layout() : !strcmp(argv[1], "retry") ? retry() : !strcmp(argv[1], "chainfull") ? chainfull()
+               : !strcmp(argv[1], "segs") ? segs() : !strcmp(argv[1], "finder") ? finder() : 2;
     size_t rows, pbase, np;
     uint32_t window_len;
     uint64_t src_len;

@@ -1,4 +1,4 @@
-"""The block finder's range tests (zlib-ng_amd/csrc/inflate_large.hip, find_headers_kernel<false>) are evaluated for the eight
+"""The block finder's range tests (zlib-ng_amd/csrc/inflate_large.hip, find_headers_range<false>) are evaluated for the eight
 bit positions of a byte at once, as bit masks over a 32-bit window.  This pins the mask algebra against the rules it stands
 for -- BTYPE == 2 (inflate.c:748-757), HLIT <= 29 and HDIST <= 29, i.e. nlen <= 286 and ndist <= 30 (inflate.c:808-813) --
 for every 20-bit window (position k looks at bits k .. k+12, k < 8).  CPU only; the device code itself is covered by

@@ -14,9 +14,12 @@ by hand from the rules in the header's and the part kernel's comments:
   joins the one in front of it unless it is the only one.
 
 The rules the device pass reads its scratch and its second launch from are driven the same way (the driver's `layout`, `retry`
-and `segs` arguments):
+and `segs` arguments), and so are the finder's host rules (`finder`):
 
-  part tables  jobs (40 bytes per part) | starts (8; SUBBLOCK: | keys, 8) | results (8 words; blocks mode: | marks, 4 words;
+  finder       a pass over N streams is cut into work items of a 4096th of its bytes, a multiple of 4096 within 4 .. 64 KiB;
+               room for a survivor per 64 bytes (F1) and per 512 (F2, the patterns) and 4096 per stream; a survivor goes to
+               the stream its tag (bits 40-61) names, without the tag and bit 63, and each stream's list is sorted by bit
+  part tables jobs (40 bytes per part) | starts (8; SUBBLOCK: | keys, 8) | results (8 words; blocks mode: | marks, 4 words;
                SUBBLOCK: | side words, 8 words) | slots, every table at a multiple of 256 bytes; the pinned mirror ends where
                the slots begin
   retry        a part that said "output full" (message 13) runs again with retry_cap = (1032 x its compressed bytes + 655360,
@@ -261,6 +264,63 @@ def test_the_first_full_part_on_the_chain(driver):
     assert ask(2, 6, [full, full, ok(4), full, ok(5), (0, 1, none), full]) == "end"
     assert ask(2, 6, [full, full, ok(4), full, ok(6), (0, 1, none), full]) == "broken"
     assert ask(2, 6, [full, full, ok(3), full, ok(5), (0, 1, none), full]) == 3
+
+
+KiB, MiB = 1 << 10, 1 << 20
+FIND_LENS = [128 * KiB, 128 * KiB + 1, MiB + 4095, 256 * MiB, (1 << 31) - 1]
+TAG_SHIFT, STORED, BEHIND_MARKER = 40, 1 << 62, 1 << 63       # kFindTagShift; a survivor's marks
+
+
+def finder(exe, lens, survivors=()):
+    """-> ((item_bytes, share), cap1, cap2, first, [(stream, lo, hi)], [patterns_first per stream], [sorted list per stream])"""
+    words = [len(lens)] + list(lens) + [len(survivors)] + list(survivors)
+    out = subprocess.run([exe, "finder"], input=" ".join(str(w) for w in words), capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stderr
+    rows = [[int(x) for x in ln.split()[1:]] for ln in out.stdout.strip("\n").split("\n")]
+    (item_bytes, cap1, cap2, first, nitems, share), items, pfirst, lists = rows[0], rows[1], rows[2], rows[3:]
+    assert len(items) == 3 * nitems and len(pfirst) == len(lens) and len(lists) == len(lens)
+    return (item_bytes, share), cap1, cap2, first, [tuple(items[i:i + 3]) for i in range(0, len(items), 3)], pfirst, lists
+
+
+@pytest.mark.parametrize("lens", [[n] for n in FIND_LENS] + [FIND_LENS], ids=lambda v: "+".join(str(n) for n in v))
+def test_finder_items_and_caps(driver, lens):
+    """one finder pass: a stream's work items tile it in order, equal ones, as few as stay within a 4096th of the pass's bytes
+    (4 .. 64 KiB) -- so one stream of up to 256 MiB is cut into 4096, as many as the chip takes in two rounds; room for a survivor per 64 (F1) and per 512 bytes (F2, the
+    patterns) of the pass and 4096 per stream; one stream is a table of one, with the bounds decoy_cases.py restates"""
+    import decoy_cases as dcy
+    ns, total = len(lens), sum(lens)
+    (item_bytes, share), cap1, cap2, first, items, pfirst, _ = finder(driver, lens)
+    assert item_bytes == max(4096, min(65536, (total // 4096 + 4095) & ~4095))
+    assert item_bytes % 4096 == 0 and 4096 <= item_bytes <= 65536
+    assert share == max(4096, min(item_bytes, -(-total // 4096)))
+    assert [k for k, _, _ in items] == sorted(k for k, _, _ in items)        # the streams in the table's order
+    assert len(items) == sum(-(-n // share) for n in lens)                   # as many as the plan counts, and no others
+    for k, n in enumerate(lens):
+        own = [(lo, hi) for s, lo, hi in items if s == k]
+        assert own[0][0] == 0 and own[-1][1] == n
+        assert all(a[1] == b[0] for a, b in zip(own, own[1:]))               # no gap, no overlap
+        assert all(0 < hi - lo <= share <= item_bytes for lo, hi in own)
+        assert len(own) == -(-n // share)
+        assert all(hi - lo == -(-n // len(own)) for lo, hi in own[:-1])      # equal shares; the last one has what is left
+    assert (cap1, cap2) == (total // 64 + 4096 * ns, total // 512 + 4096 * ns) and cap1 < 1 << 32
+    assert first == min(cap2, 16384 + 64 * ns)
+    assert pfirst == [dcy.patterns_first(n) for n in lens]
+    if ns == 1:
+        assert len(items) == (4096 if (16 << 20) <= total <= (256 << 20) else -(-total // share))
+        assert cap2 == dcy.cap2(lens[0]) and cap1 == min(lens[0] // 64 + 4096, 64 << 20)
+        assert first >= pfirst[0]                         # whether the patterns cut the stream is known without a second copy
+
+
+def test_finder_survivors_go_to_their_stream_sorted(driver):
+    def tagged(k, bit, marks=0):
+        return (k << TAG_SHIFT) | bit | marks
+    got = [tagged(0, 90, STORED | BEHIND_MARKER), tagged(1, 800), tagged(0, 50, BEHIND_MARKER), tagged(3, 5),
+           tagged(2, 7), tagged(0, 80), tagged(0x3fffff, 1), tagged(0, 70, STORED | BEHIND_MARKER), tagged(1, 16, BEHIND_MARKER)]
+    lists = finder(driver, [128 * KiB] * 3, got)[6]
+    # by its tag, which comes off with bit 63; tags 3 and 0x3fffff name no stream of a table of three; bit 62 stays and does
+    # not count in the order (by_bit: a sort by value would put 80 in front of 70 | STORED)
+    assert lists == [[50, 70 | STORED, 80, 90 | STORED], [16, 800], [7]]
+    assert finder(driver, [128 * KiB], [tagged(0, 9), tagged(1, 3), tagged(0, 4, BEHIND_MARKER)])[6] == [[4, 9]]
 
 
 def test_symbol_tables_of_one_stream(driver):

@@ -1,5 +1,6 @@
-// inflate_dev_types.h -- the part of inflate_dev.h that needs no HIP: the device job descriptor, the message ids of d_results
-// and the sync kernel's work item.  inflate_large_plan.h (plain host code, compiled by a CPU test as well) is built on these.
+// inflate_dev_types.h -- the part of inflate_dev.h that needs no HIP: the device job descriptor, the message ids of d_results,
+// the block-start finder's tables and the sync kernel's work item.  inflate_large_plan.h (plain host code, compiled by a CPU
+// test as well) is built on these.
 #pragma once
 #include <stdint.h>
 
@@ -28,6 +29,20 @@ enum InflateMsg : uint32_t {
     // wrappers (framing_dev.hip; inflate.c:509-555 header checks, :686-692 FHCRC, :1105-1147 trailer checks)
     kMsgHeaderCheck, kMsgMethod, kMsgWindow, kMsgHeaderCrc, kMsgNeedDict, kMsgDataCheck, kMsgLengthCheck, kMsgCount
 };
+
+// The block-start finder's tables (inflate_large.hip: find_headers_table_kernel, validate_headers_table_kernel,
+// first_bytes_kernel): the streams of one finder pass, and the work items -- a range of one stream each -- its scan is cut
+// into.  The survivors of all streams go to ONE list, each tagged with its stream's index in the table.
+struct FindStreamDev {
+    const uint8_t     *src;
+    unsigned long long src_len;
+};
+struct FindItemDev {
+    unsigned long long lo, hi;    // bytes of the stream
+    uint32_t           stream, pad;
+};
+constexpr unsigned kFindTagShift = 40;                   // a bit position takes 34 bits, the marks bits 62 and 63
+constexpr unsigned long long kFindTagMask = 0x3fffffull << kFindTagShift;
 
 // a region of the stream that starts at a block start the finder gave (one work item: at most 64 guesses, so a long region
 // is several items): `n` guesses at start + (k0 + k) * spacing, k = 1 .. n, written to out_bit / out_key [first + 2 (k - 1)] (a symbol boundary B and its key, or ~0 = none) and, when the region's

@@ -4,13 +4,13 @@
 // block header carries no marker.  inflate_dev.hip therefore needs many streams to fill the chip (one wavefront each).
 // This file cuts ONE stream into parts the same kernel can take -- the scheme of inflate_threads.cpp (pugz / rapidgzip),
 // with the device in place of the host threads:
-//   F1 find_headers_kernel      every BIT position of the stream is tested for the start of a dynamic block the decoder
+//   F1 find_headers_table_kernel  every BIT position of the stream is tested for the start of a dynamic block the decoder
 //        would accept, cheap tests first: BTYPE / HLIT / HDIST in range (inflate.c:808-813), the code-length code complete
 //        (inftrees.c:126-131; a Kraft sum over the 3-bit fields, three fields per table lookup).  About 1 position in
 //        10^3 is left.  Also: the byte pattern 00 00 ff ff of a sync-flush marker (deflate.c:1064-1076) -- the block
 //        behind it starts on the next byte, whatever its type -- and a stored block's header on a byte boundary
 //        (header byte, LEN, NLEN = ~LEN; inflate.c:759-775): incompressible data is a chain of those.
-//   F2 validate_headers_kernel  one lane per survivor decodes the whole header (inflate.c:814-917) and applies the
+//   F2 validate_headers_table_kernel  one lane per survivor decodes the whole header (inflate.c:814-917) and applies the
 //        validity rules of inflate_table to the two code sets (inftrees.c:104-137): about 1 random position in 10^6
 //        survives both kernels, real block starts all do.
 //   host                        sorts the few thousand candidates (at least 2 KiB of compressed bytes apart); bit 0 is
@@ -26,12 +26,13 @@
 //        K2 / K3 of inflate_resolve.hip resolve and translate.
 // Anything irregular on the chain -- a data error, a truncated stream, a distance too far back, no candidates (a stream of fixed-Huffman blocks only) -- sends the call to the sequential host decoder, which
 // then reports exactly what the reference would (status, message, bytes produced, bytes consumed).
-// The steps from P on are written ONCE, for N streams (pass_run): one part launch over the parts of all of them, one more for
-// the parts whose slot was too small, one chain per stream, one compaction, one resolve.  In front of it are two finders:
-// inflate_large_try's (F1 / F2 above, over ONE stream: the one-pass call, every piece of zng_rocm_inflate_large_pieces_dev, the
-// hook's blocks mode, a host-resident stream) and round_find's (the same scan over a table of (stream, range) items:
-// zng_rocm_inflate_large_streams_dev, a round of streams at a time).  Each caller maps what the pass says about a stream --
-// done, too large for dst_cap, or "left the pass" -- to its own convention.
+// Every step is written ONCE, for N streams.  The finder (find_starts) scans a table of (stream, range) items whose survivors
+// carry their stream: the byte patterns for all streams, F1 / F2 for those they do not cut.  The pass behind it (pass_run):
+// one part launch over the parts of all streams, one more for the parts whose slot was too small, one chain per stream, one
+// compaction, one resolve.  ONE stream -- inflate_large_try: the one-pass call, every piece of
+// zng_rocm_inflate_large_pieces_dev, the hook's blocks mode, a host-resident stream -- is a table of one;
+// zng_rocm_inflate_large_streams_dev takes a round of streams at a time.  Each caller maps what the finder and the pass say
+// about a stream -- done, too large for dst_cap, or "left the pass" -- to its own convention.
 // What the host does between the launches -- the steps named above, the SUBBLOCK regions and their merge, the slot sizes,
 // where the tables lie in scratch, which parts run again, the symbol array's layout -- is in inflate_large_plan.h.  This file
 // keeps the kernels, the scratch and table uploads, the launches and synchronisations, and each entry point's policy for a
@@ -84,11 +85,8 @@ __device__ __forceinline__ unsigned long long bits_at_dev(const uint8_t *src, un
 // PATTERNS = true: the two byte patterns only (no bit position is tested): the first pass -- a stream whose encoder left a
 // sync marker or a stored block every few tens of KiB (this library's level-6 class, pigz) offers enough starts that way.
 constexpr uint32_t kFindLocal = 2048;
-// The scan itself, bytes [lo_b, hi_b) of one stream: find_headers_kernel gives every workgroup an equal share of ONE stream,
-// find_headers_table_kernel a (stream, range) pair of a table; `tag` (0, or the stream's index << kFindTagShift) is set in
-// every survivor.
-constexpr unsigned kFindTagShift = 40;                   // a bit position takes 34 bits, the marks bits 62 and 63
-constexpr unsigned long long kFindTagMask = 0x3fffffull << kFindTagShift;
+// The scan itself, bytes [lo_b, hi_b) of one stream: find_headers_table_kernel gives every workgroup a (stream, range) pair
+// of a table; `tag` (the stream's index << kFindTagShift, inflate_dev_types.h) is set in every survivor.
 template <bool PATTERNS>
 __device__ __forceinline__ void find_headers_range(const uint8_t *__restrict__ src, const unsigned long long src_len,
                                                    const unsigned long long lo_b, const unsigned long long hi_b,
@@ -231,26 +229,9 @@ __device__ __forceinline__ void find_headers_range(const uint8_t *__restrict__ s
     flush();
 }
 
-template <bool PATTERNS>
-__global__ __launch_bounds__(256)
-void find_headers_kernel(const uint8_t *__restrict__ src, unsigned long long src_len, unsigned long long *__restrict__ cand,
-                         uint32_t *__restrict__ ncand, uint32_t cap) {
-    const unsigned long long per = (src_len + gridDim.x - 1) / gridDim.x;
-    const unsigned long long lo_b = per * blockIdx.x, hi_b = lo_b + per < src_len ? lo_b + per : src_len;
-    find_headers_range<PATTERNS>(src, src_len, lo_b, hi_b, 0ull, cand, ncand, cap);
-}
-
-// F1 over the streams of a batch (zng_rocm_inflate_large_streams_dev): grid.x = work item, a range of one stream; the
-// survivors of all streams go to ONE list, each tagged with its stream's index in the table (still one global atomic per
-// workgroup and flush)
-struct FindStreamDev {
-    const uint8_t     *src;
-    unsigned long long src_len;
-};
-struct FindItemDev {
-    unsigned long long lo, hi;    // bytes of the stream
-    uint32_t           stream, pad;
-};
+// F1 over the streams of a finder pass (FindStreamDev / FindItemDev: inflate_dev_types.h): grid.x = work item, a range of one
+// stream; the survivors of all streams go to ONE list, each tagged with its stream's index in the table (still one global
+// atomic per workgroup and flush)
 template <bool PATTERNS>
 __global__ __launch_bounds__(256)
 void find_headers_table_kernel(const FindStreamDev *__restrict__ streams, const FindItemDev *__restrict__ items,
@@ -271,30 +252,28 @@ void find_headers_table_kernel(const FindStreamDev *__restrict__ streams, const 
 constexpr int kValLanes = 64;
 __device__ __forceinline__ void validate_one(const uint8_t *__restrict__ src, unsigned long long src_len, const unsigned long long c0, uint8_t *T,
                              unsigned long long *__restrict__ good, uint32_t *__restrict__ ngood, uint32_t cap,
-                             const unsigned long long tag = 0ull);
-__global__ __launch_bounds__(kValLanes)
-void validate_headers_kernel(const uint8_t *__restrict__ src, unsigned long long src_len,
-                             const unsigned long long *__restrict__ cand, const uint32_t *__restrict__ ncand, uint32_t cand_cap,
-                             unsigned long long *__restrict__ good, uint32_t *__restrict__ ngood, uint32_t cap) {
-    __shared__ uint8_t tab[kValLanes][128];
-    // the number of candidates is read here, not on the host: F1 -> F2 needs no round trip (the grid is fixed, each
-    // workgroup takes every gridDim.x-th group of 64 candidates; a lane's candidates are independent of each other)
-    const uint32_t n = *ncand < cand_cap ? *ncand : cand_cap;
-    for (uint32_t i = blockIdx.x * kValLanes + threadIdx.x; i < n; i += gridDim.x * kValLanes)
-        validate_one(src, src_len, cand[i], tab[threadIdx.x], good, ngood, cap);
-}
+                             const unsigned long long tag);
 // F2 over the tagged list of find_headers_table_kernel: a survivor's stream is looked up by its tag, which it keeps
 __global__ __launch_bounds__(kValLanes)
 void validate_headers_table_kernel(const FindStreamDev *__restrict__ streams, const unsigned long long *__restrict__ cand,
                                    const uint32_t *__restrict__ ncand, uint32_t cand_cap, unsigned long long *__restrict__ good,
                                    uint32_t *__restrict__ ngood, uint32_t cap) {
     __shared__ uint8_t tab[kValLanes][128];
+    // the number of candidates is read here, not on the host: F1 -> F2 needs no round trip (the grid is fixed, each
+    // workgroup takes every gridDim.x-th group of 64 candidates; a lane's candidates are independent of each other)
     const uint32_t n = *ncand < cand_cap ? *ncand : cand_cap;
     for (uint32_t i = blockIdx.x * kValLanes + threadIdx.x; i < n; i += gridDim.x * kValLanes) {
         const unsigned long long c = cand[i];
         const FindStreamDev s = streams[(c & kFindTagMask) >> kFindTagShift];
         validate_one(s.src, s.src_len, c & ~kFindTagMask, tab[threadIdx.x], good, ngood, cap, c & kFindTagMask);
     }
+}
+// the tables of a finder pass (and its zeroed counts) from the pinned host memory they were written to, `n` 16-byte words,
+// one per lane: the device reads host memory over the bus, so the upload is a launch on the queue the scan follows on
+__global__ __launch_bounds__(256)
+void finder_tables_kernel(const uint4 *__restrict__ pinned, uint4 *__restrict__ tables, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) tables[i] = pinned[i];
 }
 // the first two bytes of every stream of the table (SUBBLOCK wants the first block's type), one lane each
 __global__ __launch_bounds__(256)
@@ -537,8 +516,10 @@ struct PassStream {
     uint8_t       *d_dst = nullptr;
     size_t         dst_cap = 0;
     unsigned long long start_bit = 0;                     // the stream begins at this bit of d_src (blocks mode, pieces)
-    unsigned long long key0 = 0;                          // pieces: the first start may lie inside a block itself (PiecePass)
-    uint16_t       b0 = 0;                                // the two bytes at start_bit (SUBBLOCK, when F1 + F2 ran)
+    size_t         scan_lo = 0;                           // the finder scans from this byte of d_src on: the byte start_bit lies in
+                                                          // (pieces: the buffer may begin in front of the piece, PiecePass)
+    unsigned long long key0 = 0;                         // pieces: the first start may lie inside a block itself (PiecePass)
+    uint16_t       b0 = 0;                                // the two bytes at scan_lo, where start_bit lies (SUBBLOCK, when F1 + F2 ran)
     bool           patterns_do = false;                   // the byte patterns alone cut the stream
     std::vector<unsigned long long> starts;               // sorted (thin_starts)
     size_t         heavy = 1;
@@ -561,6 +542,132 @@ struct PassStream {
 static void leave(PassStream &s, const char *reason) {
     s.left = true;
     why(reason);
+}
+
+// ---- the finder ---------------------------------------------------------------------------------------------------------
+// One finder pass over the streams `which` (indices into ss and good), each from its scan_lo on: the patterns alone, or F1 +
+// F2 (and, `bytes`, every stream's first two scanned bytes).  What is scanned, the caps and whose a survivor is are find_plan's
+// and find_demux's (inflate_large_plan.h).  Fills good[..] with each stream's survivors, as bit positions of its d_src,
+// sorted; when the lists cannot be had the streams leave the device path.  The tables (streams | items | the counts, zero) go
+// up from the pinned scratch, which is free -- every pass ends in a synchronisation; one copy down and one synchronisation
+// (a second of each when the list is longer than what comes back with the counts).
+// What a caller with ONE stream wants to know besides (inflate_large_try keeps its own answers to both):
+struct FindOne {
+    uint32_t n_f1 = ~0u;                                  // F1's survivors, when F1 + F2 ran over the one stream
+    int      no_room = ZNG_ROCM_OK;                       // the scratch reservation's error, when that is why the streams left
+};
+static int find_pass(Workspace *ws, std::vector<PassStream> &ss, std::vector<std::vector<unsigned long long>> &good,
+                     const std::vector<size_t> &which, bool patterns, bool bytes, hipStream_t st, FindOne *one = nullptr) {
+    const size_t ns = which.size();
+    if (!ns) return ZNG_ROCM_OK;
+    std::vector<uint64_t> lens(ns);
+    for (size_t k = 0; k < ns; ++k) lens[k] = ss[which[k]].src_len - ss[which[k]].scan_lo;
+    const FindPlan P = find_plan(lens.data(), ns);
+    const uint32_t cap1 = P.cap1, cap2 = P.cap2, first = P.first;
+    // streams | items | counts | first bytes | survivors on both sides (the pinned side: the first survivors alone), so that
+    // streams | items | counts go up in one copy and counts | first bytes | the first survivors come down in one; behind
+    // them, on the device, F1's candidates
+    TableLayout dl;
+    const size_t o_tab = dl.add(ns * sizeof(FindStreamDev)), o_items = dl.add(P.nitems * sizeof(FindItemDev)), o_n = dl.add(64),
+                 o_b0 = dl.add(ns * 2);
+    TableLayout hl = dl;
+    const size_t o_good = dl.add((size_t)cap2 * 8), o_cand = dl.add((size_t)cap1 * 8), o_hgood = hl.add((size_t)first * 8);
+    uint8_t *fp = nullptr, *hp = nullptr;
+    auto out = [&](const char *reason) {
+        for (size_t w : which) ss[w].left = true;
+        return why(reason);
+    };
+    int room = scratch_reserve(ws, kScrLargeCand, dl.bytes, false, (void **)&fp);
+    if (room == ZNG_ROCM_OK) room = scratch_reserve(ws, kScrLargeCandHost, hl.bytes, true, (void **)&hp);
+    if (room != ZNG_ROCM_OK) {
+        if (one) one->no_room = room;
+        return out("no room for the finder's candidates");
+    }
+    FindStreamDev *d_tab = (FindStreamDev *)(fp + o_tab), *h_tab = (FindStreamDev *)(hp + o_tab);
+    FindItemDev *d_items = (FindItemDev *)(fp + o_items);
+    uint32_t *d_n = (uint32_t *)(fp + o_n), *n12 = (uint32_t *)(hp + o_n);       // [0] survivors of F1, [1] of F2 (or the patterns)
+    uint16_t *d_b0 = (uint16_t *)(fp + o_b0), *h_b0 = (uint16_t *)(hp + o_b0);
+    unsigned long long *d_cand = (unsigned long long *)(fp + o_cand), *d_good = (unsigned long long *)(fp + o_good);
+    unsigned long long *h_good = (unsigned long long *)(hp + o_hgood);
+    for (size_t k = 0; k < ns; ++k) h_tab[k] = FindStreamDev{ss[which[k]].d_src + ss[which[k]].scan_lo, lens[k]};
+    find_items(lens.data(), ns, P.share, (FindItemDev *)(hp + o_items));
+    n12[0] = n12[1] = 0;
+    // streams | items | the two counts, zero: fetched by a kernel (o_n + 256 bytes, which both sides have: every table is a
+    // multiple of 256).  The stream is idle here, and a copy on the copy engine in front of the scan cost each pass 10 us
+    // more than the fill kernel that zeroed the counts of the one-stream finder.
+    hipLaunchKernelGGL(finder_tables_kernel, dim3((unsigned)((o_n + 256) / 16 + 255) / 256), dim3(256), 0, st, (const uint4 *)hp, (uint4 *)fp,
+                       (uint32_t)((o_n + 256) / 16));
+    ZR_HIP(hipGetLastError());
+    if (patterns) {
+        hipLaunchKernelGGL(find_headers_table_kernel<true>, dim3((unsigned)P.nitems), dim3(256), 0, st, d_tab, d_items, d_good, d_n + 1, cap2);
+        ZR_HIP(hipGetLastError());
+    } else {
+        hipLaunchKernelGGL(find_headers_table_kernel<false>, dim3((unsigned)P.nitems), dim3(256), 0, st, d_tab, d_items, d_cand, d_n, cap1);
+        ZR_HIP(hipGetLastError());
+        hipLaunchKernelGGL(validate_headers_table_kernel, dim3(8192), dim3(kValLanes), 0, st, d_tab, d_cand, d_n, cap1, d_good, d_n + 1, cap2);
+        ZR_HIP(hipGetLastError());
+        if (bytes) {
+            hipLaunchKernelGGL(first_bytes_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, st, d_tab, (uint32_t)ns, d_b0);
+            ZR_HIP(hipGetLastError());
+        }
+    }
+    // the counts, the first bytes and (what is almost always all of) the list in one copy and one round trip
+    ZR_HIP(hipMemcpyAsync(n12, d_n, (o_good - o_n) + (size_t)first * 8, hipMemcpyDeviceToHost, st));
+    ZR_HIP(hipStreamSynchronize(st));
+    if (one && ns == 1 && !patterns) one->n_f1 = n12[0];
+    if (n12[0] > cap1 || n12[1] > cap2) {
+        // One stream's payload can hold more places that pass for a block start than the whole pass has room for (a stored
+        // block full of 00 00 ff ff).  That is that stream's trouble, not its neighbours': each half of the streams on its
+        // own, down to the stream that has them -- which leaves.
+        if (ns == 1)
+            return out(n12[0] > cap1 ? "far more candidates in the stream than a deflate stream has"
+                                     : "far more valid block headers than a deflate stream has");
+        const std::vector<size_t> lower(which.begin(), which.begin() + ns / 2), upper(which.begin() + ns / 2, which.end());
+        if (int rc = find_pass(ws, ss, good, lower, patterns, bytes, st)) return rc;
+        return find_pass(ws, ss, good, upper, patterns, bytes, st);
+    }
+    const uint32_t n2 = n12[1];
+    std::vector<unsigned long long> rest;
+    if (n2 > first) {
+        rest.resize(n2 - first);
+        ZR_HIP(hipMemcpyAsync(rest.data(), d_good + first, (size_t)(n2 - first) * 8, hipMemcpyDeviceToHost, st));
+        ZR_HIP(hipStreamSynchronize(st));
+    }
+    std::vector<std::vector<unsigned long long>> per = find_demux(h_good, std::min(n2, first), rest.data(), rest.size(), ns);
+    for (size_t k = 0; k < ns; ++k) {
+        PassStream &s = ss[which[k]];
+        if (bytes && !patterns) s.b0 = h_b0[k];
+        for (unsigned long long &b : per[k]) b += 8ull * s.scan_lo;
+        good[which[k]].swap(per[k]);
+    }
+    return ZNG_ROCM_OK;
+}
+
+// The finder, for the streams `scan` (indices into ss and good) of a pass: the byte patterns (sync markers, byte-aligned
+// stored blocks) for every stream; when they leave no 128 KiB of a stream's compressed bytes without a start, that is all the
+// cutting it needs, and the search of every bit position (F1's main loop) and F2 run for the other streams alone -- 1.3 of
+// 9.4 ms for the 256 MiB cfg3 stream of this library's level-6 class.  `sub`: with F1 + F2 come the stream's first two bytes.
+// A stream whose lists cannot be had has left the device path; thinning the lists into starts is the caller's.
+// The scan begins at the byte the stream's first bit lies in, so the two bytes handed back (b0) hold the first block's header
+// at bit start_bit & 7.  Every caller has it so -- pieces pass start_bit = bit - 8 base and scan_lo = (bit >> 3) - base, blocks
+// mode start_bit < 8 and scan_lo = 0 -- and anything else is refused before a launch.
+static int find_starts(Workspace *ws, std::vector<PassStream> &ss, std::vector<std::vector<unsigned long long>> &good,
+                       const std::vector<size_t> &scan, bool sub, hipStream_t st, FindOne *one = nullptr) {
+    for (size_t k : scan) {
+        if ((ss[k].start_bit >> 3) != ss[k].scan_lo) {
+            set_error("inflate_large: the finder's scan does not begin at the byte of the stream's first bit");
+            return ZNG_ROCM_EINVAL;
+        }
+    }
+    if (int rc = find_pass(ws, ss, good, scan, true, false, st, one)) return rc;
+    std::vector<size_t> full;
+    for (size_t k : scan) {
+        PassStream &s = ss[k];
+        if (s.left) continue;
+        s.patterns_do = good[k].size() <= patterns_first(s.src_len - s.scan_lo) && patterns_cut(good[k], s.start_bit, 8ull * s.src_len);
+        if (!s.patterns_do) full.push_back(k);
+    }
+    return find_pass(ws, ss, good, full, false, sub, st, one);
 }
 
 // pass_run's counting mode (zng_rocm_uncompress_large_size_dev / _sizes_dev): the parts of the streams `on` -- `np` together,
@@ -894,7 +1001,7 @@ static int pass_run(Workspace *ws, std::vector<PassStream> &ss, bool sub, bool b
     return ZNG_ROCM_OK;
 }
 
-// ONE stream through its own finder and the pass: returns 1 with *out_len / *in_used set, or 0 = "irregular: use the
+// ONE stream through the finder and the pass, as a table of one: returns 1 with *out_len / *in_used set, or 0 = "irregular: use the
 // sequential decoder", or a negative error (-5 with *out_len set: dst_cap is too small).
 // Blocks mode (`blocks`, the streaming hook): the stream starts at bit `start_bit` of d_src, and *end_bit / *final say where
 // the delivered blocks end and whether the BFINAL one is among them.  `sub`, `pp`: see pass_run.
@@ -903,72 +1010,6 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
                              bool blocks = false, uint64_t start_bit = 0, uint64_t *end_bit_out = nullptr, int *final_out = nullptr,
                              bool sub = false, PiecePass *pp = nullptr) {
     if (!large_length_ok(src_len)) return why("stream below 128 KiB (or 2 GiB and more)");
-    // ---- candidates ---------------------------------------------------------------------------------------------
-    // (pieces: the finder scans the piece alone, from scan_lo; its bit positions are moved to the buffer's by `lo_bits`)
-    const size_t scan_lo = pp ? (size_t)pp->scan_lo : 0, scan_len = src_len - scan_lo;
-    const unsigned long long lo_bits = 8ull * scan_lo;
-    const uint32_t cap1 = (uint32_t)std::min<size_t>(scan_len / 64 + 4096, 64u << 20);
-    const uint32_t cap2 = (uint32_t)std::min<size_t>(scan_len / 512 + 4096, 8u << 20);      // starts are >= 2 KiB apart in the end
-    // first pass: the byte patterns alone (sync markers, byte-aligned stored blocks); when they leave no 128 KiB of compressed
-    // bytes without a start, that is all the cutting the stream needs and the search of every bit position (F1's
-    // main loop) and F2 are skipped -- 1.3 of 9.4 ms for the 256 MiB cfg3 stream of this library's level-6 class
-    const uint32_t first = patterns_first(scan_len);
-    TableLayout dl, hl;
-    const size_t o_cand = dl.add((size_t)cap1 * 8), o_good = dl.add((size_t)cap2 * 8), o_n = dl.add(64);
-    const size_t o_n12 = hl.add(64), o_hgood = hl.add((size_t)first * 8);
-    // what comes back from the device passes through pinned memory (see pass_run)
-    uint8_t *fp = nullptr, *hp = nullptr;
-    if (int rc = scratch_reserve(ws, kScrLargeCand, dl.bytes, false, (void **)&fp)) return rc;
-    if (int rc = scratch_reserve(ws, kScrLargeCandHost, hl.bytes, true, (void **)&hp)) return rc;
-    unsigned long long *d_cand = (unsigned long long *)(fp + o_cand), *d_good = (unsigned long long *)(fp + o_good);
-    uint32_t *d_n = (uint32_t *)(fp + o_n);               // [0] survivors of F1, [1] of F2
-    uint32_t *n12 = (uint32_t *)(hp + o_n12);
-    unsigned long long *h_good = (unsigned long long *)(hp + o_hgood);
-    std::vector<unsigned long long> good;
-    n12[0] = n12[1] = 0;
-    ZR_HIP(hipMemsetAsync(d_n, 0, 8, st));
-    hipLaunchKernelGGL(find_headers_kernel<true>, dim3(4096), dim3(256), 0, st, d_src + scan_lo, (unsigned long long)scan_len, d_good,
-                       d_n + 1, cap2);
-    ZR_HIP(hipGetLastError());
-    ZR_HIP(hipMemcpyAsync(n12, d_n, 8, hipMemcpyDeviceToHost, st));
-    ZR_HIP(hipMemcpyAsync(h_good, d_good, (size_t)first * 8, hipMemcpyDeviceToHost, st));
-    ZR_HIP(hipStreamSynchronize(st));
-    bool patterns_do = n12[1] <= first;                   // (what came back is the whole list)
-    if (patterns_do) {
-        good.assign(h_good, h_good + n12[1]);
-        for (unsigned long long &b : good) b = (b & ~(1ull << 63)) + lo_bits;
-        std::sort(good.begin(), good.end(), by_bit);
-        patterns_do = patterns_cut(good, start_bit, 8ull * src_len);
-    }
-    if (!patterns_do) {
-        ZR_HIP(hipMemsetAsync(d_n, 0, 8, st));
-        hipLaunchKernelGGL(find_headers_kernel<false>, dim3(4096), dim3(256), 0, st, d_src + scan_lo, (unsigned long long)scan_len,
-                           d_cand, d_n, cap1);
-        ZR_HIP(hipGetLastError());
-        hipLaunchKernelGGL(validate_headers_kernel, dim3(8192), dim3(kValLanes), 0, st, d_src + scan_lo, (unsigned long long)scan_len,
-                           d_cand, d_n, cap1, d_good, d_n + 1, cap2);
-        ZR_HIP(hipGetLastError());
-        // the counts and (what is almost always all of) the list in one round trip (SUBBLOCK: and the first block's header)
-        ZR_HIP(hipMemcpyAsync(n12, d_n, 8, hipMemcpyDeviceToHost, st));
-        if (sub) ZR_HIP(hipMemcpyAsync(n12 + 2, d_src + (start_bit >> 3), 2, hipMemcpyDeviceToHost, st));
-        ZR_HIP(hipMemcpyAsync(h_good, d_good, (size_t)first * 8, hipMemcpyDeviceToHost, st));
-        ZR_HIP(hipStreamSynchronize(st));
-        // (SUBBLOCK goes on without candidates: a stream of fixed-code blocks is cut inside them)
-        if ((n12[0] == 0 && !sub) || n12[0] > cap1) return why("no candidate block starts, or far more than a deflate stream has");
-        if (n12[1] <= cap2) good.assign(h_good, h_good + std::min(n12[1], first));
-    }
-    const uint32_t n2 = n12[1];
-    if (n2 > cap2) return why("far more valid block headers than a deflate stream has");
-    good.resize(n2);
-    if (n2 > first) {
-        ZR_HIP(hipMemcpyAsync(good.data() + first, d_good + first, (size_t)(n2 - first) * 8, hipMemcpyDeviceToHost, st));
-        ZR_HIP(hipStreamSynchronize(st));
-    }
-    if (!patterns_do) {                                              // (the patterns' list has been sorted above)
-        for (unsigned long long &b : good) b = (b & ~(1ull << 63)) + lo_bits;
-        std::sort(good.begin(), good.end(), by_bit);
-    }
-    // ---- the pass over this one stream ------------------------------------------------------------------------------
     std::vector<PassStream> ss(1);
     PassStream &s = ss[0];
     s.d_src = d_src;
@@ -978,10 +1019,18 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
     s.d_dst = d_dst;
     s.dst_cap = dst_cap;
     s.start_bit = start_bit;
+    s.scan_lo = pp ? (size_t)pp->scan_lo : 0;             // (pieces: the finder scans the piece alone)
     s.key0 = pp ? pp->key0 : 0ull;
-    s.b0 = (uint16_t)n12[2];                              // (copied with the finder's counts when F1 + F2 ran)
-    s.patterns_do = patterns_do;
-    thin_starts(good, start_bit, src_len, s.starts, s.heavy);
+    // ---- candidates: the finder over a table of this one stream ---------------------------------------------------------
+    std::vector<std::vector<unsigned long long>> good(1);
+    FindOne one;
+    if (int rc = find_starts(ws, ss, good, {0}, sub, st, &one)) return rc;
+    if (one.no_room) return one.no_room;                  // (no scratch is this call's error, not a reason for the slow path)
+    if (s.left) return 0;                                 // (far more candidates than a deflate stream has)
+    // (SUBBLOCK goes on without candidates: a stream of fixed-code blocks is cut inside them)
+    if (one.n_f1 == 0 && !sub) return why("no candidate block starts, or far more than a deflate stream has");
+    // ---- the pass over this one stream ------------------------------------------------------------------------------
+    thin_starts(good[0], start_bit, src_len, s.starts, s.heavy);
     s.chain.record = t_index_sink != nullptr;
     size_t taken = 0;
     int launches = 0;
@@ -1375,96 +1424,8 @@ void inflate_large_reset_counters() {
 }
 }  // namespace zr
 
-// One finder pass over the streams `which` (indices into ss and good): the patterns alone, or F1 + F2 (and, `bytes`, every
-// stream's first two bytes).  Fills good[..] with each stream's survivors, sorted; when the lists cannot be had the streams
-// leave the device path.  One synchronisation (a second one when the list is longer than what comes back with the counts).
-static int round_find(Workspace *ws, std::vector<PassStream> &ss, std::vector<std::vector<unsigned long long>> &good,
-                      const std::vector<size_t> &which, bool patterns, bool bytes, hipStream_t st) {
-    const size_t ns = which.size();
-    if (!ns) return ZNG_ROCM_OK;
-    uint64_t total = 0;
-    for (size_t w : which) total += ss[w].src_len;
-    const uint64_t item_bytes = std::max<uint64_t>(4096, std::min<uint64_t>(65536, (total / 4096 + 4095) & ~4095ull));
-    std::vector<FindItemDev> items;
-    for (size_t k = 0; k < ns; ++k) {
-        const uint64_t len = ss[which[k]].src_len;
-        for (uint64_t lo = 0; lo < len; lo += item_bytes) items.push_back(FindItemDev{lo, std::min(lo + item_bytes, len), (uint32_t)k, 0u});
-    }
-    const uint32_t cap1 = (uint32_t)(total / 64 + 4096 * ns), cap2 = (uint32_t)(total / 512 + 4096 * ns);
-    const uint32_t first = (uint32_t)std::min<size_t>(cap2, 16384 + 64 * ns);
-    // streams | items | counts | first bytes on both sides; behind them the candidates (device), the first survivors (pinned)
-    TableLayout dl;
-    const size_t o_tab = dl.add(ns * sizeof(FindStreamDev)), o_items = dl.add(items.size() * sizeof(FindItemDev)), o_n = dl.add(64),
-                 o_b0 = dl.add(ns * 2);
-    TableLayout hl = dl;
-    const size_t o_cand = dl.add((size_t)cap1 * 8), o_good = dl.add((size_t)cap2 * 8), o_hgood = hl.add((size_t)first * 8);
-    uint8_t *fp = nullptr, *hp = nullptr;
-    auto out = [&](const char *reason) {
-        for (size_t w : which) ss[w].left = true;
-        return why(reason);
-    };
-    if (scratch_reserve(ws, kScrLargeCand, dl.bytes, false, (void **)&fp) != ZNG_ROCM_OK ||
-        scratch_reserve(ws, kScrLargeCandHost, hl.bytes, true, (void **)&hp) != ZNG_ROCM_OK)
-        return out("no room for the round's candidates");
-    FindStreamDev *d_tab = (FindStreamDev *)(fp + o_tab), *h_tab = (FindStreamDev *)(hp + o_tab);
-    FindItemDev *d_items = (FindItemDev *)(fp + o_items);
-    uint32_t *d_n = (uint32_t *)(fp + o_n), *n12 = (uint32_t *)(hp + o_n);
-    uint16_t *d_b0 = (uint16_t *)(fp + o_b0), *h_b0 = (uint16_t *)(hp + o_b0);
-    unsigned long long *d_cand = (unsigned long long *)(fp + o_cand), *d_good = (unsigned long long *)(fp + o_good);
-    unsigned long long *h_good = (unsigned long long *)(hp + o_hgood);
-    for (size_t k = 0; k < ns; ++k) h_tab[k] = FindStreamDev{ss[which[k]].d_src, ss[which[k]].src_len};
-    std::copy(items.begin(), items.end(), (FindItemDev *)(hp + o_items));
-    n12[0] = n12[1] = 0;
-    ZR_HIP(hipMemcpyAsync(fp, hp, o_n, hipMemcpyHostToDevice, st));              // streams | items
-    ZR_HIP(hipMemsetAsync(d_n, 0, 8, st));
-    if (patterns) {
-        hipLaunchKernelGGL(find_headers_table_kernel<true>, dim3((unsigned)items.size()), dim3(256), 0, st, d_tab, d_items, d_good, d_n + 1, cap2);
-        ZR_HIP(hipGetLastError());
-    } else {
-        hipLaunchKernelGGL(find_headers_table_kernel<false>, dim3((unsigned)items.size()), dim3(256), 0, st, d_tab, d_items, d_cand, d_n, cap1);
-        ZR_HIP(hipGetLastError());
-        hipLaunchKernelGGL(validate_headers_table_kernel, dim3(8192), dim3(kValLanes), 0, st, d_tab, d_cand, d_n, cap1, d_good, d_n + 1, cap2);
-        ZR_HIP(hipGetLastError());
-        if (bytes) {
-            hipLaunchKernelGGL(first_bytes_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, st, d_tab, (uint32_t)ns, d_b0);
-            ZR_HIP(hipGetLastError());
-            ZR_HIP(hipMemcpyAsync(h_b0, d_b0, ns * 2, hipMemcpyDeviceToHost, st));
-        }
-    }
-    ZR_HIP(hipMemcpyAsync(n12, d_n, 8, hipMemcpyDeviceToHost, st));
-    ZR_HIP(hipMemcpyAsync(h_good, d_good, (size_t)first * 8, hipMemcpyDeviceToHost, st));
-    ZR_HIP(hipStreamSynchronize(st));
-    if (n12[0] > cap1 || n12[1] > cap2) {
-        // One stream's payload can hold more places that pass for a block start than the whole round has room for (a stored
-        // block full of 00 00 ff ff).  That is that stream's trouble, not its neighbours': each half of the round on its own,
-        // down to the stream that has them -- which leaves, as it does in the one-stream call.
-        if (ns == 1) return out("far more candidates in the stream than a deflate stream has");
-        const std::vector<size_t> lower(which.begin(), which.begin() + ns / 2), upper(which.begin() + ns / 2, which.end());
-        if (int rc = round_find(ws, ss, good, lower, patterns, bytes, st)) return rc;
-        return round_find(ws, ss, good, upper, patterns, bytes, st);
-    }
-    const uint32_t n2 = n12[1];
-    std::vector<unsigned long long> rest;
-    if (n2 > first) {
-        rest.resize(n2 - first);
-        ZR_HIP(hipMemcpyAsync(rest.data(), d_good + first, (size_t)(n2 - first) * 8, hipMemcpyDeviceToHost, st));
-        ZR_HIP(hipStreamSynchronize(st));
-    }
-    for (size_t k = 0; k < ns; ++k) {
-        good[which[k]].clear();
-        if (bytes && !patterns) ss[which[k]].b0 = h_b0[k];
-    }
-    for (uint32_t i = 0; i < n2; ++i) {
-        const unsigned long long c = i < first ? h_good[i] : rest[i - first];
-        const size_t k = (size_t)((c & kFindTagMask) >> kFindTagShift);
-        if (k < ns) good[which[k]].push_back(c & ~kFindTagMask & ~(1ull << 63));
-    }
-    for (size_t w : which) std::sort(good[w].begin(), good[w].end(), by_bit);
-    return ZNG_ROCM_OK;
-}
-
-// One round: the jobs idx[0 .. *taken) (all of idx unless their parts together pass one launch's) through the table finder
-// and the pass.  Jobs done on the device have their output fields set; the others are appended to `host` (the caller
+// One round: the jobs idx[0 .. *taken) (all of idx unless their parts together pass one launch's) through the finder and
+// the pass.  Jobs done on the device have their output fields set; the others are appended to `host` (the caller
 // decodes them sequentially, as zng_rocm_inflate_large_ex_dev does it, behind the round's device work).
 // `counting`: pass_run's counting mode -- d_dst / dst_cap are not looked at, and `host` are the jobs to be sized whole.
 static int round_run(Workspace *ws, zng_rocm_inflate_large_job *jobs, const std::vector<size_t> &idx, bool sub, hipStream_t st,
@@ -1486,15 +1447,7 @@ static int round_run(Workspace *ws, zng_rocm_inflate_large_job *jobs, const std:
         else if (!counting) s.left = true;                // (the counting mode takes it as one part: pass_run)
     }
     // ---- candidates: the byte patterns for every stream; F1 + F2 for those they do not cut ---------------------------
-    if (int rc = round_find(ws, ss, good, scan, true, false, st)) return rc;
-    std::vector<size_t> full;
-    for (size_t k : scan) {
-        PassStream &s = ss[k];
-        if (s.left) continue;
-        s.patterns_do = good[k].size() <= patterns_first(s.src_len) && patterns_cut(good[k], 0, 8ull * s.src_len);
-        if (!s.patterns_do) full.push_back(k);
-    }
-    if (int rc = round_find(ws, ss, good, full, false, sub, st)) return rc;
+    if (int rc = find_starts(ws, ss, good, scan, sub, st)) return rc;
     for (size_t k : scan) {
         PassStream &s = ss[k];
         if (s.left) continue;

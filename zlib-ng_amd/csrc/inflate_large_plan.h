@@ -1,7 +1,7 @@
-// inflate_large_plan.h -- the host steps between the kernel launches of inflate_large.hip (pass_run, and the finders in front
-// of it).  Plain C++ over integers and the part tables, no HIP: every rule that decides what a valid result is -- which
-// candidates become starts, where guesses go, how large a slot is, where the tables lie in scratch, which parts run again,
-// which parts are genuine, how parts are grouped for the context chain and laid out in the symbol array -- lives here, and a
+// inflate_large_plan.h -- the host steps between the kernel launches of inflate_large.hip (pass_run, and the finder in front
+// of it).  Plain C++ over integers and the part tables, no HIP: every rule that decides what a valid result is -- how a
+// finder pass is cut into work items, how many survivors it has room for and whose they are, which candidates become
+// starts, where guesses go, how large a slot is, where the tables lie in scratch, which parts run again, which parts are genuine, how parts are grouped for the context chain and laid out in the symbol array -- lives here, and a
 // CPU test (tests/test_large_plan_cpu.py) drives them with hand-written tables.
 #pragma once
 #include <stddef.h>
@@ -98,6 +98,54 @@ inline bool large_length_ok(uint64_t src_len) { return src_len >= (128u << 10) &
 // ---- candidates -> starts ---------------------------------------------------------------------------------------------
 // a candidate is its bit position, bit 62 set for "a stored block" (light work)
 inline bool by_bit(unsigned long long x, unsigned long long y) { return (x & ~(1ull << 62)) < (y & ~(1ull << 62)); }
+
+// One finder pass over `ns` streams, stream k scanned over lens[k] bytes (one stream is a table of one).  The scan is cut
+// into work items, one workgroup each, that tile each stream in order.  About 4096 of them, whatever the pass's bytes:
+// that is 16 per CU and twice what the chip holds at once, so no CU is left with a share more (one 101 MB stream in 3529
+// items of 28 KiB ran F1 4 % longer than in 4096 of 24 KiB).  `share` is a 4096th of the pass's bytes within 4 .. 64 KiB; a
+// stream is cut into as few EQUAL items as stay within it; item_bytes, `share` in whole rounds of the pattern scan (4096
+// bytes), is the bound no item passes.  cap1 / cap2: room for the survivors of F1 and of F2 (or of the pattern pass) of ALL
+// the streams, a survivor per 64 and per 512 bytes and 4096 per stream -- starts are 2 KiB apart in the end; a pass with
+// more is no deflate data.  `first`: as many survivors as come back with the counts.
+struct FindPlan {
+    uint64_t item_bytes = 0, share = 0;
+    size_t   nitems = 0;
+    uint32_t cap1 = 0, cap2 = 0, first = 0;
+};
+inline FindPlan find_plan(const uint64_t *lens, size_t ns) {
+    FindPlan p;
+    uint64_t total = 0;
+    for (size_t k = 0; k < ns; ++k) total += lens[k];
+    p.item_bytes = std::max<uint64_t>(4096, std::min<uint64_t>(65536, (total / 4096 + 4095) & ~4095ull));
+    p.share = std::max<uint64_t>(4096, std::min<uint64_t>(p.item_bytes, (total + 4095) / 4096));
+    for (size_t k = 0; k < ns; ++k) p.nitems += (size_t)((lens[k] + p.share - 1) / p.share);
+    p.cap1 = (uint32_t)(total / 64 + 4096 * ns);
+    p.cap2 = (uint32_t)(total / 512 + 4096 * ns);
+    p.first = (uint32_t)std::min<size_t>(p.cap2, 16384 + 64 * ns);
+    return p;
+}
+// the plan's nitems work items, written where they go up from (the host prepares a pass while the device waits for it)
+inline void find_items(const uint64_t *lens, size_t ns, uint64_t share, FindItemDev *items) {
+    for (size_t k = 0; k < ns; ++k) {
+        const uint64_t n = (lens[k] + share - 1) / share, each = n ? (lens[k] + n - 1) / n : 0;
+        for (uint64_t i = 0; i < n; ++i) *items++ = FindItemDev{std::min(i * each, lens[k]), std::min((i + 1) * each, lens[k]), (uint32_t)k, 0u};
+    }
+}
+// The pass's survivors (two runs of the one list: what came back with the counts, and the rest) -> one list per stream,
+// sorted: a survivor goes by its tag, which is taken off together with the "behind a marker" bit 63 (bit 62, "a stored
+// block", stays); a tag that names no stream of the table is dropped.
+inline std::vector<std::vector<unsigned long long>> find_demux(const unsigned long long *a, size_t na, const unsigned long long *b,
+                                                               size_t nb, size_t ns) {
+    std::vector<std::vector<unsigned long long>> per(ns);
+    for (auto &list : per) list.reserve((na + nb) / ns + 1);                     // (one stream: the whole list, grown once)
+    for (size_t i = 0; i < na + nb; ++i) {
+        const unsigned long long c = i < na ? a[i] : b[i - na];
+        const size_t k = (size_t)((c & kFindTagMask) >> kFindTagShift);
+        if (k < ns) per[k].push_back(c & ~kFindTagMask & ~(1ull << 63));
+    }
+    for (auto &list : per) std::sort(list.begin(), list.end(), by_bit);
+    return per;
+}
 
 // as many of the pattern pass's survivors as come back with its counts; a longer list is not one the patterns cut
 inline uint32_t patterns_first(size_t scan_len) { return (uint32_t)std::min<size_t>(scan_len / 512 + 4096, 16384u); }
