@@ -237,7 +237,10 @@ uint32_t zng_rocm_chunksize(void);
  *   in:  device; any alignment; `dict_len` (<= 32768) bytes of history sit directly in front of it
  *        (in - dict_len .. in): they prime the hash as deflateSetDictionary does (deflate.c:456-531) and
  *        matches may reach back into them, but they are neither emitted nor part of the checksum
- *   out: device, 4-byte aligned, out_cap >= zng_rocm_deflate_quick_bound(in_len)
+ *   out: device, 4-byte aligned, out_cap >= zng_rocm_deflate_quick_bound(in_len).  out_cap is 32 bits wide, so ONE stream is at
+ *        most 3 817 748 681 bytes (3.55 GiB), the largest in_len whose bound is at most 0xffffffff; a longer one is
+ *        ZNG_ROCM_EINVAL.  Up to there a stream's output bits (up to 8 * 2^32) and its check row are exact
+ *        (csrc/deflate_quick_plan.h)
  *   flags: 0 = the block is the stream's last (BFINAL = 1: what one deflate(Z_FINISH) call emits);
  *        ZNG_ROCM_BLOCK_NOT_FINAL = BFINAL 0; with ZNG_ROCM_BLOCK_SYNC_FLUSH an empty stored block follows
  *        (00 00 ff ff after the padding bits: the Z_SYNC_FLUSH marker, deflate.c:1064-1076), so the job's

@@ -124,6 +124,82 @@ def test_many_tiny_streams_and_one_long(mods):
     assert (int(batch.results.cpu()[0, 1]) & 0xffffffff) == zlib.adler32(long.tobytes())
 
 
+def _wave_sums_of_a_run(v, n):
+    """deflate_quick_kernel's sum B = sum of (n - p) * byte over the positions of each of its four waves, for n bytes of value v:
+    position p goes to lane p % 256, wave (p % 256) // 64 -- in unbounded integers"""
+    sums = [0] * 4
+    for t in range(256):
+        count = (n - 1 - t) // 256 + 1 if t < n else 0
+        sums[t // 64] += v * (count * n - (count * t + 256 * count * (count - 1) // 2))
+    return sums
+
+
+def test_one_stream_across_the_cursor_wrap_and_one_across_the_adler_edge(mods):
+    """One launch, four jobs, the two large ones side by side -- the smallest inputs at which the two quantities of
+    deflate_quick_plan.h leave 32 / 64 bits (a byte is at most 255, a literal costs at most 9 bits):
+      job 1   768 MiB of 0xff: the plain sum of the Adler-32 row over each wave's 64 lanes is above 2^64 (asserted on the input,
+              before the launch), so the row is right only if every lane is reduced before lanes are added
+      job 2   ceil(2^32 / 9) bytes + 16 MiB of bytes uniform in 144..255 (nine-bit literals; a four-byte repeat has probability
+              112^-4 per position, about three matches in the stream): more than 2^32 + 2^27 output bits, so the bit cursor wraps
+              and some thousand flushes follow the wrap
+      jobs 0, 3   small neighbours in front and behind; the destination is filled with 0xA5 and every slot must be untouched
+              behind its stream's last word.
+    CPython's zlib is the reader.  Measured on an MI355X: the launch takes 8.03 s (the 40 MiB + 3 stream of the test above, alone:
+    406 ms, which scales to 7.8 s for 768 MiB); the whole test 14 s, most of the rest CPython inflating 1.2 GiB."""
+    zr, dfl, inf = mods
+    torch = torch_mod()
+    mix = _streams()[-1]
+    assert len(mix) == 4096 + 3
+    n_ff = 768 << 20
+    assert all(s >= 1 << 64 for s in _wave_sums_of_a_run(255, n_ff))
+    n_lit = (-(-(1 << 32) // 9) + (16 << 20) + 15) & ~15
+    lit = np.random.default_rng(0x51C0).integers(144, 256, size=n_lit, dtype=np.uint8)
+    small = [mix, b"a" * 259]
+    lens = [len(mix), n_ff, n_lit, 259]
+    offs, pos = [], 0
+    for v in lens:
+        offs.append(pos)
+        pos += (v + 15) & ~15
+    src = torch.empty(pos + 16, dtype=torch.uint8, device="cuda")
+    src[offs[0]:offs[0] + lens[0]] = torch.from_numpy(np.frombuffer(mix, dtype=np.uint8).copy()).cuda()
+    src[offs[1]:offs[1] + n_ff] = 0xff
+    src[offs[2]:offs[2] + n_lit] = torch.from_numpy(lit).cuda()
+    src[offs[3]:offs[3] + 259] = ord("a")
+    batch = dfl.QuickBatch(src, offs, lens)
+    batch.dst.fill_(0xA5)
+    torch.cuda.synchronize()
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    batch.run()
+    t1.record()
+    torch.cuda.synchronize()
+    print("four-job launch: %.1f ms" % t0.elapsed_time(t1))
+    res = batch.results.cpu().numpy().astype(np.int64) & 0xffffffff
+    clens = [int(res[i, 0]) for i in range(4)]
+    print("compressed lengths", clens, "bounds", batch.bounds)
+    for i in range(4):
+        assert clens[i] <= batch.bounds[i], i
+        lo, hi = batch.out_off[i] + ((clens[i] + 3) & ~3), batch.out_off[i] + batch.bounds[i]
+        assert bool((batch.dst[lo:hi] == 0xA5).all()), i
+    assert 8 * clens[2] >= (1 << 32) + (1 << 27)
+
+    def inflate(i):
+        d = zlib.decompressobj(-15)
+        out = d.decompress(batch.dst[batch.out_off[i]:batch.out_off[i] + clens[i]].cpu().numpy().tobytes())
+        assert d.eof and d.unused_data == b"", i
+        return out
+    for i, s in ((0, small[0]), (3, small[1])):
+        assert inflate(i) == s, i
+        assert int(res[i, 1]) == zlib.adler32(s), i
+    out = inflate(1)
+    assert len(out) == n_ff and out.count(b"\xff") == n_ff
+    assert int(res[1, 1]) == zlib.adler32(out)
+    del out
+    out = inflate(2)
+    assert len(out) == n_lit and np.array_equal(np.frombuffer(out, dtype=np.uint8), lit)
+    assert int(res[2, 1]) == zlib.adler32(out)
+
+
 def test_two_batches_on_two_streams_from_two_host_threads(mods):
     """Independent streams from independent threads (zlib-ng.h.in:157-159; test/test_deflate_concurrency.cc:73-170
     drives two at once): two QuickBatch-es enqueued concurrently from two host threads on two HIP streams must not

@@ -37,8 +37,8 @@
         }
     }
 
-    uint32_t cursor = 3;                 // bits placed so far (uniform over the workgroup)
-    uint32_t flushed = 0;                // whole words already written to `out`
+    uint32_t cursor = 3;                 // bits placed so far, modulo 2^32 (uniform over the workgroup)
+    uint32_t flushed = 0;                // whole words already written to `out`: the true count (deflate_quick_plan.h)
     uint32_t pend_code = 0, pend_nb = 0, pend_pre = 0;     // this lane's token of the previous batch, not yet placed
     bool have_pending = false;
     unsigned long long accA = 0, accB = 0;                 // Adler-32, linear form: B += (n - pos) * byte
@@ -56,17 +56,18 @@
         }
         cursor += wb.x + wb.y + wb.z + wb.w;
     };
-    // stream out complete words; everything below `cursor` was ORed before the last barrier
+    // stream out complete words (quick_flush_words, deflate_quick_plan.h); everything below `cursor` was ORed before the last barrier
     auto flush = [&](uint32_t keep_below) {
-        const uint32_t full = cursor >> 5;
-        if (full - flushed >= keep_below) {
-            const uint32_t cnt = keep_below > 1 ? ((full - flushed) & ~31u) : full - flushed;
-            for (uint32_t i = (uint32_t)t; i < cnt; i += 256) {
-                const uint32_t slot = (flushed + i) & (kRingWords - 1u);
-                __builtin_nontemporal_store(sh.ring[slot], outw + flushed + i);
+        const uint32_t bits = quick_pending_bits(cursor, flushed);
+        if (quick_flush_due(bits, keep_below)) {
+            const uint32_t cnt = quick_flush_count(bits, keep_below);
+            const uint32_t end = flushed + cnt;                  // true word indices: below 2^30
+            for (uint32_t w = flushed + (uint32_t)t; w < end; w += 256) {
+                const uint32_t slot = w & (kRingWords - 1u);
+                __builtin_nontemporal_store(sh.ring[slot], outw + w);
                 sh.ring[slot] = 0;
             }
-            flushed += cnt;
+            flushed = end;
         }
     };
 
@@ -115,39 +116,37 @@
     __syncthreads();
     flush(1);                                                // every complete word
 
-    // end-of-block code 256 = seven 0 bits (zng_emit_end_block, trees_emit.h:169-180), then pad to a byte
+    // Adler-32: every lane reduced before lanes are added (quick_adler_lane: a wave's plain sum passes 2^64 from 726 MiB of 0xff on)
+    uint32_t redA = quick_adler_lane(accA), redB = quick_adler_lane(accB);
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) {
-        accA += __shfl_xor(accA, m, 64);
-        accB += __shfl_xor(accB, m, 64);
+        redA += (uint32_t)__shfl_xor((int)redA, m, 64);
+        redB += (uint32_t)__shfl_xor((int)redB, m, 64);
     }
     if (lane == 0) {
-        sh.red_a[wave] = accA % kAdlerBase;
-        sh.red_b[wave] = accB % kAdlerBase;
+        sh.red_a[wave] = redA;
+        sh.red_b[wave] = redB;
     }
     __syncthreads();
+    // end-of-block code 256 = seven 0 bits (zng_emit_end_block, trees_emit.h:169-180), then pad to a byte
     if (t == 0) {
         uint8_t *outb = job.out;
-        uint32_t cbits = (cursor & 31u) + 7u;                // the partial word + EOB
-        uint32_t cw = sh.ring[(cursor >> 5) & (kRingWords - 1u)];
-        uint32_t wbase = flushed;                            // == cursor >> 5
-        if (cbits >= 32) {
-            outw[wbase++] = cw;
-            cw = 0;
-            cbits -= 32;
-        }
-        uint32_t bytes = wbase * 4u;
         const bool sync = !final_block && (job.flags & ZNG_ROCM_BLOCK_SYNC_FLUSH) != 0;
-        if (sync) cbits += 3;                                // header of an empty stored block: BFINAL = 0, BTYPE = 00
-        for (uint32_t k = 0; k < (cbits + 7u) / 8u; ++k) outb[bytes++] = (uint8_t)((unsigned long long)cw >> (8 * k));   // up to 34 bits
-        if (sync) {                                          // ... byte aligned, LEN = 0, NLEN = 0xffff: what Z_SYNC_FLUSH
+        const QuickTail tail = quick_tail(cursor, flushed, sync);    // tail.word == flushed: flush(1) wrote every complete word
+        uint32_t cw = sh.ring[tail.word & (kRingWords - 1u)];        // the partial word + EOB
+        if (tail.spill) {
+            outw[tail.word] = cw;
+            cw = 0;
+        }
+        uint32_t bytes = tail.first;
+        for (uint32_t k = 0; k < tail.nbytes; ++k) outb[bytes++] = (uint8_t)((unsigned long long)cw >> (8 * k));   // up to 34 bits
+        if (sync) {                                          // header of an empty stored block (BFINAL = 0, BTYPE = 00: three 0 bits),
+            outb[bytes++] = 0x00;                            // byte aligned, LEN = 0, NLEN = 0xffff: what Z_SYNC_FLUSH
             outb[bytes++] = 0x00;                            // appends (deflate.c:1064-1076, zng_tr_stored_block)
-            outb[bytes++] = 0x00;
             outb[bytes++] = 0xff;
             outb[bytes++] = 0xff;
         }
-        const unsigned long long A = (sh.red_a[0] + sh.red_a[1] + sh.red_a[2] + sh.red_a[3]) % kAdlerBase;
-        const unsigned long long B = (sh.red_b[0] + sh.red_b[1] + sh.red_b[2] + sh.red_b[3]) % kAdlerBase;
-        results[2 * blockIdx.x] = bytes;
-        results[2 * blockIdx.x + 1] = (uint32_t)(((1 + A) % kAdlerBase) | ((((unsigned long long)(n - start) + B) % kAdlerBase) << 16));
+        results[2 * blockIdx.x] = tail.bytes;
+        results[2 * blockIdx.x + 1] = quick_adler_row(sh.red_a[0] + sh.red_a[1] + sh.red_a[2] + sh.red_a[3],
+                                                      sh.red_b[0] + sh.red_b[1] + sh.red_b[2] + sh.red_b[3], n - start);
     }

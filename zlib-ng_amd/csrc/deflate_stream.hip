@@ -21,6 +21,7 @@
 #include "context.h"
 #include "deflate_dev.h"
 #include "deflate_lz.h"
+#include "deflate_quick_plan.h"
 #include "dict_dev.h"
 
 #include <stdlib.h>
@@ -85,12 +86,7 @@ __device__ __forceinline__ void static_match(uint32_t len, uint32_t dist, uint32
     nb += deb;
 }
 
-// The bit ring: output bit b of the stream lives in ring[(b / 32) & (kRingWords - 1u)] while it is being assembled.  A batch
-// produces at most 256 nine-bit literals = 72 words; words are streamed out once 128 are complete, 32 (one 128-byte
-// line) at a time, so fewer than 128 + 72 + 32 < 512 are ever pending.
-constexpr uint32_t kRingWords = 512;       // 2 KiB: with the 16 KiB head table still eight workgroups per CU
-constexpr uint32_t kFlushWords = 128;
-
+// The bit ring (kRingWords, kFlushWords), the rule that streams it out, the Adler-32 fold and the job check: deflate_quick_plan.h
 struct QuickShared {
     LzShared<kQuickHashBits> lz;
     uint32_t ring[kRingWords];
@@ -169,7 +165,7 @@ void deflate_quick_wave_kernel(const StreamJobDev *__restrict__ jobs, uint32_t *
     }
 
     uint32_t cover = start;              // first byte not yet produced (uniform)
-    uint32_t cursor = 3, flushed = 0;    // bits placed / whole words written (uniform)
+    uint32_t cursor = 3, flushed = 0;    // bits placed, modulo 2^32 / whole words written, true (uniform; deflate_quick_plan.h)
     unsigned long long accA = 0, accB = 0;
 
     // ---- software pipeline: own bytes two steps ahead, insertion + candidate gather one step ahead.
@@ -297,16 +293,16 @@ void deflate_quick_wave_kernel(const StreamJobDev *__restrict__ jobs, uint32_t *
                 atomicOr(&sh.ring[(word + 1) & (kRingWords - 1u)], (uint32_t)(wide >> 32));
             }
             cursor += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-            const uint32_t full = cursor >> 5;
-            if (full - flushed >= kFlushWords) {
+            const uint32_t bits = quick_pending_bits(cursor, flushed);
+            if (quick_flush_due(bits, kFlushWords)) {
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                const uint32_t cnt = (full - flushed) & ~31u;
-                for (uint32_t i = (uint32_t)lane; i < cnt; i += 64u) {
-                    const uint32_t slot = (flushed + i) & (kRingWords - 1u);
-                    __builtin_nontemporal_store(sh.ring[slot], outw + flushed + i);
+                const uint32_t end = flushed + quick_flush_count(bits, kFlushWords);     // true word indices: below 2^30
+                for (uint32_t w = flushed + (uint32_t)lane; w < end; w += 64u) {
+                    const uint32_t slot = w & (kRingWords - 1u);
+                    __builtin_nontemporal_store(sh.ring[slot], outw + w);
                     sh.ring[slot] = 0;
                 }
-                flushed += cnt;
+                flushed = end;
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             }
         }
@@ -341,48 +337,40 @@ void deflate_quick_wave_kernel(const StreamJobDev *__restrict__ jobs, uint32_t *
     // ---- everything that is left in the ring, the end-of-block code, the optional sync marker
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     {
-        const uint32_t full = cursor >> 5;
-        for (uint32_t i = flushed + (uint32_t)lane; i < full; i += 64u) {
-            __builtin_nontemporal_store(sh.ring[i & (kRingWords - 1u)], outw + i);
+        const uint32_t end = flushed + quick_flush_words(cursor, flushed, 1u);       // every complete word
+        for (uint32_t w = flushed + (uint32_t)lane; w < end; w += 64u) {
+            __builtin_nontemporal_store(sh.ring[w & (kRingWords - 1u)], outw + w);
         }
-        flushed = full;
+        flushed = end;
     }
+    // Adler-32: every lane reduced before lanes are added (quick_adler_lane)
+    uint32_t redA = quick_adler_lane(accA), redB = quick_adler_lane(accB);
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) {
-        accA += __shfl_xor(accA, m, 64);
-        accB += __shfl_xor(accB, m, 64);
+        redA += (uint32_t)__shfl_xor((int)redA, m, 64);
+        redB += (uint32_t)__shfl_xor((int)redB, m, 64);
     }
     if (lane == 0) {
         uint8_t *outb = job.out;
-        uint32_t cbits = (cursor & 31u) + 7u;                // the partial word + EOB (seven 0 bits, trees_emit.h:169-180)
-        uint32_t cw = sh.ring[(cursor >> 5) & (kRingWords - 1u)];
-        uint32_t wbase = flushed;
-        if (cbits >= 32) {
-            outw[wbase++] = cw;
-            cw = 0;
-            cbits -= 32;
-        }
-        uint32_t bytes = wbase * 4u;
         const bool sync = !final_block && (job.flags & ZNG_ROCM_BLOCK_SYNC_FLUSH) != 0;
-        if (sync) cbits += 3;                                // header of an empty stored block: BFINAL = 0, BTYPE = 00
-        for (uint32_t k = 0; k < (cbits + 7u) / 8u; ++k) outb[bytes++] = (uint8_t)((unsigned long long)cw >> (8 * k));
-        if (sync) {                                          // deflate.c:1064-1076
+        const QuickTail tail = quick_tail(cursor, flushed, sync);    // tail.word == flushed
+        uint32_t cw = sh.ring[tail.word & (kRingWords - 1u)];        // the partial word + EOB (seven 0 bits, trees_emit.h:169-180)
+        if (tail.spill) {
+            outw[tail.word] = cw;
+            cw = 0;
+        }
+        uint32_t bytes = tail.first;
+        for (uint32_t k = 0; k < tail.nbytes; ++k) outb[bytes++] = (uint8_t)((unsigned long long)cw >> (8 * k));
+        if (sync) {                                          // the empty stored block behind its 3 header bits, deflate.c:1064-1076
             outb[bytes++] = 0x00;
             outb[bytes++] = 0x00;
             outb[bytes++] = 0xff;
             outb[bytes++] = 0xff;
         }
-        const unsigned long long A = accA % kAdlerBase, B = accB % kAdlerBase;
-        results[2 * blockIdx.x] = bytes;
-        results[2 * blockIdx.x + 1] = (uint32_t)(((1 + A) % kAdlerBase) | ((((unsigned long long)(n - start) + B) % kAdlerBase) << 16));
+        results[2 * blockIdx.x] = tail.bytes;
+        results[2 * blockIdx.x + 1] = quick_adler_row(redA, redB, n - start);
     }
 }
-
-}  // namespace zr
-
-extern "C" size_t zng_rocm_deflate_quick_bound(size_t source_len);
-
-namespace zr {
 
 int launch_deflate_quick_dict(const zng_rocm_stream_job *jobs, size_t njobs, uint32_t *d_results, const zng_rocm_dict *dict,
                               hipStream_t st) {
@@ -397,12 +385,9 @@ int launch_deflate_quick_dict(const zng_rocm_stream_job *jobs, size_t njobs, uin
     const uint32_t W = dict->window;
     for (size_t i = 0; i < njobs; ++i) {
         const zng_rocm_stream_job &j = jobs[i];
-        if (!j.out || (j.in_len && !j.in) || ((uintptr_t)j.out & 3) || j.out_cap < zng_rocm_deflate_quick_bound(j.in_len) ||
-            j.dict_len || (uint64_t)j.in_len + W > 0xffffffffull ||
-            (j.flags & ~(uint32_t)(ZNG_ROCM_BLOCK_NOT_FINAL | ZNG_ROCM_BLOCK_SYNC_FLUSH))) {
-            set_error("job %zu: out must be 4-byte aligned with out_cap >= the bound, dict_len 0 (the history is the dictionary "
-                      "object's), known flags, and window + plaintext below 4 GiB", i);
-            return ZNG_ROCM_EINVAL;
+        if (int rc = quick_job_check(j, true, W)) {          // dict_len 0: the history is the dictionary object's
+            set_error(kQuickJobRule, i);
+            return rc;
         }
         // position W + k names plaintext byte k: the address of "position 0" is never read
         h_jobs[i] = StreamJobDev{(const uint8_t *)((uintptr_t)j.in - W), j.out, j.in_len + W, j.out_cap, W, j.flags};
@@ -422,11 +407,7 @@ using namespace zr;
 extern "C" {
 
 size_t zng_rocm_deflate_quick_bound(size_t source_len) {
-    // 3 header bits + at most 9 bits per input byte (a match of >= 4 bytes costs <= 31 bits) + 7 EOB bits,
-    // cf. DEFLATE_QUICK_OVERHEAD / DEFLATE_BLOCK_OVERHEAD (zutil.h:71-79, deflate.c:773-777); rounded so that
-    // consecutive streams stay 16-byte aligned.
-    size_t b = source_len + ((source_len + 7) >> 3) + 8 + 5;          // + the sync-flush terminator of a non-final block
-    return (b + 15) & ~(size_t)15;
+    return (size_t)quick_bound(source_len);                  // deflate_quick_plan.h
 }
 
 int zng_rocm_deflate_quick_dev(const zng_rocm_stream_job *jobs, size_t njobs, uint32_t *d_results, void *stream) {
@@ -450,14 +431,9 @@ int zng_rocm_deflate_quick_dev(const zng_rocm_stream_job *jobs, size_t njobs, ui
     if (int rc = scratch_reserve(ws, kScrQuickJobsHost, njobs * sizeof(StreamJobDev), true, (void **)&h_jobs)) return rc;
     for (size_t i = 0; i < njobs; ++i) {
         const zng_rocm_stream_job &j = jobs[i];
-        if (!j.out || (j.in_len && !j.in) || ((uintptr_t)j.out & 3) || j.out_cap < zng_rocm_deflate_quick_bound(j.in_len)) {
-            set_error("job %zu: out must be 4-byte aligned and out_cap >= zng_rocm_deflate_quick_bound(in_len)", i);
-            return ZNG_ROCM_EINVAL;
-        }
-        if (j.dict_len > 32768u || (uint64_t)j.in_len + j.dict_len > 0xffffffffull || (j.dict_len && !j.in) ||
-            (j.flags & ~(uint32_t)(ZNG_ROCM_BLOCK_NOT_FINAL | ZNG_ROCM_BLOCK_SYNC_FLUSH))) {
-            set_error("job %zu: dict_len above 32768, unknown flags, or dictionary + plaintext of 4 GiB and more", i);
-            return ZNG_ROCM_EINVAL;
+        if (int rc = quick_job_check(j, false, 0u)) {
+            set_error(kQuickJobRule, i);
+            return rc;
         }
         h_jobs[i] = StreamJobDev{j.in - j.dict_len, j.out, j.in_len + j.dict_len, j.out_cap, j.dict_len, j.flags};
     }
