@@ -277,7 +277,11 @@ int    zng_rocm_deflate_quick_dev(const zng_rocm_stream_job *jobs, size_t njobs,
  * -5 (Z_BUF_ERROR).
  * zng_rocm_deflate_block_dev is the same for one BLOCK of a longer stream: `dict_len` (<= 32768) bytes of history
  * in front of d_in prime the first segment, and `flags` (ZNG_ROCM_BLOCK_*, above) say whether the stream ends
- * here; a non-final block always ends byte aligned behind an empty stored block. */
+ * here; a non-final block always ends byte aligned behind an empty stored block.
+ * d_in and d_out: no alignment is asked of either, here and in the async, streams, strategy and window forms below (the
+ * blocks are built in 4-byte aligned scratch of the library's own and packed into d_out by bytes; level 0 writes its headers
+ * and payload with stores that take any address).  Of d_in, only [d_in - dict_len, d_in + in_len) is read; no byte outside
+ * [d_out, d_out + out_cap) is written. */
 size_t zng_rocm_deflate_bound(size_t source_len);
 int    zng_rocm_deflate_dev(int level, const uint8_t *d_in, size_t in_len, uint8_t *d_out, size_t out_cap,
                             size_t *out_len, void *stream);

@@ -523,8 +523,9 @@ void emit_dynamic_kernel(const BlkJob *__restrict__ jobs, const unsigned long lo
         const uint32_t p0 = base + (uint32_t)t * kDynPer;
         uint32_t c1[kDynPer], n1[kDynPer], c2[kDynPer], n2[kDynPer];
         uint32_t mine = 0;
-        // this lane's 16 input bytes in one (unaligned) dwordx4 instead of up to 16 byte loads; bytes beyond the end of
-        // the stream are never looked at (p < hi below), the slack after the last segment is the caller's 16 bytes
+        // this lane's 16 input bytes in one (unaligned) dwordx4 instead of up to 16 byte loads, at any address: the load is
+        // issued only where all 16 lie in front of `hi`, the lane that straddles it takes its bytes one by one -- nothing at
+        // or behind the stream's last byte is read (zng_rocm.h asks the caller for no slack and no alignment)
         uint32_t rw[4] = {0u, 0u, 0u, 0u};
         if (p0 + 16u <= hi) {
             const u32x4_unaligned raw = load_u128(in + p0);

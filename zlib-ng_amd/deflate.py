@@ -24,9 +24,10 @@ def deflate_quick_bound(n):
 class QuickBatch:
     """A fixed set of streams laid out in two device tensors.
 
-    src:  uint8 CUDA tensor holding the streams; stream i = src[in_off[i] : in_off[i] + in_len[i]],
-          every in_off a multiple of 16 and the tensor padded to a multiple of 16.
-    The compressed streams land in `dst` at out_off[i] (bound-sized slots); `results` is an int32
+    src:  uint8 CUDA tensor holding the streams; stream i = src[in_off[i] : in_off[i] + in_len[i]] at any
+          in_off (no alignment, no padding behind a stream: zng_rocm.h), its dict_len[i] bytes of history
+          directly in front of it.  What else lies around a stream is never looked at.
+    The compressed streams land in `dst` at out_off[i] (bound-sized slots, 4-byte aligned); `results` is an int32
     CUDA tensor [n, 2] = {compressed length, adler32 of the input}.
     """
 
