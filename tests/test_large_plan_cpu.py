@@ -29,7 +29,24 @@ and `segs` arguments), and so are the finder's host rules (`finder`):
                the links from the stream's first part meets, "end" when the chain ends without one, "broken" otherwise
   symbol array streams one behind the other, each behind a gap of 32768 symbols, the first at 32768; a copy's dst is re-based
                to the array, gstart / first name the first copy of its segment; a segment's bytes end where the next segment
-               of the same stream begins, the last one's where the stream's do"""
+               of the same stream begins, the last one's where the stream's do
+
+And the rules the pieces loop steps by (`pieces`; tools/sanitize_inflate_large_plan.sh runs the driver's `self` sweep of them
+under ASan + UBSan):
+
+  next piece   [bit >> 3, end): p bytes, the stream's end when that is nearer, and a quarter of p in front of the stream's end
+               when less than a quarter would be left; the pass's buffer begins at base = the piece's first byte -- the byte
+               of the dynamic header H, for a key of H + 2 with H in front -- rounded down to 256; the pass counts bits from
+               there: start_bit = bit - 8 base, scan_lo = (bit >> 3) - base, key0 = key - 8 base for a key of 2 and more
+  after a pass not stopped: done, in_used = base + used.  Stopped: bit and a key of 2 and more go back by + 8 base, fin is the
+               chain's, p is piece_bytes again, and a key of 0 moves the anchor (abit, aout) to (bit, produced)
+  halving      to p / 2 while that is at least 4 MiB (kPieceMin)
+  history      the last min(32768, pos + window_len) bytes in front of output position pos: in the output when pos has them
+               all; the window as it stands at pos 0; else the window's last (that - pos) bytes and then the pos delivered
+  sequential   from byte a0 = abit >> 3, bit sb = abit & 7: max(2 p, (bit >> 3) - a0 + p) bytes, doubled while the blocks form
+               says 0 with its end bit still sb and input is left; its answer stands on 1, on 0 with the end bit moved and on
+               -4, anything else is decoded again in the stream form; behind complete blocks up to bit eb the state is
+               bit = 8 a0 + eb, key 0, fin -1, the anchor there, p = piece_bytes"""
 import os
 import subprocess
 import tempfile
@@ -350,3 +367,148 @@ def test_symbol_tables_of_streams_one_behind_the_other(driver):
     assert got["seg_dst"] == [7000000, 7050000, 9000000]           # its own destination
     assert got["seg_end"] == [82768, 132768, v2 + 40000]
     assert got["v_end"] == [v2 + 40000]
+
+
+# ---- the pieces loop's rules ------------------------------------------------------------------------------------------------
+PIECE_MIN = 4 * MiB                               # kPieceMin
+IN_DST, WINDOW, SPLICED = 0, 1, 2                 # PieceHistory::Where
+
+
+def pieces(exe, op, words):
+    """-> the numbers of every output line of the driver's `pieces` operation `op`, in order"""
+    out = subprocess.run([exe, "pieces"], input=" ".join(str(w) for w in [op] + list(words)), capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stderr
+    return [[int(x) for x in ln.split()[1:]] for ln in out.stdout.strip("\n").split("\n")]
+
+
+def state(bit=0, key=0, fin=-1, produced=0, abit=0, aout=0, p=PIECE_MIN):
+    return [bit, key, fin, produced, abit, aout, p]
+
+
+def next_piece(exe, st, src_len, piece_bytes=PIECE_MIN):
+    """-> dict of piece_next's answer"""
+    (any_, end, base, start_bit, scan_lo, key0), (fin0,), (last, q) = pieces(exe, "next", st + [src_len, piece_bytes])
+    return dict(any=any_, end=end, base=base, start_bit=start_bit, scan_lo=scan_lo, key0=key0, fin0=fin0, last=last, q=q)
+
+
+@pytest.mark.parametrize("bit, p, src_len, end, last", [
+    (0, PIECE_MIN, 300000, 300000, 1),                                    # a stream shorter than one piece
+    (0, PIECE_MIN, PIECE_MIN, PIECE_MIN, 1),                              # exactly one piece
+    (0, PIECE_MIN, PIECE_MIN + MiB, PIECE_MIN, 0),                        # a tail of exactly a quarter piece: not shortened
+    (0, PIECE_MIN, PIECE_MIN + MiB - 1, PIECE_MIN - 1, 0),                # one byte less: a quarter piece is left behind
+    (8 * 1000 + 3, PIECE_MIN, 1000 + PIECE_MIN + MiB - 1, 1000 + PIECE_MIN - 1, 0),       # the same from byte 1000
+    (0, PIECE_MIN, PIECE_MIN + 1, PIECE_MIN + 1 - MiB, 0),                # a tail of one byte
+    (8 * PIECE_MIN, PIECE_MIN, PIECE_MIN + 5, PIECE_MIN + 5, 1),          # the last piece
+    (0, 2 * MiB, 2 * MiB + MiB // 2 - 1, 2 * MiB - 1, 0),                 # a halved piece: a quarter of ITS size
+])
+def test_where_a_piece_ends(driver, bit, p, src_len, end, last):
+    got = next_piece(driver, state(bit=bit, p=p), src_len, piece_bytes=2 * PIECE_MIN)
+    assert (got["any"], got["end"], got["last"]) == (1, end, last)
+    assert got["end"] > bit >> 3                                          # never in front of its start
+    assert got["q"] == 2 * PIECE_MIN and got["fin0"] == -1                # the caps go by the call's piece size, not by p
+
+
+def test_no_piece_behind_the_last_byte(driver):
+    assert next_piece(driver, state(bit=8 * 5000), 5000)["any"] == 0
+    assert next_piece(driver, state(bit=8 * 5000 + 7), 5001)["any"] == 1
+
+
+@pytest.mark.parametrize("bit, key, base, scan_lo, start_bit, key0", [
+    (8003, 0, 768, 232, 8003 - 6144, 0),                                  # byte 1000 is no multiple of 256: base 768
+    (8003, 1, 768, 232, 1859, 1),                                         # keys 0 and 1 are no positions: as they are
+    # H = bit 1 of byte 99000, 1000 bytes in front of the piece's byte 100000: base = 99000 & ~255 = 98816, 8 base = 790528
+    (800005, 792001 + 2, 98816, 1184, 800005 - 790528, 792003 - 790528),
+    # H = bit 7 of byte 99990, 10 bytes in front: base = 99840, 8 base = 798720
+    (800005, 799927 + 2, 99840, 160, 800005 - 798720, 799929 - 798720),
+    # H in the piece's first byte itself (bit 1 of byte 100000; the start is bit 5)
+    (800005, 800001 + 2, 99840, 160, 1285, 800003 - 798720),
+])
+def test_where_the_pass_buffer_begins_and_what_is_rebased(driver, bit, key, base, scan_lo, start_bit, key0):
+    st = state(bit=bit, key=key, fin=1, produced=5000, abit=4000, aout=700)
+    got = next_piece(driver, st, 10 * MiB)
+    assert (got["base"], got["scan_lo"], got["start_bit"], got["key0"], got["fin0"]) == (base, scan_lo, start_bit, key0, 1)
+    assert got["scan_lo"] + got["base"] == bit >> 3 and got["base"] % 256 == 0
+    if key >= 2:
+        assert (key0 - 2) >> 3 == ((key - 2) >> 3) - base                 # the header lies in the buffer, at its own byte
+    # a pass that stops at its own first start with its own key hands back the bit and the key that went in
+    step, after = pieces(driver, "pass", st + [10 * MiB, PIECE_MIN, 1, start_bit, key0, 1, 0, 0])
+    assert step == [0, 0, 1 if key == 0 else 0]
+    assert after[:3] == [bit, key, 1]
+
+
+def test_the_state_behind_a_pass(driver):
+    # the piece begins at bit 5 of byte 100000 inside the dynamic block at bit 792001: base 98816 (above); p had been halved
+    st = state(bit=800005, key=792003, fin=1, produced=5000, abit=700000, aout=4000, p=2 * MiB)
+    run = lambda *said: pieces(driver, "pass", st + [10 * MiB, PIECE_MIN] + list(said))
+    # stopped at a block start, bit 20000 of the buffer, behind 7000 bytes: the anchor moves there
+    assert run(1, 20000, 0, -1, 7000, 0) == [[0, 0, 1], [810528, 0, -1, 12000, 810528, 12000, PIECE_MIN]]
+    # stopped inside a fixed-code block whose BFINAL the chain knows: the anchor stays, fin is carried
+    assert run(1, 20000, 1, 1, 7000, 0) == [[0, 0, 0], [810528, 1, 1, 12000, 700000, 4000, PIECE_MIN]]
+    # stopped inside the dynamic block at bit 15000 of the buffer: its key goes back by 8 base
+    assert run(1, 20000, 15002, 0, 7000, 0) == [[0, 0, 0], [810528, 15002 + 790528, 0, 12000, 700000, 4000, PIECE_MIN]]
+    # not stopped: the stream ended 123456 bytes into the buffer
+    step, after = run(0, 0, 0, -1, 7000, 123456)
+    assert step == [1, 98816 + 123456, 0] and after[3] == 12000
+
+
+def test_halving_stops_at_the_least_piece(driver):
+    assert pieces(driver, "halve", [2 * PIECE_MIN]) == [[1, PIECE_MIN]]
+    assert pieces(driver, "halve", [2 * PIECE_MIN - 1]) == [[0, 2 * PIECE_MIN - 1]]
+    assert pieces(driver, "halve", [PIECE_MIN]) == [[0, PIECE_MIN]]
+    assert pieces(driver, "halve", [64 * MiB]) == [[1, 32 * MiB]]
+
+
+@pytest.mark.parametrize("pos, window_len, want", [
+    # len, where, dst_off, window_off, from_window, from_dst
+    (0, 0, [0, IN_DST, 0, 0, 0, 0]),                                       # nothing in front: no history
+    (0, 1000, [1000, WINDOW, 0, 0, 0, 0]),                                # the caller's window as it stands
+    (0, 32768, [32768, WINDOW, 0, 0, 0, 0]),
+    (100, 0, [100, IN_DST, 0, 0, 0, 0]),                                  # no window: what was delivered
+    (100, 200, [300, SPLICED, 0, 0, 200, 100]),                           # pos + window_len < 32768: all of both
+    (20000, 20000, [32768, SPLICED, 0, 7232, 12768, 20000]),              # pos < 32768 <= pos + window_len: the window's end
+    (30000, 32768, [32768, SPLICED, 0, 30000, 2768, 30000]),
+    (32767, 5, [32768, SPLICED, 0, 4, 1, 32767]),
+    (32768, 32768, [32768, IN_DST, 0, 0, 0, 0]),                          # pos >= 32768: the output has it all
+    (100000, 0, [32768, IN_DST, 67232, 0, 0, 0]),
+])
+def test_the_history_in_front_of_an_output_position(driver, pos, window_len, want):
+    assert pieces(driver, "history", [pos, window_len]) == [want]
+
+
+def test_the_sequential_decoders_input(driver):
+    # the anchor is bit 5 of byte 10 MiB, the piece the device could not do begins 40 MiB behind it: that piece whole
+    far = state(bit=8 * 50 * MiB + 3, abit=8 * 10 * MiB + 5, p=PIECE_MIN)
+    got = pieces(driver, "seq", far + [100 * MiB, 3, 0, 5, 0, 5, 0, 5])
+    assert got[0] == [10 * MiB, 5, 44 * MiB, 44 * MiB]
+    # no block completed (status 0, the end bit still 5): twice as much, until all 90 MiB behind the anchor were given --
+    # then the stream form says how the stream ends
+    assert got[1:] == [[1, 88 * MiB, 88 * MiB, 1], [1, 176 * MiB, 90 * MiB, 1], [0, 176 * MiB, 90 * MiB, 1]]
+    # the piece begins at the anchor: two pieces
+    near = state(bit=8 * 10 * MiB + 5, abit=8 * 10 * MiB + 5, p=PIECE_MIN)
+    assert pieces(driver, "seq", near + [100 * MiB, 0])[0] == [10 * MiB, 5, 8 * MiB, 8 * MiB]
+    assert pieces(driver, "seq", near + [12 * MiB, 0])[0] == [10 * MiB, 5, 8 * MiB, 2 * MiB]
+    # a block completed: no more input is asked for, whatever is left
+    assert pieces(driver, "seq", near + [100 * MiB, 1, 0, 900])[1] == [0, 8 * MiB, 8 * MiB, 0]
+
+
+@pytest.mark.parametrize("status, moved, stream_form", [
+    (1, True, 0), (1, False, 0),                  # the stream ended in the blocks form
+    (0, True, 0),                                 # complete blocks: delivered, and the device goes on
+    (0, False, 1),                                # the input ends inside the first block
+    (-3, True, 1), (-3, False, 1),                # a data error: the stream form's message and counts
+    (-4, True, 0), (-4, False, 0),                # out of memory: no second attempt
+    (-5, False, 1), (2, True, 1),                 # anything else the decoder might say
+])
+def test_which_form_of_the_sequential_decoder_answers(driver, status, moved, stream_form):
+    # all of the input was given (4000 bytes behind byte 1000), so nothing is doubled
+    st = state(bit=8 * 1000 + 5, abit=8 * 1000 + 5)
+    got = pieces(driver, "seq", st + [5000, 1, status, 77 if moved else 5])
+    assert got == [[1000, 5, 8 * MiB, 4000], [0, 8 * MiB, 4000, stream_form]]
+    assert stream_form == int(status != 1 and not (status == 0 and moved) and status != -4)
+
+
+def test_the_state_behind_the_sequential_decoders_blocks(driver):
+    st = state(bit=8 * 50 * MiB + 3, key=792003, fin=1, produced=9000, abit=8 * 10 * MiB + 5, aout=4000, p=2 * MiB)
+    # complete blocks up to bit 1000005 from byte 10 MiB, 14000 bytes delivered with them: a block start, the new anchor
+    at = 8 * 10 * MiB + 1000005
+    assert pieces(driver, "blocks", st + [1000005, 14000, PIECE_MIN]) == [[at, 0, -1, 14000, at, 14000, PIECE_MIN]]

@@ -36,7 +36,10 @@
 // What the host does between the launches -- the steps named above, the SUBBLOCK regions and their merge, the slot sizes,
 // where the tables lie in scratch, which parts run again, the symbol array's layout -- is in inflate_large_plan.h.  This file
 // keeps the kernels, the scratch and table uploads, the launches and synchronisations, and each entry point's policy for a
-// stream the device path cannot do.
+// stream the device path cannot do.  ONE stream's pass is asked for and answered by value (LargeRequest, LargeAnswer); what
+// the last_* getters report is published once, at each entry point's exit (LargeCounters, one_pass).  The pieces loop
+// (inflate_pieces_call) steps by the plan's rules too (PiecesState): here it splices the history, runs the pass or the
+// sequential decoder, and uploads.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -461,14 +464,17 @@ void compact_parts_kernel(const PartCopy *__restrict__ parts, uint16_t *__restri
     }
 }
 
-static thread_local int t_large_parts = 0;
-static thread_local int t_large_subparts = 0;           // of them, parts that began inside a block
-static thread_local int t_large_substarts = 0;          // SUBBLOCK: sub-starts placed (the sync kernel's boundaries, deduplicated)
-static thread_local int t_large_pieces = 0;             // pieces: device passes of the last call
-static thread_local uint64_t t_large_host_bytes = 0;    // pieces: compressed bytes the sequential decoder took
+// What the zng_rocm_inflate_large_last_* getters report: the calling thread's last call.  An entry point counts in a value of
+// its own (or takes inflate_large_try's answer) and publishes it here once, at its exit; nothing below an entry point writes it.
+struct LargeCounters {
+    int      parts = 0;
+    int      subparts = 0;                              // of them, parts that began inside a block
+    int      substarts = 0;                             // SUBBLOCK: sub-starts placed (the sync kernel's boundaries, deduplicated)
+    int      pieces = 0;                                // pieces: device passes of the call
+    uint64_t host_bytes = 0;                            // pieces: compressed bytes the sequential decoder took
+};
+static thread_local LargeCounters t_last;
 static thread_local IndexSink *t_index_sink = nullptr;  // an index is being built (inflate_dev.h); null outside such a call
-// the last pass's candidates (walk_chain, Chain::record), in the pass's own positions: inflate_pieces_call moves them
-static thread_local std::vector<std::pair<unsigned long long, uint64_t>> t_pass_cands;
 #ifdef ZR_INFLATE_STATS
 static std::vector<unsigned long long> g_dbg_starts;     // diagnostic builds: the last call's part starts and result words
 static std::vector<uint32_t> g_dbg_res;
@@ -498,12 +504,7 @@ IndexSink *inflate_index_sink() { return t_index_sink; }
 void inflate_index_sink_set(IndexSink *sink) { t_index_sink = sink; }
 
 // the part counters of the calling thread back to 0 (a call begins; or "the sequential decoder did it": inflate_resolve.hip)
-void inflate_large_forget_parts() {
-    t_large_parts = 0;
-    t_large_subparts = 0;
-    t_large_substarts = 0;
-}
-
+void inflate_large_forget_parts() { t_last.parts = t_last.subparts = t_last.substarts = 0; }
 
 // ---- the pass -----------------------------------------------------------------------------------------------------------
 // One stream of a device pass: what its finder found, and what pass_run made of it.
@@ -1001,42 +1002,59 @@ static int pass_run(Workspace *ws, std::vector<PassStream> &ss, bool sub, bool b
     return ZNG_ROCM_OK;
 }
 
-// ONE stream through the finder and the pass, as a table of one: returns 1 with *out_len / *in_used set, or 0 = "irregular: use the
-// sequential decoder", or a negative error (-5 with *out_len set: dst_cap is too small).
-// Blocks mode (`blocks`, the streaming hook): the stream starts at bit `start_bit` of d_src, and *end_bit / *final say where
-// the delivered blocks end and whether the BFINAL one is among them.  `sub`, `pp`: see pass_run.
-static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len, const uint8_t *d_window, uint32_t window_len,
-                             uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, size_t *in_used, hipStream_t st,
-                             bool blocks = false, uint64_t start_bit = 0, uint64_t *end_bit_out = nullptr, int *final_out = nullptr,
-                             bool sub = false, PiecePass *pp = nullptr) {
-    if (!large_length_ok(src_len)) return why("stream below 128 KiB (or 2 GiB and more)");
+// ONE stream through the finder and the pass, as a table of one.  What a caller asks for:
+struct LargeRequest {
+    const uint8_t *d_src = nullptr;
+    size_t         src_len = 0;
+    const uint8_t *d_window = nullptr;
+    uint32_t       window_len = 0;
+    uint8_t       *d_dst = nullptr;
+    size_t         dst_cap = 0;
+    uint64_t       start_bit = 0;                         // the stream begins at this bit of d_src (blocks mode, pieces)
+    bool           blocks = false;                        // blocks mode (the streaming hook), `sub`, `pp`: see pass_run
+    bool           sub = false;
+    PiecePass     *pp = nullptr;
+};
+// ... and what it gets.  The counts hold when inflate_large_try returns 1, or -5 (`produced` says how much room is needed);
+// the counters and the block starts always (a pass that was not done has no parts).
+struct LargeAnswer {
+    uint64_t produced = 0;
+    size_t   in_used = 0;
+    uint64_t end_bit = 0;                                 // blocks mode: where the delivered blocks end ...
+    bool     final = false;                               // ... and whether the BFINAL one is among them
+    int      parts = 0, subparts = 0, substarts = 0;      // LargeCounters' first three, of this pass
+    std::vector<std::pair<unsigned long long, uint64_t>> cands;      // an index is being built: Chain::cands, the pass's own positions
+};
+// Returns 1, or 0 = "irregular: use the sequential decoder", or a negative error (-5: dst_cap is too small).
+static int inflate_large_try(Workspace *ws, const LargeRequest &q, LargeAnswer &a, hipStream_t st) {
+    if (!large_length_ok(q.src_len)) return why("stream below 128 KiB (or 2 GiB and more)");
     std::vector<PassStream> ss(1);
     PassStream &s = ss[0];
-    s.d_src = d_src;
-    s.src_len = src_len;
-    s.d_window = d_window;
-    s.window_len = window_len;
-    s.d_dst = d_dst;
-    s.dst_cap = dst_cap;
-    s.start_bit = start_bit;
-    s.scan_lo = pp ? (size_t)pp->scan_lo : 0;             // (pieces: the finder scans the piece alone)
-    s.key0 = pp ? pp->key0 : 0ull;
+    s.d_src = q.d_src;
+    s.src_len = q.src_len;
+    s.d_window = q.d_window;
+    s.window_len = q.window_len;
+    s.d_dst = q.d_dst;
+    s.dst_cap = q.dst_cap;
+    s.start_bit = q.start_bit;
+    s.scan_lo = q.pp ? (size_t)q.pp->scan_lo : 0;         // (pieces: the finder scans the piece alone)
+    s.key0 = q.pp ? q.pp->key0 : 0ull;
     // ---- candidates: the finder over a table of this one stream ---------------------------------------------------------
     std::vector<std::vector<unsigned long long>> good(1);
     FindOne one;
-    if (int rc = find_starts(ws, ss, good, {0}, sub, st, &one)) return rc;
+    if (int rc = find_starts(ws, ss, good, {0}, q.sub, st, &one)) return rc;
     if (one.no_room) return one.no_room;                  // (no scratch is this call's error, not a reason for the slow path)
     if (s.left) return 0;                                 // (far more candidates than a deflate stream has)
     // (SUBBLOCK goes on without candidates: a stream of fixed-code blocks is cut inside them)
-    if (one.n_f1 == 0 && !sub) return why("no candidate block starts, or far more than a deflate stream has");
+    if (one.n_f1 == 0 && !q.sub) return why("no candidate block starts, or far more than a deflate stream has");
     // ---- the pass over this one stream ------------------------------------------------------------------------------
-    thin_starts(good[0], start_bit, src_len, s.starts, s.heavy);
+    thin_starts(good[0], q.start_bit, q.src_len, s.starts, s.heavy);
     s.chain.record = t_index_sink != nullptr;
     size_t taken = 0;
     int launches = 0;
-    const int rc = pass_run(ws, ss, sub, blocks, pp, st, &taken, &launches);
-    if (t_index_sink) t_pass_cands.swap(s.chain.cands);
-    t_large_substarts += (int)s.substarts;
+    const int rc = pass_run(ws, ss, q.sub, q.blocks, q.pp, st, &taken, &launches);
+    a.cands.swap(s.chain.cands);
+    a.substarts = (int)s.substarts;
 #ifdef ZR_INFLATE_STATS
     if (s.res) {
         g_dbg_starts = s.starts;
@@ -1045,23 +1063,36 @@ static int inflate_large_try(Workspace *ws, const uint8_t *d_src, size_t src_len
 #endif
     if (rc) return rc;
     if (s.left) return 0;
-    const uint64_t produced = s.chain.produced;
-    if (out_len) *out_len = produced;
-    if (in_used) *in_used = (size_t)((s.chain.end_bit + 7) >> 3);
-    if (end_bit_out) *end_bit_out = s.chain.end_bit;
-    if (final_out) *final_out = s.chain.final ? 1 : 0;
-    if ((blocks || (pp && pp->stopped)) && produced == 0) {       // no block complete yet (pieces: no symbol): nothing was launched
-        t_large_parts = 0;
-        t_large_subparts = 0;
-        return 1;
-    }
+    a.produced = s.chain.produced;
+    a.in_used = (size_t)((s.chain.end_bit + 7) >> 3);
+    a.end_bit = s.chain.end_bit;
+    a.final = s.chain.final;
+    // no block complete yet (pieces: no symbol): nothing was launched
+    if ((q.blocks || (q.pp && q.pp->stopped)) && a.produced == 0) return 1;
     if (s.status == -5) {
-        set_error("inflate output (%llu bytes) exceeds dst_cap", (unsigned long long)produced);
+        set_error("inflate output (%llu bytes) exceeds dst_cap", (unsigned long long)a.produced);
         return -5;
     }
-    t_large_parts = (int)s.chain.copies.size();
-    t_large_subparts = (int)s.chain.subparts;
+    a.parts = (int)s.chain.copies.size();
+    a.subparts = (int)s.chain.subparts;
     return 1;
+}
+// A one-pass entry point's call (the workspace's lock is held): the stream through inflate_large_try, the calling thread's
+// part counters from its answer (`pieces` and `host_bytes` are a pieces call's, and stay), and the caller's out parameters
+// as far as the return value says they hold.
+static int one_pass(Workspace *ws, const LargeRequest &q, hipStream_t st, uint64_t *out_len, size_t *in_used,
+                    uint64_t *end_bit = nullptr, int *final = nullptr) {
+    LargeAnswer a;
+    const int rc = inflate_large_try(ws, q, a, st);
+    t_last.parts = a.parts;
+    t_last.subparts = a.subparts;
+    t_last.substarts = a.substarts;
+    if (rc != 1 && rc != -5) return rc;
+    if (out_len) *out_len = a.produced;
+    if (in_used) *in_used = a.in_used;
+    if (end_bit) *end_bit = a.end_bit;
+    if (final) *final = a.final ? 1 : 0;
+    return rc;
 }
 
 // A large stream that is in HOST memory (zng_rocm_inflate_raw*, and with them uncompress2 and the gzip / zlib one-shots):
@@ -1074,42 +1105,54 @@ int inflate_large_from_host(const uint8_t *src, size_t src_len, const uint8_t *d
     uint8_t *d_src = nullptr;
     if (scratch_reserve(ws, kScrLargeSrc, src_len + 64, false, (void **)&d_src) != ZNG_ROCM_OK) return 0;
     if (hipMemcpyAsync(d_src, src, src_len, hipMemcpyHostToDevice, st) != hipSuccess) return 0;
-    uint64_t n = 0;
-    size_t used = 0;
-    const int rc = inflate_large_try(ws, d_src, src_len, d_window, window_len, d_dst, dst_cap, &n, &used, st);
-    if (rc == 1 || rc == -5) {
-        if (out_len) *out_len = n;
-        if (in_used) *in_used = used;
-        return rc;
-    }
-    return 0;
+    LargeRequest q;
+    q.d_src = d_src;
+    q.src_len = src_len;
+    q.d_window = d_window;
+    q.window_len = window_len;
+    q.d_dst = d_dst;
+    q.dst_cap = dst_cap;
+    const int rc = one_pass(ws, q, st, out_len, in_used);
+    return rc == 1 || rc == -5 ? rc : 0;
 }
 
-// The device path alone, for callers inside the library that have their own sequential decoder to fall back on
-// (hook.hip): 1 = done, 0 = irregular (nothing usable was written), -5 with *out_len set = dst_cap too small, other
-// negatives = errors.
-int inflate_large_device_only(const uint8_t *d_src, size_t src_len, const uint8_t *d_window, uint32_t window_len, uint8_t *d_dst,
-                              size_t dst_cap, uint64_t *out_len, size_t *in_used, hipStream_t st) {
+// The device path alone, for callers that have their own sequential decoder to fall back on (hook.hip; inflate_large_call):
+// 1 = done, 0 = irregular (nothing usable was written), -5 with *out_len set = dst_cap too small, other negatives = errors.
+// Blocks mode (the streaming hook): d_src holds the stream from the byte that contains bit `start_bit` (0..7) on; 1 = *out_len
+// bytes of complete blocks at d_dst, *end_bit = where they end, *final = the BFINAL block is among them; 0 = irregular (the
+// caller's host decoder in blocks mode takes the call); -5 with *out_len = dst_cap too small.
+static int device_only(const LargeRequest &q, hipStream_t st, uint64_t *out_len, size_t *in_used, uint64_t *end_bit = nullptr,
+                       int *final = nullptr) {
     inflate_large_forget_parts();
-    Workspace *ws = workspace_for(st);
+    Workspace *ws = workspace_for(st);                   // scratch is keyed by the caller's HIP stream (context.h)
     if (!ws) return ZNG_ROCM_ENOMEM;
     std::lock_guard<std::mutex> use(ws->mu);
-    return inflate_large_try(ws, d_src, src_len, d_window, window_len, d_dst, dst_cap, out_len, in_used, st);
+    return one_pass(ws, q, st, out_len, in_used, end_bit, final);
 }
-
-// Blocks mode of the above (the streaming hook, hook.hip): d_src holds the stream from the byte that contains bit `start_bit`
-// (0..7) on; 1 = *out_len bytes of complete blocks at d_dst, *end_bit = where they end, *final = the BFINAL block is among
-// them; 0 = irregular (the caller's host decoder in blocks mode takes the call); -5 with *out_len = dst_cap too small.
+int inflate_large_device_only(const uint8_t *d_src, size_t src_len, const uint8_t *d_window, uint32_t window_len, uint8_t *d_dst,
+                              size_t dst_cap, uint64_t *out_len, size_t *in_used, hipStream_t st) {
+    LargeRequest q;
+    q.d_src = d_src;
+    q.src_len = src_len;
+    q.d_window = d_window;
+    q.window_len = window_len;
+    q.d_dst = d_dst;
+    q.dst_cap = dst_cap;
+    return device_only(q, st, out_len, in_used);
+}
 int inflate_large_blocks_device_only(const uint8_t *d_src, size_t src_len, unsigned start_bit, const uint8_t *d_window,
                                      uint32_t window_len, uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, uint64_t *end_bit,
                                      int *final, hipStream_t st) {
-    inflate_large_forget_parts();
-    Workspace *ws = workspace_for(st);
-    if (!ws) return ZNG_ROCM_ENOMEM;
-    std::lock_guard<std::mutex> use(ws->mu);
-    size_t used = 0;
-    return inflate_large_try(ws, d_src, src_len, d_window, window_len, d_dst, dst_cap, out_len, &used, st, true, start_bit & 7u,
-                             end_bit, final);
+    LargeRequest q;
+    q.d_src = d_src;
+    q.src_len = src_len;
+    q.d_window = d_window;
+    q.window_len = window_len;
+    q.d_dst = d_dst;
+    q.dst_cap = dst_cap;
+    q.start_bit = start_bit & 7u;
+    q.blocks = true;
+    return device_only(q, st, out_len, nullptr, end_bit, final);
 }
 
 }  // namespace zr
@@ -1118,11 +1161,11 @@ using namespace zr;
 
 extern "C" {
 
-int zng_rocm_inflate_large_last_parts(void) { return t_large_parts; }
-int zng_rocm_inflate_large_last_subparts(void) { return t_large_subparts; }
-int zng_rocm_inflate_large_last_substarts(void) { return t_large_substarts; }
-int zng_rocm_inflate_large_last_pieces(void) { return t_large_pieces; }
-uint64_t zng_rocm_inflate_large_last_host_bytes(void) { return t_large_host_bytes; }
+int zng_rocm_inflate_large_last_parts(void) { return t_last.parts; }
+int zng_rocm_inflate_large_last_subparts(void) { return t_last.subparts; }
+int zng_rocm_inflate_large_last_substarts(void) { return t_last.substarts; }
+int zng_rocm_inflate_large_last_pieces(void) { return t_last.pieces; }
+uint64_t zng_rocm_inflate_large_last_host_bytes(void) { return t_last.host_bytes; }
 #ifdef ZR_INFLATE_STATS
 unsigned zng_rocm_debug_large_parts(unsigned long long *starts, uint32_t *res8, unsigned cap) {
     const unsigned n = (unsigned)std::min<size_t>(cap, g_dbg_starts.size());
@@ -1136,6 +1179,15 @@ unsigned zng_rocm_debug_large_parts(unsigned long long *starts, uint32_t *res8, 
 
 }  // extern "C"
 
+// a host copy of [d_src, d_src + len), complete when this returns (never empty: the decoders want a pointer)
+static int host_copy(std::vector<uint8_t> &host, const uint8_t *d_src, size_t len, hipStream_t st) {
+    host.resize(len ? len : 1);
+    if (!len) return ZNG_ROCM_OK;
+    ZR_HIP(hipMemcpyAsync(host.data(), d_src, len, hipMemcpyDeviceToHost, st));
+    ZR_HIP(hipStreamSynchronize(st));
+    return ZNG_ROCM_OK;
+}
+
 // zng_rocm_inflate_large_dev, and zng_rocm_inflate_large_ex_dev with `sub` = ZNG_ROCM_INFLATE_SUBBLOCK
 static int inflate_large_call(const uint8_t *d_src, size_t src_len, const uint8_t *d_window, uint32_t window_len,
                               uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, size_t *in_used, void *stream, bool sub) {
@@ -1146,21 +1198,18 @@ static int inflate_large_call(const uint8_t *d_src, size_t src_len, const uint8_
     if ((!d_src && src_len) || window_len > 32768u || (window_len && !d_window)) return ZNG_ROCM_EINVAL;
     DeviceGuard dev;
     hipStream_t st = (hipStream_t)stream;
-    inflate_large_forget_parts();
-    {
-        Workspace *ws = workspace_for(st);               // scratch is keyed by the caller's HIP stream (context.h)
-        if (!ws) return ZNG_ROCM_ENOMEM;
-        std::lock_guard<std::mutex> use(ws->mu);
-        const int rc = inflate_large_try(ws, d_src, src_len, d_window, window_len, d_dst, dst_cap, out_len, in_used, st, false, 0,
-                                         nullptr, nullptr, sub);
-        if (rc != 0) return rc;
-    }
+    LargeRequest q;
+    q.d_src = d_src;
+    q.src_len = src_len;
+    q.d_window = d_window;
+    q.window_len = window_len;
+    q.d_dst = d_dst;
+    q.dst_cap = dst_cap;
+    q.sub = sub;
+    if (int rc = device_only(q, st, out_len, in_used)) return rc;
     // irregular: the sequential decoder on a host copy of the stream says exactly what the reference would
-    std::vector<uint8_t> host(src_len ? src_len : 1);
-    if (src_len) {
-        ZR_HIP(hipMemcpyAsync(host.data(), d_src, src_len, hipMemcpyDeviceToHost, st));
-        ZR_HIP(hipStreamSynchronize(st));
-    }
+    std::vector<uint8_t> host;
+    if (int rc = host_copy(host, d_src, src_len, st)) return rc;
     return inflate_raw_window_sequential(host.data(), src_len, d_window, window_len, d_dst, dst_cap, out_len, in_used, st);
 }
 
@@ -1173,187 +1222,134 @@ static int inflate_large_call(const uint8_t *d_src, size_t src_len, const uint8_
 // the sequential decoder from the last block start delivered: complete blocks first, and the loop goes on behind them; a
 // data error or the end of the input there is decoded once more in the stream form, whose status, message and counts
 // are then the reference's.
-// kPieceMin / kPieceDefault / kPieceMax: inflate_large_limits.h
-
+// The loop's rules -- the state it carries, where a piece and its pass's buffer begin and end, how positions are re-based,
+// which bytes are the history, what the sequential decoder is given -- are inflate_large_plan.h's (PiecesState); here are the
+// splice, the pass, the host decoder and the uploads.  `c` counts the call (substarts: a pass repeated with half the piece
+// does not count, every other pass does).  kPieceMin / kPieceDefault / kPieceMax: inflate_large_limits.h
 static int inflate_pieces_call(const uint8_t *d_src, size_t src_len, const uint8_t *d_window, uint32_t window_len,
                                uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, size_t *in_used, size_t piece_bytes, bool sub,
-                               hipStream_t st) {
+                               hipStream_t st, LargeCounters &c) {
     Workspace *ws = workspace_for(st);                   // scratch is keyed by the caller's HIP stream (context.h)
     if (!ws) return ZNG_ROCM_ENOMEM;
     std::unique_lock<std::mutex> use(ws->mu);            // (let go while the sequential decoder works on the host)
     uint8_t *d_hist = nullptr;
     if (int rc = scratch_reserve(ws, kScrLargeHist, 32768 + 64, false, (void **)&d_hist)) return rc;
-    // the last min(32768, pos + window_len) bytes in front of output position `pos`: in d_dst, or spliced from the caller's
-    // window and d_dst while pos < 32768
-    auto history = [&](uint64_t pos, const uint8_t **h, uint32_t *hl) -> int {
-        const uint64_t n = std::min<uint64_t>(32768u, pos + window_len);
-        *hl = (uint32_t)n;
-        *h = pos >= n ? d_dst + (pos - n) : d_window;
-        if (pos >= n || pos == 0) return ZNG_ROCM_OK;
-        if (int rc = scratch_reserve(ws, kScrLargeHist, 32768 + 64, false, (void **)&d_hist)) return rc;   // (under the lock)
-        const uint64_t from_window = n - pos;
-        ZR_HIP(hipMemcpyAsync(d_hist, d_window + (window_len - from_window), from_window, hipMemcpyDeviceToDevice, st));
-        ZR_HIP(hipMemcpyAsync(d_hist + from_window, d_dst, pos, hipMemcpyDeviceToDevice, st));
+    // the history H (piece_history) as a pointer: where it lies, or spliced into d_hist (under the lock)
+    auto history = [&](const PieceHistory &H, const uint8_t **h) -> int {
+        *h = H.where == PieceHistory::kInDst ? d_dst + H.dst_off : d_window;
+        if (H.where != PieceHistory::kSpliced) return ZNG_ROCM_OK;
+        if (int rc = scratch_reserve(ws, kScrLargeHist, 32768 + 64, false, (void **)&d_hist)) return rc;
+        ZR_HIP(hipMemcpyAsync(d_hist, d_window + H.window_off, H.from_window, hipMemcpyDeviceToDevice, st));
+        ZR_HIP(hipMemcpyAsync(d_hist + H.from_window, d_dst, H.from_dst, hipMemcpyDeviceToDevice, st));
         *h = d_hist;
         return ZNG_ROCM_OK;
     };
-    uint64_t bit = 0, key = 0, produced = 0;              // where the next piece begins, its key; bytes delivered
-    uint64_t abit = 0, aout = 0;                          // the last block start delivered up to (the sequential decoder's start)
-    int fin = -1;
-    size_t p = piece_bytes;
-    int parts = 0, subparts = 0, passes = 0;
-    uint64_t host_bytes = 0;
-    auto done = [&](int rc) {
-        t_large_parts = parts;
-        t_large_subparts = subparts;
-        t_large_pieces = passes;
-        t_large_host_bytes = host_bytes;
+    // the tail behind the sequential decoder, in either form: the tokens' bytes go behind the anchor (`aout`) with the history H
+    // in front of them, *total = the output up to their end; -5 when that does not fit.  The tokens are freed.
+    auto deliver = [&](zng_rocm_inflate_tokens *tk, uint64_t aout, const PieceHistory &H, uint64_t *total) -> int {
+        *total = aout + tk->out_len;
+        const uint8_t *h = nullptr;
+        int rc = -5;
+        if (*total > dst_cap) set_error("inflate output (%llu bytes) exceeds dst_cap", (unsigned long long)*total);
+        else if ((rc = history(H, &h)) == ZNG_ROCM_OK) rc = inflate_tokens_to_device(tk, h, H.len, d_dst + aout, st);
+        zng_rocm_inflate_tokens_free(tk);
         return rc;
     };
+    PiecesState s = pieces_begin(piece_bytes);
     for (;;) {
-        const uint64_t sbyte = bit >> 3;
-        if (sbyte < src_len) {
-            // the piece [sbyte, end); one that would leave less than a quarter piece behind it ends a quarter piece early
-            uint64_t end = sbyte + p;
-            if (end >= src_len) end = src_len;
-            else if (src_len - end < p / 4) end = src_len - p / 4;
-            // the pass's buffer begins at the piece, or at the header of the dynamic block its first start lies in
-            const uint64_t base = (key >= 2 ? std::min<uint64_t>(sbyte, (key - 2) >> 3) : sbyte) & ~(uint64_t)255;
-            PiecePass pp;
-            pp.scan_lo = sbyte - base;
-            pp.key0 = key >= 2 ? key - 8 * base : key;
-            pp.fin0 = fin;
-            pp.last = end == src_len;
-            pp.q = piece_bytes;
-            const uint8_t *h = nullptr;
-            uint32_t hl = 0;
-            if (int rc = history(produced, &h, &hl)) return done(rc);
-            const int substarts0 = t_large_substarts;
-            uint64_t n = 0;
-            size_t used = 0;
-            const int rc = inflate_large_try(ws, d_src + base, (size_t)(end - base), h, hl, d_dst + produced,
-                                             dst_cap > produced ? dst_cap - produced : 0, &n, &used, st, false, bit - 8 * base,
-                                             nullptr, nullptr, sub, &pp);
+        NextPiece np = piece_next(s, src_len, piece_bytes);
+        if (np.any) {
+            const PieceHistory H = piece_history(s.produced, window_len);
+            LargeRequest q;
+            q.d_src = d_src + np.base;
+            q.src_len = (size_t)np.len();
+            if (int rc = history(H, &q.d_window)) return rc;
+            q.window_len = H.len;
+            q.d_dst = d_dst + s.produced;
+            q.dst_cap = dst_cap > s.produced ? dst_cap - s.produced : 0;
+            q.start_bit = np.start_bit;
+            q.sub = sub;
+            q.pp = &np.pp;
+            LargeAnswer a;
+            const int rc = inflate_large_try(ws, q, a, st);
+            if (rc == 0 && np.pp.halve && piece_halve(s)) continue;       // over a scratch cap: the same start with half the piece
+            c.substarts += a.substarts;
             if (rc == 1) {
-                ++passes;
-                parts += t_large_parts;
-                subparts += t_large_subparts;
-                if (t_index_sink)                         // the pass's block starts, moved by its base and by what lay in front
-                    for (const auto &c : t_pass_cands) t_index_sink->cands.emplace_back(c.first + 8 * base, produced + c.second);
-                produced += n;
-                if (!pp.stopped) {                        // the stream ended in this piece
-                    *out_len = produced;
-                    *in_used = (size_t)(base + used);
-                    return done(1);
+                ++c.pieces;
+                c.parts += a.parts;
+                c.subparts += a.subparts;
+                if (t_index_sink) piece_cands(a.cands, np, s, t_index_sink->cands);
+                const PieceStep step = piece_after_pass(s, np, a.produced, a.in_used, piece_bytes);
+                if (step.done) {                          // the stream ended in this piece
+                    *out_len = s.produced;
+                    *in_used = (size_t)step.in_used;
+                    return 1;
                 }
-                bit = pp.next_bit + 8 * base;
-                key = pp.next_key >= 2 ? pp.next_key + 8 * base : pp.next_key;
-                fin = pp.next_fin;
-                if (key == 0) {
-                    abit = bit;
-                    aout = produced;
-                    if (t_index_sink) t_index_sink->cands.emplace_back(abit, aout);
-                }
-                p = piece_bytes;
+                if (step.anchored && t_index_sink) t_index_sink->cands.emplace_back(s.abit, s.aout);
                 continue;
             }
             if (rc == -5) {                               // the piece's output does not fit behind what is there
-                *out_len = produced + n;
-                *in_used = (size_t)(base + used);
-                set_error("inflate output (%llu bytes) exceeds dst_cap", (unsigned long long)(produced + n));
-                return done(-5);
+                *out_len = s.produced + a.produced;
+                *in_used = (size_t)np.stream_byte(a.in_used);
+                set_error("inflate output (%llu bytes) exceeds dst_cap", (unsigned long long)*out_len);
+                return -5;
             }
-            if (rc < 0) return done(rc);
-            if (pp.halve && p / 2 >= kPieceMin) {         // over a scratch cap: the same start with half the piece
-                p /= 2;
-                t_large_substarts = substarts0;
-                continue;
-            }
+            if (rc < 0) return rc;
         }
-        // the sequential decoder from the last block start delivered, with the history in front of it; complete blocks of at
-        // least two pieces of input, more while none completes.  The workspace is not used while it decodes: the lock is let
-        // go, and taken again to splice the history (d_hist) and upload what was decoded.
-        const uint64_t a0 = abit >> 3, sb = abit & 7u;
-        const uint8_t *h = nullptr;
-        uint32_t hl = (uint32_t)std::min<uint64_t>(32768u, aout + window_len);
+        // the sequential decoder from the anchor, with the history in front of it (seq_input: how much input, and when more).
+        // The workspace is not used while it decodes: the lock is let go, and taken again to splice the history (d_hist) and
+        // upload what was decoded.
+        SeqInput in = seq_input(s);
+        const PieceHistory H = piece_history(s.aout, window_len);
         use.unlock();
         std::vector<uint8_t> host;
-        uint64_t span = std::max<uint64_t>(2ull * p, sbyte - a0 + p), len = 0, eb = sb;
+        uint64_t len = 0, eb = in.sb;
         zng_rocm_inflate_tokens tk;
         int status = 0;
         for (;;) {
-            len = std::min<uint64_t>(src_len - a0, span);
-            host.resize(len ? (size_t)len : 1);
-            if (len) {
-                ZR_HIP(hipMemcpyAsync(host.data(), d_src + a0, (size_t)len, hipMemcpyDeviceToHost, st));
-                ZR_HIP(hipStreamSynchronize(st));
-            }
-            status = zng_rocm_inflate_tokens_decode_blocks(host.data(), (size_t)len, sb, hl, &tk, &eb);
-            if (status == 0 && eb == sb && len < src_len - a0) {
-                zng_rocm_inflate_tokens_free(&tk);
-                span *= 2;
-                continue;
-            }
-            break;
+            len = in.len(src_len);
+            if (int rc = host_copy(host, d_src + in.a0, (size_t)len, st)) return rc;
+            status = zng_rocm_inflate_tokens_decode_blocks(host.data(), (size_t)len, in.sb, H.len, &tk, &eb);
+            if (!seq_wants_more(in, src_len, status, eb)) break;
+            zng_rocm_inflate_tokens_free(&tk);
         }
         // a data error, or the end of the input inside a block: the stream form from the same bit (still without the lock)
-        const bool stream_form = status != 1 && !(status == 0 && eb != sb) && status != -4;
+        const bool stream_form = seq_stream_form(status, eb, in.sb);
         if (stream_form) {
             zng_rocm_inflate_tokens_free(&tk);
-            status = zr_inflate_decode_from(host.data(), (size_t)len, sb, hl, &tk);
+            status = zr_inflate_decode_from(host.data(), (size_t)len, in.sb, H.len, &tk);
         }
         use.lock();
         // (sb <= 7 < 8 * len unless len = 0 and sb = 0: the decoder's ZNG_ROCM_EINVAL, which has the value of Z_DATA_ERROR,
         // cannot come back)
         if (status == -4) {
             zng_rocm_inflate_tokens_free(&tk);
-            return done(ZNG_ROCM_ENOMEM);
+            return ZNG_ROCM_ENOMEM;
         }
-        if (!stream_form) {                              // complete blocks: delivered, and the device goes on behind them
-            const uint64_t total = aout + tk.out_len;
-            host_bytes += (eb + 7) >> 3;
-            if (total > dst_cap) {
-                *out_len = total;
-                *in_used = (size_t)(a0 + ((eb + 7) >> 3));
-                set_error("inflate output (%llu bytes) exceeds dst_cap", (unsigned long long)total);
-                zng_rocm_inflate_tokens_free(&tk);
-                return done(-5);
-            }
-            int rc = history(aout, &h, &hl);
-            if (rc == ZNG_ROCM_OK) rc = inflate_tokens_to_device(&tk, h, hl, d_dst + aout, st);
-            const size_t tk_used = tk.in_used;
-            zng_rocm_inflate_tokens_free(&tk);
-            if (rc != ZNG_ROCM_OK) return done(rc);
-            produced = total;
-            if (status == 1) {
-                *out_len = produced;
-                *in_used = (size_t)(a0 + tk_used);
-                return done(1);
-            }
-            bit = 8 * a0 + eb;
-            key = 0;
-            fin = -1;
-            abit = bit;
-            aout = produced;
-            if (t_index_sink) t_index_sink->cands.emplace_back(abit, aout);
-            p = piece_bytes;
-            continue;
+        const size_t tk_used = tk.in_used;
+        if (stream_form && status < 0) set_error("%s", tk.msg);       // (a -5 below replaces it)
+        uint64_t total = 0;
+        const int rc = deliver(&tk, s.aout, H, &total);
+        if (stream_form) {                               // its status, message and counts are the one-shot's
+            c.host_bytes += tk_used;
+            *out_len = total;
+            *in_used = (size_t)in.stream_byte(tk_used);
+            return rc != ZNG_ROCM_OK ? rc : status;
         }
-        // the stream form (decoded above): its status, message and counts are the one-shot's
-        const uint64_t total = aout + tk.out_len;
-        *out_len = total;
-        *in_used = (size_t)(a0 + tk.in_used);
-        host_bytes += tk.in_used;
-        if (total > dst_cap) {
-            set_error("inflate output (%llu bytes) exceeds dst_cap", (unsigned long long)total);
-            zng_rocm_inflate_tokens_free(&tk);
-            return done(-5);
+        // complete blocks: delivered, and the device goes on behind them
+        c.host_bytes += seq_blocks_bytes(eb);
+        if (total > dst_cap) {                           // (deliver's -5)
+            *out_len = total;
+            *in_used = (size_t)in.stream_byte(seq_blocks_bytes(eb));
         }
-        if (status < 0) set_error("%s", tk.msg);
-        int rc = history(aout, &h, &hl);
-        if (rc == ZNG_ROCM_OK) rc = inflate_tokens_to_device(&tk, h, hl, d_dst + aout, st);
-        zng_rocm_inflate_tokens_free(&tk);
-        return done(rc != ZNG_ROCM_OK ? rc : status);
+        if (rc != ZNG_ROCM_OK) return rc;
+        if (status == 1) {
+            *out_len = total;
+            *in_used = (size_t)in.stream_byte(tk_used);
+            return 1;
+        }
+        piece_after_blocks(s, in, eb, total, piece_bytes);
+        if (t_index_sink) t_index_sink->cands.emplace_back(s.abit, s.aout);
     }
 }
 
@@ -1362,9 +1358,7 @@ extern "C" {
 int zng_rocm_inflate_large_pieces_dev(const uint8_t *d_src, size_t src_len, const uint8_t *d_window, uint32_t window_len,
                                       uint8_t *d_dst, size_t dst_cap, uint64_t *out_len, size_t *in_used, size_t piece_bytes,
                                       uint32_t flags, void *stream) {
-    inflate_large_forget_parts();
-    t_large_pieces = 0;
-    t_large_host_bytes = 0;
+    t_last = LargeCounters{};
     if (out_len) *out_len = 0;
     if (in_used) *in_used = 0;
     if (!ctx()) {
@@ -1381,8 +1375,11 @@ int zng_rocm_inflate_large_pieces_dev(const uint8_t *d_src, size_t src_len, cons
     }
     if ((!d_src && src_len) || window_len > 32768u || (window_len && !d_window) || !out_len || !in_used) return ZNG_ROCM_EINVAL;
     DeviceGuard dev;
-    return inflate_pieces_call(d_src, src_len, d_window, window_len, d_dst, dst_cap, out_len, in_used,
-                               piece_bytes ? piece_bytes : kPieceDefault, flags != 0, (hipStream_t)stream);
+    LargeCounters c;
+    const int rc = inflate_pieces_call(d_src, src_len, d_window, window_len, d_dst, dst_cap, out_len, in_used,
+                                       piece_bytes ? piece_bytes : kPieceDefault, flags != 0, (hipStream_t)stream, c);
+    t_last = c;
+    return rc;
 }
 
 int zng_rocm_inflate_large_dev(const uint8_t *d_src, size_t src_len, const uint8_t *d_window, uint32_t window_len,
@@ -1417,9 +1414,7 @@ namespace zr {
 // framing_large.hip answers a wrapped member whose header it refuses without reaching the calls above: the calling
 // thread's last_* counters then say that nothing ran
 void inflate_large_reset_counters() {
-    inflate_large_forget_parts();
-    t_large_pieces = 0;
-    t_large_host_bytes = 0;
+    t_last = LargeCounters{};
     t_batch_rounds = t_batch_part_launches = 0;
 }
 }  // namespace zr
@@ -1547,13 +1542,9 @@ static int rounds_run(zng_rocm_inflate_large_job *jobs, size_t njobs, size_t rou
         if (counting) host.clear();                      // (sized above)
         for (size_t i : host) {
             zng_rocm_inflate_large_job &j = jobs[i];
-            std::vector<uint8_t> copy(j.src_len ? j.src_len : 1);
-            int s = ZNG_ROCM_OK;
-            if (j.src_len && (hipMemcpyAsync(copy.data(), j.d_src, j.src_len, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                              hipStreamSynchronize(st) != hipSuccess)) {
-                set_error("zng_rocm_inflate_large_streams_dev: copying job %zu to the host failed", i);
-                s = ZNG_ROCM_EHIP;
-            }
+            std::vector<uint8_t> copy;
+            int s = host_copy(copy, j.d_src, j.src_len, st);
+            if (s != ZNG_ROCM_OK) set_error("zng_rocm_inflate_large_streams_dev: copying job %zu to the host failed", i);
             uint64_t n = 0;
             size_t used = 0;
             const char *msg = nullptr;
@@ -1575,7 +1566,7 @@ namespace zr {
 int inflate_large_sizes_raw(zng_rocm_inflate_large_job *jobs, size_t njobs, size_t round_bytes, bool single, hipStream_t st) {
     inflate_large_reset_counters();
     const int rc = rounds_run(jobs, njobs, round_bytes, false, true, st);
-    if (single && njobs == 1 && jobs[0].status == 1) t_large_parts = (int)jobs[0].parts;
+    if (single && njobs == 1 && jobs[0].status == 1) t_last.parts = (int)jobs[0].parts;
     return rc;
 }
 }  // namespace zr

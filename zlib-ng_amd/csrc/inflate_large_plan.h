@@ -1,8 +1,10 @@
 // inflate_large_plan.h -- the host steps between the kernel launches of inflate_large.hip (pass_run, and the finder in front
 // of it).  Plain C++ over integers and the part tables, no HIP: every rule that decides what a valid result is -- how a
 // finder pass is cut into work items, how many survivors it has room for and whose they are, which candidates become
-// starts, where guesses go, how large a slot is, where the tables lie in scratch, which parts run again, which parts are genuine, how parts are grouped for the context chain and laid out in the symbol array -- lives here, and a
-// CPU test (tests/test_large_plan_cpu.py) drives them with hand-written tables.
+// starts, where guesses go, how large a slot is, where the tables lie in scratch, which parts run again, which parts are
+// genuine, how parts are grouped for the context chain and laid out in the symbol array, and how the pieces loop steps from
+// one piece to the next (where a piece ends, where its pass's buffer begins, which bytes are its history, what the sequential
+// decoder is given) -- lives here, and a CPU test (tests/test_large_plan_cpu.py) drives them with hand-written tables.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -12,6 +14,7 @@
 #include <vector>
 
 #include "inflate_dev_types.h"
+#include "inflate_large_limits.h"
 
 namespace zr {
 
@@ -493,6 +496,158 @@ inline SymTables symbol_tables(std::vector<SymStream> &streams) {
     }
     if (!t.copies.empty()) t.segs.insert(t.segs.end(), {0, t.v_end, 0});
     return t;
+}
+
+// ---- pieces: the loop of zng_rocm_inflate_large_pieces_dev --------------------------------------------------------------
+// What the loop carries from one turn to the next.  A turn is a device pass over the next piece (piece_next, then
+// piece_after_pass or piece_halve), or the sequential decoder from the anchor (seq_input .. piece_after_blocks).
+struct PiecesState {
+    uint64_t bit = 0, key = 0;        // where the next piece begins (a bit of the stream) and that start's key (0 a block start, 1
+                                      // inside a fixed-code block, H + 2 inside the dynamic block whose header is at stream bit H)
+    int      fin = -1;                // PiecePass::fin0 of the next pass
+    uint64_t produced = 0;            // bytes delivered
+    uint64_t abit = 0, aout = 0;      // the anchor: the last BLOCK start delivered up to, and the output in front of it
+    uint64_t p = 0;                   // the piece size of the next pass: piece_bytes, halved while passes ask for it
+};
+inline PiecesState pieces_begin(uint64_t piece_bytes) {
+    PiecesState s;
+    s.p = piece_bytes;
+    return s;
+}
+
+// The next piece: [bit >> 3, end) of the stream; one that would leave less than a quarter piece behind it ends a quarter
+// piece early (so the last piece is never a sliver).  The pass's buffer [base, end) begins at the piece, or at the header of
+// the dynamic block its first start lies in when that is in front of it, rounded down to 256 bytes; bit positions of the
+// pass -- the first start, a key of 2 and more -- count from the buffer's first byte (keys 0 and 1 are no positions).
+struct NextPiece {
+    bool      any = false;            // input is left at the state's bit (else the sequential decoder says how the stream ends)
+    uint64_t  end = 0, base = 0;
+    uint64_t  start_bit = 0;          // the state's bit as a bit of the buffer: start_bit >> 3 == pp.scan_lo
+    PiecePass pp;                     // in fields set
+    uint64_t len() const { return end - base; }
+    uint64_t stream_byte(uint64_t used) const { return base + used; }      // a byte count of the buffer, as one of the stream
+};
+inline NextPiece piece_next(const PiecesState &s, uint64_t src_len, uint64_t piece_bytes) {
+    NextPiece n;
+    const uint64_t sbyte = s.bit >> 3;
+    n.any = sbyte < src_len;
+    if (!n.any) return n;
+    n.end = sbyte + s.p;
+    if (n.end >= src_len) n.end = src_len;
+    else if (src_len - n.end < s.p / 4) n.end = src_len - s.p / 4;
+    n.base = (s.key >= 2 ? std::min<uint64_t>(sbyte, (s.key - 2) >> 3) : sbyte) & ~(uint64_t)255;
+    n.start_bit = s.bit - 8 * n.base;
+    n.pp.scan_lo = sbyte - n.base;
+    n.pp.key0 = s.key >= 2 ? s.key - 8 * n.base : s.key;
+    n.pp.fin0 = s.fin;
+    n.pp.last = n.end == src_len;
+    n.pp.q = piece_bytes;
+    return n;
+}
+
+// After a pass that returned 1 with `out` bytes and `used` bytes of its buffer: the stream ended in the piece (done, with the
+// call's in_used), or the next piece begins where the chain stopped -- that start and its key back in stream positions, the
+// BFINAL the chain carried to it, the full piece size again; a stop at a block start moves the anchor there.
+struct PieceStep {
+    bool     done = false;
+    uint64_t in_used = 0;
+    bool     anchored = false;        // the anchor moved (to the state's bit and produced)
+};
+inline PieceStep piece_after_pass(PiecesState &s, const NextPiece &n, uint64_t out, uint64_t used, uint64_t piece_bytes) {
+    PieceStep r;
+    s.produced += out;
+    if (!n.pp.stopped) {
+        r.done = true;
+        r.in_used = n.stream_byte(used);
+        return r;
+    }
+    s.bit = n.pp.next_bit + 8 * n.base;
+    s.key = n.pp.next_key >= 2 ? n.pp.next_key + 8 * n.base : n.pp.next_key;
+    s.fin = n.pp.next_fin;
+    s.p = piece_bytes;
+    r.anchored = s.key == 0;
+    if (r.anchored) {
+        s.abit = s.bit;
+        s.aout = s.produced;
+    }
+    return r;
+}
+// the block starts a pass recorded (Chain::cands: the pass's own positions) as positions of the stream and the call's output
+inline void piece_cands(const std::vector<std::pair<unsigned long long, uint64_t>> &pass, const NextPiece &n, const PiecesState &s,
+                        std::vector<std::pair<uint64_t, uint64_t>> &out) {
+    for (const auto &c : pass) out.emplace_back(c.first + 8 * n.base, s.produced + c.second);
+}
+// A pass over its scratch caps (PiecePass::halve): the same start with half the piece, while that is a piece the call takes
+inline bool piece_halve(PiecesState &s) {
+    if (s.p / 2 < kPieceMin) return false;
+    s.p /= 2;
+    return true;
+}
+
+// The history of a pass (or of the sequential decoder's tokens) at output position `pos`: the last min(32768, pos +
+// window_len) bytes in front of it.  They lie in the call's output, or -- nothing delivered yet -- are the caller's window as
+// it stands, or are spliced: the window's last `from_window` bytes, then the `from_dst` bytes delivered.
+struct PieceHistory {
+    enum Where { kInDst, kWindow, kSpliced };
+    uint32_t len = 0;
+    Where    where = kInDst;
+    uint64_t dst_off = 0;             // kInDst: where it begins in the output
+    uint64_t window_off = 0, from_window = 0, from_dst = 0;       // kSpliced
+};
+inline PieceHistory piece_history(uint64_t pos, uint32_t window_len) {
+    PieceHistory h;
+    const uint64_t n = std::min<uint64_t>(32768u, pos + window_len);
+    h.len = (uint32_t)n;
+    if (pos >= n) {
+        h.dst_off = pos - n;
+    } else if (pos == 0) {
+        h.where = PieceHistory::kWindow;
+    } else {
+        h.where = PieceHistory::kSpliced;
+        h.from_window = n - pos;
+        h.window_off = window_len - h.from_window;
+        h.from_dst = pos;
+    }
+    return h;
+}
+
+// The sequential decoder takes the stream from the anchor: byte a0, bit sb of it.  It is given complete blocks' worth of input:
+// at least two pieces, and the piece the device could not do whole; twice as much while no block completes (status 0, the
+// end bit still sb) and more input exists.
+struct SeqInput {
+    uint64_t a0 = 0, sb = 0, span = 0;
+    uint64_t len(uint64_t src_len) const { return std::min<uint64_t>(src_len - a0, span); }
+    uint64_t stream_byte(uint64_t used) const { return a0 + used; }
+};
+inline SeqInput seq_input(const PiecesState &s) {
+    SeqInput in;
+    in.a0 = s.abit >> 3;
+    in.sb = s.abit & 7u;
+    in.span = std::max<uint64_t>(2 * s.p, (s.bit >> 3) - in.a0 + s.p);
+    return in;
+}
+inline bool seq_wants_more(SeqInput &in, uint64_t src_len, int status, uint64_t eb) {
+    if (!(status == 0 && eb == in.sb && in.len(src_len) < src_len - in.a0)) return false;
+    in.span *= 2;
+    return true;
+}
+// The blocks form's answer stands when it ended the stream (1), completed a block (0, the end bit moved) or ran out of memory
+// (-4); a data error, or the end of the input inside the first block, is decoded once more in the stream form, whose status,
+// message and counts are the reference's.
+inline bool seq_stream_form(int status, uint64_t eb, uint64_t sb) {
+    return status != 1 && !(status == 0 && eb != sb) && status != -4;
+}
+inline uint64_t seq_blocks_bytes(uint64_t eb) { return (eb + 7) >> 3; }          // input bytes the complete blocks took, from a0
+// After the sequential decoder's complete blocks, which end at bit `eb` (counted from byte a0) with `produced` bytes delivered
+// in all (the anchor's and theirs): the next piece begins there, at a block start, which is the new anchor.
+inline void piece_after_blocks(PiecesState &s, const SeqInput &in, uint64_t eb, uint64_t produced, uint64_t piece_bytes) {
+    s.produced = produced;
+    s.bit = 8 * in.a0 + eb;
+    s.key = 0;
+    s.fin = -1;
+    s.abit = s.bit;
+    s.aout = s.produced;
+    s.p = piece_bytes;
 }
 
 }  // namespace zr
